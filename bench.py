@@ -15,7 +15,12 @@ torch.distributed.run`, spawned before this process touches a GPU); under an ext
 torch.distributed.run (WORLD_SIZE set) it is a rank.  --scaling strong (default: BASELINE.json
 configs[3], "2 M x 8 sharded across 8 MI355X": --rows is the GLOBAL row count, rows/N per rank) or
 weak (--rows per rank); for N > 1 the other of the two is measured as well, after the first, and reported
-under "other_scaling" (same K and W; `value` is always the --scaling one).
+under "other_scaling" (same K and W; `value` is always the --scaling one) by a --full run.
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds everything else, none of it part of
+`value`: the roofline and per-stage breakdown (two more passes of the K steps, with HIP events), the other scaling mode, the
+HBM-bound kernels, the theta grid, the end-to-end pipeline, the host-buffer entry and the CPU baseline (the --no-* options
+leave legs of a --full run out).  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
 
 Prints ONE JSON line on rank 0.
 """
@@ -33,6 +38,35 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured streaming)
 FP64_VALU_PEAK_TFLOPS = 78.6  # vector fp64, = 1/2 of the 157.3 TF fp32 figure in the guide
+
+
+DUMP_BYTES = 60 << 20  # --dump-outputs: the per-row arrays are cut to a sample of rows that fits (all files < 64 MB)
+
+
+def timed_outputs(outputs, sc, row0):
+    """--dump-outputs: what the caller of the timed path receives from one step, as float64 host arrays: every per-row column
+    it asked for and the scalars returned beside them.  Above DUMP_BYTES the columns hold a fixed sample of rows (seeded,
+    ascending), the same sample for the same --rows, so two builds compare row for row.  NA stays out of the numbers: a sampled
+    row with a non-finite value in any column (an all-zero row: dispersion ... pvalue are NA, as in DESeq2) is listed in
+    `na_row_index` instead of the columns, `row_index` holds the global row numbers of the rows the columns hold, and an NA
+    scalar (`sumDeviance` once a row is all zero: sum() without na.rm, chicdiff.R:1647) is not written."""
+    import torch
+
+    cols = list(outputs.values())
+    n = cols[0].numel()
+    cap = DUMP_BYTES // (8 * (len(cols) + 1))
+    rows = np.arange(n) if n <= cap else np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+    idx = torch.from_numpy(rows).to(cols[0].device)
+    vals = {k: v[idx].double() for k, v in outputs.items()}
+    defined = torch.stack([torch.isfinite(v) for v in vals.values()]).all(0).cpu().numpy()
+    out = {k: v.cpu().numpy()[defined] for k, v in vals.items()}
+    out["row_index"] = (rows[defined] + row0).astype(np.float64)
+    out["na_row_index"] = (rows[~defined] + row0).astype(np.float64)
+    for k, v in sc.items():
+        v = np.asarray(v, dtype=np.float64)
+        if np.isfinite(v).all():
+            out[k] = v
+    return out
 
 
 def algorithmic_bytes(S):
@@ -416,12 +450,19 @@ def main():
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong")
     ap.add_argument("--samples", type=int, default=8)
     ap.add_argument("--theta", type=float, default=0.5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-hbm-kernels", action="store_true", help="skip the window-sum / offsets / count-join side measurement")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the resident default-mode pipeline leg (region universe ... IHW application)")
+    ap.add_argument("--full", action="store_true", help="after the headline, every other measurement: roofline, per-stage breakdown, "
+                    "other scaling mode, HBM kernels, theta grid, end to end, host-buffer entry, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float64; with "
+                    "--gpus N > 1 rank 0's rows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-hbm-kernels", action="store_true", help="--full: skip the HBM-bound kernels' side measurement and with it "
+                    "the theta grid, end-to-end and host-buffer legs")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full: skip the resident default-mode pipeline leg (region universe ... IHW application)")
     ap.add_argument("--cpu-sample-rows", type=int, default=400_000)
-    ap.add_argument("--one-mode", action="store_true", help="N > 1: skip the second measurement (the other of strong / weak scaling)")
+    ap.add_argument("--one-mode", action="store_true", help="--full, N > 1: skip the second measurement (the other of strong / weak scaling)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     force_dist = os.environ.get("CHICDIFF_BENCH_FORCE_DIST") == "1"  # rehearse the N > 1 code path with a 1-rank group
     share_gpu = os.environ.get("CHICDIFF_BENCH_SHARE_GPU") == "1"    # rehearsal on a one-GPU box: all ranks on device 0, gloo transport
@@ -517,8 +558,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(scaling, breakdown=True):
-        """W warm-up steps, then exactly K timed steps between two barriers; the MAX over ranks."""
+    def measure(scaling, full=False, dump=False):
+        """W warm-up steps, then exactly K timed steps between two barriers; the MAX over ranks.  dump: the last timed step's
+        outputs on the host (timed_outputs).  full: two more passes of the same K steps, not part of `value` (below)."""
         if scaling == "strong":
             lo, hi = shard_bounds(args.rows, fake_world if fake_world > 1 else world, rank)
             n, n_global = hi - lo, args.rows
@@ -535,28 +577,30 @@ def main():
 
         for _ in range(args.warmup):
             step()
-        # HIP events on the library's stream around the gene-wise line search only — the dominant kernel of every configuration
-        # measured (checked against the second pass below) and the one the roofline is quoted on: an event is a packet of its own
-        # on the stream, each bracketed stage costs the step ~12 us (rocprofv3 kernel trace, profiles/r05_kernel_gaps_250000x8.txt;
-        # round 4 bracketed three stages here, all ~20 cost 0.09 ms: tools/timing_overhead.py), so the full breakdown comes from a
-        # second pass of the same steps
-        ctx.enable_timing(3)
-        ktimes = {}
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
             _, sc = step()
-            for k, (ms, cnt) in ctx.kernel_times().items():
-                a = ktimes.setdefault(k, [0.0, 0]); a[0] += ms; a[1] += cnt
         barrier()
         elapsed = time.perf_counter() - t0
-        ctx.enable_timing(False)
         if dist is not None:
             t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if share_gpu else "cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        kfull, coll = {}, {}
-        if breakdown:  # the same K steps again, every stage and every collective bracketed (not part of `value`)
+        dumped = timed_outputs(outputs, sc, lo) if dump else None
+        ktimes, kfull, coll = {}, {}, {}
+        if full:
+            # HIP events on the library's stream around the gene-wise line search only — the dominant kernel of every configuration
+            # measured (checked against the breakdown pass below) and the one the roofline is quoted on: an event is a packet of its
+            # own on the stream, each bracketed stage costs the step ~12 us (profiles/r05_kernel_gaps_250000x8.txt; all ~20 stages
+            # cost 0.09 ms: tools/timing_overhead.py), so the full breakdown comes from a pass of its own
+            ctx.enable_timing(3)
+            for _ in range(args.steps):
+                step()
+                for k, (ms, cnt) in ctx.kernel_times().items():
+                    a = ktimes.setdefault(k, [0.0, 0]); a[0] += ms; a[1] += cnt
+            ctx.enable_timing(False)
+            # the same K steps again, every stage and every collective bracketed
             ctx.enable_timing(1)
             for _ in range(args.steps):
                 step()
@@ -566,10 +610,15 @@ def main():
                     a = coll.setdefault(k, [0, 0.0, 0.0]); a[0] += cnt; a[1] += ms; a[2] += nbytes
             ctx.enable_timing(False)
             barrier()
-        return dict(elapsed=elapsed, n=n, n_global=n_global, ktimes=ktimes, kfull=kfull, coll=coll, sc=sc, d=d, dk=dk, dfm=dfm, group=group)
+        return dict(elapsed=elapsed, n=n, n_global=n_global, ktimes=ktimes, kfull=kfull, coll=coll, sc=sc, d=d, dk=dk, dfm=dfm, group=group,
+                    dumped=dumped)
 
-    m = measure(args.scaling)
+    m = measure(args.scaling, full=args.full, dump=bool(args.dump_outputs) and rank == 0)
     elapsed, n, n_global, ktimes, kfull, sc, d, dk, dfm, group = (m[k] for k in ("elapsed", "n", "n_global", "ktimes", "kfull", "sc", "d", "dk", "dfm", "group"))
+    if m["dumped"] is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, v in m.pop("dumped").items():
+            np.save(os.path.join(args.dump_outputs, k + ".npy"), v)
 
     ms_per_step = elapsed / args.steps * 1e3
     value = n_global / (elapsed / args.steps)
@@ -577,12 +626,37 @@ def main():
     if fake_world > 1:  # a rehearsal: `value` stays what was MEASURED (this rank's rows / its step); the x N projection has a key of its own
         projected_value = value
         value = n / (elapsed / args.steps)
+    result = {
+        "metric": "interactions/sec NB-GLM Wald test", "value": round(value, 1), "unit": "interactions/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"synthetic {n_global} interactions x {S} samples ({S // 2}v{S - S // 2}), "
+                               f"size factors + offsets(theta={args.theta}) + dispersions + Wald, design ~condition",
+                   "rows_per_gpu": n, "samples": S, "global_rows": n_global,
+                   "parallelism": (f"rows-sharded x{world}" if fake_world <= 1 else
+                                   f"REHEARSAL on one GPU of one rank's step of a x{fake_world} run: {n} rows here, trend + MAD on all {fake_world} x {n} gathered rows, "
+                                   f"1-rank RCCL group; value = THIS rank's rows / its step (measured); projected_value = global rows / this step, a projection before inter-GPU latency"),
+                   "collectives": collectives, "ranks_in_communicator": comm_ranks},
+        "timed_outputs": want,
+        "fit_status": int(sc["status"]),
+    }
+    if projected_value is not None:
+        result["projected_value"] = round(projected_value, 1)
 
-    # dominant kernel = largest total HIP-event time inside the timed region
+    def report():
+        if rank == 0:
+            print(json.dumps(result))
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not args.full:
+        return report()
+
+    # dominant kernel = largest total HIP-event time of the line-search pass
     dom = max(((k, v) for k, v in ktimes.items() if k != "allreduce"), key=lambda kv: kv[1][0])
     dom_name, (dom_ms, dom_launches) = dom
     avg_ms = dom_ms / dom_launches
-    if kfull:  # the stage bracketed in the timed region must be the largest of the fully bracketed pass
+    if kfull:  # the stage bracketed in the line-search pass must be the largest of the fully bracketed pass
         top = max(((k, v) for k, v in kfull.items() if k not in ("allreduce", "allgather")), key=lambda kv: kv[1][0])[0]
         if top != dom_name:
             print(f"bench.py: WARNING the largest stage of the breakdown pass is {top}, the roofline is quoted on {dom_name}", file=sys.stderr)
@@ -632,35 +706,21 @@ def main():
                         "launch the SIMDs spend executing VALU instructions (SQ_ACTIVE_INST_VALU x 4 cycles / (duration x 1024 SIMDs x 2.4 GHz), "
                         "replayed from profiles/pmc_traffic.json: counters cannot be read inside a timed run); achieved / peak / frac stay the HBM "
                         "figures BASELINE.json's north_star asks for (algorithmic bytes / launch duration against 8 TB/s)"}
-    result = {
-        "metric": "interactions/sec NB-GLM Wald test", "value": round(value, 1), "unit": "interactions/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"synthetic {n_global} interactions x {S} samples ({S // 2}v{S - S // 2}), "
-                               f"size factors + offsets(theta={args.theta}) + dispersions + Wald, design ~condition",
-                   "rows_per_gpu": n, "samples": S, "global_rows": n_global,
-                   "parallelism": (f"rows-sharded x{world}" if fake_world <= 1 else
-                                   f"REHEARSAL on one GPU of one rank's step of a x{fake_world} run: {n} rows here, trend + MAD on all {fake_world} x {n} gathered rows, "
-                                   f"1-rank RCCL group; value = THIS rank's rows / its step (measured); projected_value = global rows / this step, a projection before inter-GPU latency"),
-                   "collectives": collectives, "ranks_in_communicator": comm_ranks},
+    result.update({
         "roofline": roofline,
         "kernels_ms": {k: [round(v[0] / args.steps, 4), v[1] // args.steps] for k, v in sorted(kfull.items(), key=lambda kv: -kv[1][0]) if k != "allreduce"},
-        "kernels_ms_note": "second pass of the same K steps with every stage bracketed by HIP events (costs 0.09 ms per step); the timed region brackets only the gene-wise line search (roofline.avg_launch_ms); since round 5 the offsets are formed inside prep (no stage of their own)",
+        "kernels_ms_note": "a pass of the same K steps with every stage bracketed by HIP events (costs 0.09 ms per step), after a pass that brackets only the gene-wise line search (roofline.avg_launch_ms); the timed steps carry no events; since round 5 the offsets are formed inside prep (no stage of their own)",
         "collectives_per_step": ({"count": kfull["allreduce"][1] // args.steps, "ms": round(kfull["allreduce"][0] / args.steps, 4),
                                   "note": "sum-all-reduces of one fit on this rank and their summed duration on the stream (already inside the stages' kernels_ms)"}
                                  if "allreduce" in kfull else None),
         "collectives_per_rank": coll_all if dist is not None else None,
-        "timed_outputs": want,
-        "fit_status": int(sc["status"]),
-    }
-    if projected_value is not None:
-        result["projected_value"] = round(projected_value, 1)
+    })
     if world > 1 and not args.one_mode:
         # the other way of scaling, measured in the same run with the same K / W: `value` follows --scaling (default strong =
         # BASELINE.json configs[3], 2 M rows in all); this is the same metric with the per-GPU work fixed instead
         other = "weak" if args.scaling == "strong" else "strong"
         del m, dk, dfm, d
-        mo = measure(other, breakdown=False)
+        mo = measure(other)
         result["other_scaling"] = {"scaling": other, "value": round(mo["n_global"] / (mo["elapsed"] / args.steps), 1), "unit": "interactions/s",
                                    "ms_per_step": round(mo["elapsed"] / args.steps * 1e3, 3), "rows_per_gpu": mo["n"], "global_rows": mo["n_global"],
                                    "steps": args.steps, "warmup": args.warmup}
@@ -698,10 +758,7 @@ def main():
                       f"{dt1:.1f} s on 1 of {os.cpu_count() or 1} cores",
         }
         result["gpu_over_cpu_1core"] = round(value / v1, 1)
-    if rank == 0:
-        print(json.dumps(result))
-    if dist is not None:
-        dist.destroy_process_group()
+    report()
 
 
 if __name__ == "__main__":

@@ -3,6 +3,7 @@ C compiler and text can: the shim compiles against declaration-only stand-ins fo
 syntax / prototype check that PINS NOTHING about R's behaviour), every .Call in the R sources names a registered
 routine with the registered number of arguments, every library entry point the shim uses is declared in
 include/chicdiff_hip.h, and the R file defines the reference's DESeq2Wrap signature."""
+import hashlib
 import os
 
 import pytest
@@ -148,34 +149,69 @@ def test_r_host_enters_through_the_patch_and_restates_none_of_the_reference_bodi
                       ".hipApplyIHWweights", ".hipDeviceIndex"}, called
 
 
-def test_patch_applies_to_the_reference_and_r_host_shares_few_lines_with_it(tmp_path):
-    """Where the reference tree exists (the authoring container; never the GPU box): `patch --dry-run` of the committed hunks
-    succeeds, and — VERDICT r03's line-overlap measure: comments and whitespace stripped, package prefixes removed — every
-    file under r/R/ shares fewer than 10 code lines with Chicdiff/R/chicdiff.R."""
-    import shutil
-    ref_dir = "/root/reference/Chicdiff"
-    if not os.path.exists(os.path.join(ref_dir, "R", "chicdiff.R")):
-        pytest.skip("reference tree not present")
-    if shutil.which("patch"):
-        shutil.copytree(ref_dir, tmp_path / "Chicdiff")
-        subprocess.run(["patch", "-p1", "--dry-run", "-i", PATCH], cwd=tmp_path, check=True, capture_output=True)
+def _digest(line):
+    """what tests/golden/reference_chicdiff_R_digests.json holds for a line of the reference (tools/make_reference_line_digests.py)"""
+    return hashlib.sha256(line.encode("utf-8")).hexdigest()[:16]
 
-    def code_lines(path):
-        out = []
-        for l in open(path, errors="replace"):
-            l = re.sub(r"#.*$", "", l)
-            l = re.sub(r"\b(data\.table|stats|IHW|cowplot|ggplot2|Chicago|DESeq2|utils|methods)::", "", l)
-            l = re.sub(r"\s+", "", l)
-            # not statements one could have written differently: a lone brace / `}else{`, and message() — a drop-in must emit the
-            # reference's progress messages verbatim (SURVEY.md 8b: "Side effects: messages")
-            if len(l) > 3 and l != "}else{" and not l.startswith("message("):
-                out.append(l)
-        return out
 
-    ref_lines = set(code_lines(os.path.join(ref_dir, "R", "chicdiff.R")))
+def _code_lines(lines):
+    """VERDICT r03's line-overlap measure: comments and whitespace stripped, package prefixes removed"""
+    out = []
+    for l in lines:
+        l = re.sub(r"#.*$", "", l)
+        l = re.sub(r"\b(data\.table|stats|IHW|cowplot|ggplot2|Chicago|DESeq2|utils|methods)::", "", l)
+        l = re.sub(r"\s+", "", l)
+        # not statements one could have written differently: a lone brace / `}else{`, and message() — a drop-in must emit the
+        # reference's progress messages verbatim (SURVEY.md 8b: "Side effects: messages")
+        if len(l) > 3 and l != "}else{" and not l.startswith("message("):
+            out.append(l)
+    return out
+
+
+def _hunks(patch_text):
+    """(target file, [(old start, old-side lines, new-side line count)]) of a one-file unified diff"""
+    lines = patch_text.split("\n")
+    target, hunks, i = None, [], 0
+    while i < len(lines):
+        m = re.match(r"@@ -(\d+)(?:,(\d+))? \+\d+(?:,(\d+))? @@", lines[i])
+        if lines[i].startswith("--- a/"):
+            target = lines[i][len("--- a/"):].split("\t")[0]
+        if not m:
+            i += 1
+            continue
+        start, n_old, n_new = int(m.group(1)), int(m.group(2) or 1), int(m.group(3) or 1)
+        old, new_count, i = [], 0, i + 1
+        while len(old) < n_old or new_count < n_new:
+            assert i < len(lines), ("hunk at", start, "ends early")
+            l = lines[i]
+            assert l[:1] in (" ", "-", "+", "\\"), ("hunk at", start, "malformed line", l)
+            if l[:1] in (" ", "-"):
+                old.append(l[1:])
+            if l[:1] in (" ", "+"):
+                new_count += 1
+            i += 1
+        assert (len(old), new_count) == (n_old, n_new), ("hunk at", start, "line counts differ from its header")
+        hunks.append((start, old, new_count))
+    return target, hunks
+
+
+def test_patch_applies_to_the_reference_and_r_host_shares_few_lines_with_it():
+    """Against the reference's Chicdiff/R/chicdiff.R as digested in tests/golden/reference_chicdiff_R_digests.json: every hunk
+    of the committed patch finds its context and removed lines at the line numbers it names (what `patch` needs to apply it
+    without offset or fuzz), and every file under r/R/ shares fewer than 10 code lines with the reference."""
+    import json
+    ref = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_chicdiff_R_digests.json")))
+    target, hunks = _hunks(open(PATCH).read())
+    assert target == ref["source"], (target, ref["source"])
+    assert len(hunks) >= 7
+    for start, old, _ in hunks:
+        at = ref["lines"][start - 1:start - 1 + len(old)]
+        assert [_digest(l) for l in old] == at, ("hunk at line", start, "does not match the reference there")
+
+    ref_lines = set(ref["code_lines"])
     for path in _r_host_sources():
-        mine = code_lines(path)
-        same = [l for l in mine if l in ref_lines]
+        mine = _code_lines(open(path, errors="replace"))
+        same = [l for l in mine if _digest(l) in ref_lines]
         print(os.path.basename(path), "code lines", len(mine), "identical to a reference line:", len(same))
         assert len(same) < 10, (path, same)
 

@@ -10,7 +10,7 @@ df["dur"] = (df["End_Timestamp"] - df["Start_Timestamp"]) / 1e3
 df["gap"] = (df["Start_Timestamp"] - df["End_Timestamp"].shift(1)) / 1e3
 # the last full step: from the last prep16 / row_ratio kernel on
 starts = df.index[df["name"].str.startswith("row_ratio")]
-which = int(sys.argv[2]) if len(sys.argv) > 2 else -2   # which step (index into the row_ratio launches; bench.py: W warm-ups, K timed steps, K fully bracketed ones)
+which = int(sys.argv[2]) if len(sys.argv) > 2 else -2   # which step (index into the row_ratio launches; a plain bench.py: W warm-ups, then K timed steps)
 if len(starts) >= 2:
     a, b = starts[which], starts[which + 1]
     step = df.iloc[a:b]
