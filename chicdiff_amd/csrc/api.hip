@@ -189,7 +189,7 @@ int chicdiff_hip_set_option(chicdiff_hip_ctx *c, const char *name, int64_t value
     else if (k == "line_search_prio" && value >= 0 && value <= 100) c->opt_prio = (int)value;
     else if (k == "line_search_chunk" && (value == 0 || (value >= 8 && value <= 64))) c->opt_chunk = (int)value;
     else if (k == "line_search_classes_a" && value >= 0 && value <= 6) c->opt_classes_a = (int)value;
-    else if (k == "line_search_schedule" && (value == 0 || value == 1)) c->opt_schedule = (int)value;
+    else if (k == "line_search_schedule" && value >= 0 && value <= 4 && value != 2) c->opt_schedule = (int)value;  // (2 is what the theta grid's concurrent fits get)
     else if (k == "line_search_deal" && value >= 0 && value <= 64) c->opt_deal = (int)value;
     else if (k == "local_trend_substitute" && (value == 0 || value == 1)) c->opt_no_local_substitute = value ? 0 : 1;
     else if (k == "sharded_trend_gather" && (value == 0 || value == 1)) c->opt_trend_gather = (int)value;
@@ -1729,6 +1729,15 @@ extern "C" int chicdiff_hip_selftest_r_random(int32_t kind, uint32_t seed, doubl
     if (kind == 3 && !(a > 0 && b > 0)) return CHICDIFF_E_INVALID;
     RStream r(seed);
     for (int64_t i = 0; i < n; i++) out[i] = kind == 0 ? r.unif() : kind == 1 ? r.norm() : kind == 2 ? r.expo() : r.gamma(a, b);
+    return CHICDIFF_OK;
+}
+// the gene-wise schedule's class function (common.h), evaluated on the host: class index of each score, and in `bounds` (7 values) the
+// first class index that is not dealt out statically for 0 .. 6 of the half-decade classes
+extern "C" int chicdiff_hip_selftest_sched_class(int32_t mode, double min_disp, const double *alpha_init, const double *group_mean, int64_t n,
+                                                 int32_t *cls_out, int32_t *bounds) {
+    if (n < 0 || (n > 0 && (!alpha_init || !group_mean || !cls_out)) || mode < 1 || mode > 4) return CHICDIFF_E_INVALID;
+    for (int64_t i = 0; i < n; i++) cls_out[i] = cd::sched_class(alpha_init[i], group_mean[i], min_disp, mode);
+    if (bounds) for (int a = 0; a <= 6; a++) bounds[a] = cd::sched_classes_a(a, mode);
     return CHICDIFF_OK;
 }
 extern "C" int chicdiff_hip_selftest_prior_mc(int32_t df, const double *hist40, double *dens_out, double *prior_var_out) {

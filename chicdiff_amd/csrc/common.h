@@ -59,7 +59,8 @@ struct Opts {
     // tuning (chicdiff_hip_set_option): not part of the algorithm, results do not depend on them
     int32_t spread = 1;     // line search: samples-across-lanes evaluation for straggler waves (0 = row per lane only)
     int32_t min_waves = 0;  // line search: waves per SIMD (2 .. 4; 0 = by launch_disp's rule)
-    int32_t schedule = 1;   // gene-wise line search / IRLS: visit the rows likely-long first (0 = natural order; 2 = class order through the queue only)
+    int32_t schedule = 1;   // gene-wise line search / IRLS: visit the rows likely-long first (0 = natural order; 2 = class order through the queue only;
+                            // gene-wise only: 3 = the six half-decade classes of rounds 3-6, 4 = minDisp starts last instead of in front of the score >= 3.16 rows)
     int32_t deal = 0;       // ... entries per group of its static deal (0 = chosen from the number of entries per wave)
     int32_t chunk = 0;      // line search: rows per dequeue (0 = chosen from the row count; 8 .. 64)
     int32_t classes_a = 0;  // gene-wise line search: score classes dealt out statically (0 = the default, 2; 1 .. 6)
@@ -70,27 +71,79 @@ struct Opts {
 
 // ---- schedule of a row-queue kernel (disp_kernels.hip order_*): rows in class order; the class counts per tile of rows come from
 // the kernel that writes the classes (disp_init for the gene-wise search; wald_prep, for fits of one row per thread, for the IRLS)
-constexpr int kSchedClasses = 6, kSchedBlocks = 1024;
+constexpr int kSchedClasses = 6, kSchedBlocks = 1024;  // (the IRLS's class count: wald_prep uses four of them)
 inline void order_tiles(int64_t n, int64_t &nblk, int64_t &tile) {
     nblk = (n + 255) / 256;
     if (nblk > kSchedBlocks) nblk = kSchedBlocks;
     tile = ((n + nblk - 1) / nblk + 255) / 256 * 256;
     nblk = (n + tile - 1) / tile;
 }
+// ---- classes of the gene-wise line search's schedule (disp_kernels.hip, "schedule of the gene-wise line search") ----
+// The score alpha_init * (smaller group mean) ranks the rows by how likely they are to creep for all 100 iterations; the visit
+// order follows it in steps of 1/8 decade from 0.0316 to 10 (the half-decade edges are the literals of the six-class order of
+// rounds 3-6, so that order is the same partition, coarser).  Layout of the kSchedClassesFine = 23 class indices:
+//    0       score < 0.0316
+//    1 .. 16 the sixteen 1/8-decade steps up to 3.16      (0 .. 8: score < 0.316, the static deal "A" by default)
+//   17       the rows that start at minDisp: never long (at most ~35 evaluations, mostly rejected steps), but longer than the rows
+//            behind them (at most ~18), so the queue ends on those — empty under kSchedSix and kSchedMinDispLast
+//   18 .. 21 the four steps from 3.16 to 10
+//   22       score >= 10 (and the minDisp starts under kSchedSix and kSchedMinDispLast, where they were up to round 6)
+// mode = Opts::schedule: kSchedSix (3) keeps the six-class order (its classes sit at indices 0, 5, 9, 13, 18, 22).
+constexpr int kSchedClassesFine = 23, kSchedEdgesFine = 21, kSchedMinDispSlot = 17;
+constexpr int kSchedSix = 3, kSchedMinDispLast = 4;  // values of Opts::schedule besides 0 (off), 1 (on), 2 (queue only)
+__host__ __device__ inline int sched_class(double a0, double gmin, double minDisp, int mode) {
+    constexpr double edge[kSchedEdgesFine] = {0.0316, 0.0422, 0.0562, 0.0750, 0.1, 0.1334, 0.1778, 0.2371, 0.316, 0.4217, 0.5623,
+                                              0.7499, 1.0, 1.3335, 1.7783, 2.3714, 3.16, 4.2170, 5.6234, 7.4989, 10.0};
+    if (!(a0 > 1.5 * minDisp)) return (mode == kSchedSix || mode == kSchedMinDispLast) ? kSchedClassesFine - 1 : kSchedMinDispSlot;
+    const double s = a0 * gmin;
+    int f = 0;  // edges not above the score (a NaN score counts as the highest, as the chain of `s < edge` did)
+    if (mode == kSchedSix) {
+#pragma unroll
+        for (int k = 4; k < kSchedEdgesFine; k += 4) f += !(s < edge[k]) ? 4 : 0;
+        f += f > 0 ? 1 : 0;  // 0, 5, 9, 13, 17, 21: the first index of each half-decade
+    } else {
+#pragma unroll
+        for (int k = 0; k < kSchedEdgesFine; k++) f += !(s < edge[k]) ? 1 : 0;
+    }
+    return f < kSchedMinDispSlot ? f : f + 1;
+}
+// first class index that is NOT dealt out statically when `a` of the six half-decade classes are (option "line_search_classes_a")
+__host__ __device__ inline int sched_classes_a(int a, int mode) {
+    if (a <= 0) return 0;
+    if (a <= 3) return 1 + 4 * a;                                         // score < 0.1, 0.316, 1
+    if (a == 4) return kSchedMinDispSlot;                                 // score < 3.16
+    if (a == 5) return (mode == kSchedSix || mode == kSchedMinDispLast) ? kSchedClassesFine - 1 : kSchedMinDispSlot;  // all but the minDisp starts and what is behind them
+    return kSchedClassesFine;
+}
 #ifdef __HIPCC__
-// per-thread class counts -> hist[class][block] (wave shuffles, then one LDS add per wave and class)
-__device__ __forceinline__ void order_hist_store(const unsigned int (&mine)[kSchedClasses], unsigned int *hist) {
-    __shared__ unsigned int s_cnt[kSchedClasses];
-    if (threadIdx.x < kSchedClasses) s_cnt[threadIdx.x] = 0;
+// class counts per tile: hist[class * kSchedBlocks + block] (rows of fixed length: order_scatter_kernel reads them 16 bytes at a time)
+// per-thread class counts -> hist (wave shuffles, then one LDS add per wave and class)
+template <int NC>
+__device__ __forceinline__ void order_hist_store(const unsigned int (&mine)[NC], unsigned int *hist) {
+    __shared__ unsigned int s_cnt[NC];
+    if (threadIdx.x < NC) s_cnt[threadIdx.x] = 0;
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < kSchedClasses; k++) {
+    for (int k = 0; k < NC; k++) {
         unsigned int v = mine[k];
         for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
         if ((threadIdx.x & 63) == 0 && v) atomicAdd(&s_cnt[k], v);
     }
     __syncthreads();
-    if (threadIdx.x < kSchedClasses) hist[threadIdx.x * gridDim.x + blockIdx.x] = s_cnt[threadIdx.x];
+    if (threadIdx.x < NC) hist[threadIdx.x * kSchedBlocks + blockIdx.x] = s_cnt[threadIdx.x];
+}
+// the lanes of the wave that hold this lane's class (c < 32; a lane with valid == false has no peers): how many they are, and how many
+// of them sit below this lane — five ballots whatever the number of classes
+__device__ __forceinline__ void class_peers(int c, bool valid, int lane, unsigned int &rank, unsigned int &count) {
+    unsigned long long m = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 5; b++) {
+        const bool bit = (c >> b) & 1;
+        const unsigned long long set = __ballot(bit);
+        m &= bit ? set : ~set;
+    }
+    rank = __popcll(m & ((1ull << lane) - 1ull));
+    count = __popcll(m);
 }
 #endif
 
@@ -103,7 +156,7 @@ void launch_prep(const int32_t *counts, double *nf, FitDims d, FitWork w, Opts o
 void launch_prep_finish(FitDims d, FitWork w, double *slot, hipStream_t st);  // partials -> colsum, nnz (slot: as (hi, lo) pairs into this rank's slot instead)
 void launch_xim(FitDims d, FitWork w, const double *slots, int world, hipStream_t st);  // (the ranks' slots ->) colsum -> xim
 void launch_disp_gene(const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o, hipStream_t st);
-void launch_order_build(FitDims d, FitWork w, int classesA, bool have_hist, hipStream_t st);  // w.cls -> w.order (schedule of a row-queue kernel)
+void launch_order_build(FitDims d, FitWork w, int classesA, bool have_hist, hipStream_t st, bool fine = false);  // w.cls -> w.order (schedule of a row-queue kernel; fine: kSchedClassesFine classes)
 void launch_disp_map(const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o, hipStream_t st);
 // single rank (or the gathered rows of a sharded fit): whole trend fit, one launch; with_mad: the same launch goes on to the residuals,
 // their median and MAD and the closed-form prior variance (w.resid, sc->med / nres / mad / varLogDispEsts / dispPriorVar)

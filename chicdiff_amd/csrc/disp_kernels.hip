@@ -316,11 +316,18 @@ void launch_xim(FitDims d, FitWork w, const double *slots, int world, hipStream_
 // lowest 8 % of the scores hold 82 % of the rows with >= 50 iterations, the lowest 23 % hold 99.2 %, the lowest 54 %
 // 99.95 %; rows that start at minDisp are never long).  A row dequeued late that needs 100 + 40 serial ticks IS the tail
 // of the launch (0.5 ms of 2.0 ms at 2 M rows, 0.55 of 0.72 ms at 250 k), so the rows are visited in score order:
-//   classes 0, 1 (score < 0.1, 0.32: 8 % of the rows, 82 % of the long ones) -> "A": dealt out statically, in groups of
+//   score < 0.316 (8 % of the rows, 82 % of the long ones) -> "A": dealt out statically, in groups of
 //       eight consecutive schedule entries round-robin over the waves, so every wave starts its share of the likely-long
 //       rows at once and — when rows are few (a rank's share of a sharded fit) — is left with a handful of them, which is
 //       what the samples-across-lanes evaluation wants (250 k x 8: 0.74 ms against 0.87 ms with the queue alone);
-//   classes 2..5 (score < 1, 3.2, 10; the rest and the minDisp starts) -> "B": the dynamic queue, in class order, after A.
+//   everything else -> "B": the dynamic queue, in class order, after A.
+// Classes (round 7; sched_class() in common.h): the score in steps of 1/8 decade from 0.0316 to 10 — P(long | score) falls smoothly
+// (0.62 below 0.05, 0.001 at 1 - 1.5), and with half-decade classes (rounds 3-6) the waves that left last held a long row from the far
+// end of a wide class (score 1 - 3.16 is a third of the queue: a long row at its end starts at tick 75 of 140 and owes 100 from
+// there).  The rows that start at minDisp (12 %: never long, but up to 35 evaluations, mostly rejected steps) come in front of the
+// score >= 3.16 rows (at most ~18 evaluations), so the queue ends on the shortest rows.  2 M x 8, last wave out / p99 / median (wave
+// stamps): six classes 1.376 / 1.322 / 1.267 ms, 1/8 decade with the minDisp starts last 1.339 / 1.323 / 1.272, in front 1.338 /
+// 1.273 / 1.215 (profiles/r07_*stamps*); option "line_search_schedule" 3 / 4 selects the first two.
 // Measured at 2 M x 8 (disp_gene incl. the two order_* launches): natural order 2.08-2.11 ms, class order through the
 // queue alone 1.92, A = classes 0-1 1.88-1.90, A = 0-2 1.90-1.95, A = 0-3 1.94-2.05, everything dealt statically 2.33-2.39:
 // the drain shrinks from 0.48 to 0.14 ms, but its ticks move into the bulk (143 -> 167 per wave), which is bound by fp64
@@ -328,82 +335,109 @@ void launch_xim(FitDims d, FitWork w, const double *slots, int world, hipStream_
 // long row (~ 105 serial ticks at 3.6-4 us in the samples-across-lanes layout): 0.79 -> 0.74 ms.
 // Within a class rows keep their natural order (neighbouring lanes read neighbouring rows).  Results never depend on
 // the schedule (tests/test_gpu_parity.py::test_line_search_layouts_agree_bit_for_bit runs both).
-constexpr int kSchedClassesA = 2, kSchedDeal = 8;  // (kSchedClasses, kSchedBlocks, order_tiles(), order_hist_store(): common.h — wald_prep builds the IRLS's class counts too)
-__device__ __forceinline__ int sched_class(double a0, double gmin, double minDisp) {
-    if (!(a0 > 1.5 * minDisp)) return 5;
-    const double s = a0 * gmin;
-    return s < 0.1 ? 0 : (s < 0.316 ? 1 : (s < 1.0 ? 2 : (s < 3.16 ? 3 : (s < 10.0 ? 4 : 5))));
-}
+constexpr int kSchedClassesA = 2, kSchedDeal = 8;  // (kSchedClasses*, kSchedBlocks, sched_class(), order_tiles(), order_hist_store(): common.h — wald_prep builds the IRLS's class counts too)
 // per-block class counts over contiguous tiles of rows: hist[class][block]
+template <int NC>
 __global__ __launch_bounds__(256) void order_hist_kernel(const uint8_t *__restrict__ cls, int64_t n, int64_t tile, unsigned int *hist) {
     const int64_t lo = (int64_t)blockIdx.x * tile, hi = lo + tile < n ? lo + tile : n;
-    unsigned int mine[kSchedClasses] = {0, 0, 0, 0, 0, 0};
+    unsigned int mine[NC] = {};
     for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
         const int c = cls[i];
 #pragma unroll
-        for (int k = 0; k < kSchedClasses; k++) mine[k] += (c == k);
+        for (int k = 0; k < NC; k++) mine[k] += (c == k);
     }
-    order_hist_store(mine, hist);
+    order_hist_store<NC>(mine, hist);
 }
-// class-major exclusive scan of hist (every block recomputes the offsets it needs: 6 x 1024 entries from L2), then a
+// class-major exclusive scan of hist (every block recomputes the offsets it needs: NC x 1024 entries from L2), then a
 // stable scatter of the block's rows: order[] = class 0 rows in row order, class 1 rows, ...
+// Round 7 (23 classes for the gene-wise search): a thread loads four tiles' counts per class in one piece and the sums go through LDS
+// (no shuffle trees); each wave scatters its own quarter of the tile from bases of its own, so the row loop has no workgroup barrier and
+// costs five ballots per 64 rows whatever NC (before: one ballot per class and three barriers per 256 rows).  Per call at 2 M rows
+// (rocprof): six classes 21.5 us before, 14.0 now; 23 classes 42.8 us in the old form, 21.7 now.
+template <int NC>
 __global__ __launch_bounds__(256) void order_scatter_kernel(const uint8_t *__restrict__ cls, int64_t n, int64_t tile,
                                                             const unsigned int *__restrict__ hist, int32_t *__restrict__ order,
                                                             FitScalars *sc, int classesA) {
-    __shared__ unsigned long long s_base[kSchedClasses + 1];
-    __shared__ unsigned int s_wcnt[4][kSchedClasses];
-    const int nblk = gridDim.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // s_base[c] = number of schedule entries before this block's class-c rows = the sum of hist[0 .. c nblk + blockIdx.x); block 0
-    // also leaves |A| = sum of hist[0 .. classesA nblk) and the total.  ONE pass over the 6 nblk counts for all eight sums (round 4;
-    // before: a pass, a shuffle tree and two workgroup barriers per sum — half of the kernel's 20 us at 1024 tiles).
-    {
-        unsigned long long part[kSchedClasses + 2] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const int total = kSchedClasses * nblk, cutA = classesA * nblk;
-        for (int e = threadIdx.x; e < total; e += 256) {
-            const unsigned long long hv = hist[e];
-#pragma unroll
-            for (int c = 0; c < kSchedClasses; c++) part[c] += e < c * nblk + (int)blockIdx.x ? hv : 0ull;
-            part[kSchedClasses] += e < cutA ? hv : 0ull;
-            part[kSchedClasses + 1] += hv;
-        }
-        __shared__ unsigned long long s_part[4][kSchedClasses + 2];
-#pragma unroll
-        for (int c = 0; c < kSchedClasses + 2; c++) {
-            unsigned long long v = part[c];
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-            if (lane == 0) s_part[wave][c] = v;
-        }
-        __syncthreads();
-        if (threadIdx.x < kSchedClasses + 2) {
-            const unsigned long long tot = s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
-            if (threadIdx.x < kSchedClasses) s_base[threadIdx.x] = tot;
-            else if (blockIdx.x == 0) {
-                if (threadIdx.x == kSchedClasses) sc->ord_na = (int64_t)tot;
-                else sc->ord_n = (int64_t)tot;
-            }
-        }
-        __syncthreads();
+    static_assert(NC <= 32 && kSchedBlocks == 4 * 256, "8 threads per class sum 256 partial counts; class_peers() tells 32 classes apart");
+    __shared__ unsigned int s_m[NC][256];    // thread t's four tiles (4 t .. 4 t + 3), summed, by class
+    __shared__ unsigned int s_edge[NC];      // ... of the thread that holds this block's own tile: the tiles in front of it only
+    __shared__ unsigned int s_part[NC][8][2];
+    __shared__ unsigned int s_tot[NC], s_pre[NC];
+    __shared__ unsigned int s_wh[4][NC];     // class counts of each wave's quarter of the tile
+    __shared__ unsigned int s_wbase[4][NC];  // schedule position of the wave's next row of each class (the order holds < 2^31 rows)
+    const int nblk = gridDim.x, t = threadIdx.x, lane = t & 63, wave = t >> 6, blk = blockIdx.x;
+    if (t < 4 * NC) (&s_wh[0][0])[t] = 0;
+    __syncthreads();
+    const int64_t lo = (int64_t)blk * tile, hi = lo + tile < n ? lo + tile : n;
+    const int64_t quarter = tile / 4;  // (tile is a multiple of 256)
+    const int64_t wlo = lo + wave * quarter, whi = wlo + quarter < hi ? wlo + quarter : hi;
+    for (int64_t i0 = wlo; i0 < whi; i0 += 64) {
+        const int64_t i = i0 + lane;
+        const int c = i < whi ? cls[i] : 255;
+        unsigned int rank, count;
+        class_peers(c, c < NC, lane, rank, count);
+        if (c < NC && rank == 0) atomicAdd(&s_wh[wave][c], count);
     }
-    const int64_t lo = (int64_t)blockIdx.x * tile, hi = lo + tile < n ? lo + tile : n;
-    for (int64_t i0 = lo; i0 < hi; i0 += 256) {
-        const int64_t i = i0 + threadIdx.x;
-        const int c = i < hi ? cls[i] : 255;
-        unsigned int rank = 0;
+    // s_tot[c] = rows of class c, s_pre[c] = those of them in the tiles in front of this block's
+    const int t_own = blk >> 2;
 #pragma unroll
-        for (int k = 0; k < kSchedClasses; k++) {
-            const unsigned long long m = __ballot(c == k);
-            if (c == k) rank = __popcll(m & ((1ull << lane) - 1ull));
-            if (lane == 0) s_wcnt[wave][k] = __popcll(m);
+    for (int c = 0; c < NC; c++) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(hist + c * kSchedBlocks + 4 * t);
+        const unsigned int e0 = 4 * t < nblk ? v.x : 0u, e1 = 4 * t + 1 < nblk ? v.y : 0u, e2 = 4 * t + 2 < nblk ? v.z : 0u, e3 = 4 * t + 3 < nblk ? v.w : 0u;
+        s_m[c][t] = e0 + e1 + e2 + e3;
+        if (t == t_own) s_edge[c] = (4 * t < blk ? e0 : 0u) + (4 * t + 1 < blk ? e1 : 0u) + (4 * t + 2 < blk ? e2 : 0u);
+    }
+    __syncthreads();
+    if (t < NC * 8) {
+        const int c = t >> 3, j = t & 7;
+        unsigned int tot = 0, pre = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int q = (k + j) & 7;  // (the eight threads of a class start on different banks)
+            const uint4 v = reinterpret_cast<const uint4 *>(&s_m[c][32 * j])[q];
+            const int first = 32 * j + 4 * q;
+            tot += v.x + v.y + v.z + v.w;
+            pre += (first < t_own ? v.x : 0u) + (first + 1 < t_own ? v.y : 0u) + (first + 2 < t_own ? v.z : 0u) + (first + 3 < t_own ? v.w : 0u);
         }
-        __syncthreads();
-        if (c < kSchedClasses) {
-            unsigned int before = 0;
-            for (int w2 = 0; w2 < wave; w2++) before += s_wcnt[w2][c];
-            order[s_base[c] + before + rank] = (int32_t)i;
+        s_part[c][j][0] = tot;
+        s_part[c][j][1] = pre;
+    }
+    __syncthreads();
+    if (t < NC) {
+        unsigned int tot = 0, pre = s_edge[t];
+        for (int j = 0; j < 8; j++) {
+            tot += s_part[t][j][0];
+            pre += s_part[t][j][1];
         }
-        __syncthreads();
-        if (threadIdx.x < kSchedClasses) s_base[threadIdx.x] += s_wcnt[0][threadIdx.x] + s_wcnt[1][threadIdx.x] + s_wcnt[2][threadIdx.x] + s_wcnt[3][threadIdx.x];
-        __syncthreads();
+        s_tot[t] = tot;
+        s_pre[t] = pre;
+    }
+    __syncthreads();
+    if (t < 4 * NC) {  // wave w's class-c rows start behind every row of the classes below, the class's rows of the tiles in front and of the waves in front
+        const int w = t / NC, c = t - w * NC;
+        unsigned int base = s_pre[c];
+        for (int k = 0; k < c; k++) base += s_tot[k];
+        for (int w2 = 0; w2 < w; w2++) base += s_wh[w2][c];
+        s_wbase[w][c] = base;
+    }
+    if (blk == 0 && t == 0) {
+        unsigned long long na = 0, all = 0;
+        for (int c = 0; c < NC; c++) {
+            na += c < classesA ? s_tot[c] : 0u;
+            all += s_tot[c];
+        }
+        sc->ord_na = (int64_t)na;
+        sc->ord_n = (int64_t)all;
+    }
+    __syncthreads();
+    // (LDS operations of one wave complete in order: the leaders' adds of one pass are behind its reads and in front of the next pass's)
+    for (int64_t i0 = wlo; i0 < whi; i0 += 64) {
+        const int64_t i = i0 + lane;
+        const int c = i < whi ? cls[i] : 255;
+        unsigned int rank, count;
+        class_peers(c, c < NC, lane, rank, count);
+        if (c < NC) order[s_wbase[wave][c] + rank] = (int32_t)i;
+        if (c < NC && rank == 0) atomicAdd(&s_wbase[wave][c], count);
     }
 }
 
@@ -427,7 +461,11 @@ __global__ __launch_bounds__(256) void disp_init_kernel(FitDims d, FitWork w, Op
         }
     }
     const double out_thr = MAP ? o.outlierSD * sqrt(sc->varLogDispEsts) : 0.0;
-    unsigned int mine[kSchedClasses] = {0, 0, 0, 0, 0, 0};
+    __shared__ unsigned int s_cnt[kSchedClassesFine];  // the tile's class counts (first half of order_*)
+    if (!MAP && tile > 0) {
+        if (threadIdx.x < kSchedClassesFine) s_cnt[threadIdx.x] = 0;
+        __syncthreads();
+    }
     const int64_t lo = tile > 0 ? (int64_t)blockIdx.x * tile : (int64_t)blockIdx.x * 256;
     const int64_t hi = tile > 0 ? (lo + tile < d.n ? lo + tile : d.n) : d.n;
     const int64_t step = tile > 0 ? 256 : (int64_t)gridDim.x * 256;
@@ -470,10 +508,13 @@ __global__ __launch_bounds__(256) void disp_init_kernel(FitDims d, FitWork w, Op
             const double a0 = fmin(fmax(o.minDisp, fmin(cur.b, moments)), o.maxDisp);
             const double g0 = cur.g0, g1 = cur.g1;
             reinterpret_cast<double2 *>(w.start)[2 * i] = make_double2(a0, log(a0));  // what the search reads with the row
-            const int c = sched_class(a0, d.p == 2 ? fmin(g0, g1) : g0, o.minDisp);
+            const int c = sched_class(a0, d.p == 2 ? fmin(g0, g1) : g0, o.minDisp, o.schedule);
             w.cls[i] = (uint8_t)c;
-#pragma unroll
-            for (int k = 0; k < kSchedClasses; k++) mine[k] += (c == k);
+            if (tile > 0) {  // one LDS add per class present in the wave (the lanes that skipped an all-zero row are not in the ballots)
+                unsigned int rank, count;
+                class_peers(c, true, threadIdx.x & 63, rank, count);
+                if (rank == 0) atomicAdd(&s_cnt[c], count);
+            }
         } else {
             const double dg = cur.a, df = sc->trend_local ? cur.b : c0 + c1 / bm;
             const double ldf = log(df);
@@ -485,7 +526,10 @@ __global__ __launch_bounds__(256) void disp_init_kernel(FitDims d, FitWork w, Op
             if (is_out) w.disp[i] = dg;  // an outlier keeps its gene-wise estimate (A4): written HERE, so that the search carries one bit for it, not the value
         }
     }
-    if (!MAP && tile > 0) order_hist_store(mine, hist);
+    if (!MAP && tile > 0) {
+        __syncthreads();
+        if (threadIdx.x < kSchedClassesFine) hist[threadIdx.x * kSchedBlocks + blockIdx.x] = s_cnt[threadIdx.x];
+    }
 }
 
 constexpr int kChunk = 64;   // rows a wave takes from the global queue per atomic (at most: DispArgs::chunk)
@@ -1476,12 +1520,18 @@ __global__ __launch_bounds__(128) void disp_grid_kernel(DispArgs A) {
 
 // w.cls[] -> w.order[], sc->ord_na (entries of classes < classesA), sc->ord_n; w.hist is idle between the selects
 // have_hist: the class counts per tile are in w.hist already (left there by the kernel that wrote w.cls)
-void launch_order_build(FitDims d, FitWork w, int classesA, bool have_hist, hipStream_t st) {
+// fine: the classes are the gene-wise search's kSchedClassesFine (classesA: a class index of that layout), else the IRLS's kSchedClasses
+void launch_order_build(FitDims d, FitWork w, int classesA, bool have_hist, hipStream_t st, bool fine) {
     int64_t nblk, tile;
     order_tiles(d.n, nblk, tile);
     unsigned int *hist = reinterpret_cast<unsigned int *>(w.hist);
-    if (!have_hist) order_hist_kernel<<<(unsigned)nblk, 256, 0, st>>>(w.cls, d.n, tile, hist);
-    order_scatter_kernel<<<(unsigned)nblk, 256, 0, st>>>(w.cls, d.n, tile, hist, w.order, w.sc, classesA);
+    if (fine) {
+        if (!have_hist) order_hist_kernel<kSchedClassesFine><<<(unsigned)nblk, 256, 0, st>>>(w.cls, d.n, tile, hist);
+        order_scatter_kernel<kSchedClassesFine><<<(unsigned)nblk, 256, 0, st>>>(w.cls, d.n, tile, hist, w.order, w.sc, classesA);
+    } else {
+        if (!have_hist) order_hist_kernel<kSchedClasses><<<(unsigned)nblk, 256, 0, st>>>(w.cls, d.n, tile, hist);
+        order_scatter_kernel<kSchedClasses><<<(unsigned)nblk, 256, 0, st>>>(w.cls, d.n, tile, hist, w.order, w.sc, classesA);
+    }
 }
 
 static void launch_disp(bool map, const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o,
@@ -1519,6 +1569,10 @@ static void launch_disp(bool map, const int32_t *counts, const double *nf, FitDi
     // all drain (250 k x 8: 0.50 -> 0.63).  So: three waves for the MAP search of >= 750 k rows; for the gene-wise search only where the
     // launch is long against that chain (105 ticks of ~2 + 1.1 S us): from 3 M rows (3 M x 8 1.85 -> 1.82 ms, 4 M 2.39 -> 2.25, 6 M 3.45 ->
     // 3.20), at S <= 4 from 1.5 M (2 M x 4 1.16 -> 1.13, 4 M x 4 1.97 -> 1.91); two otherwise.
+    // Round 7, re-measured under the 1/8-decade order (profiles/r07_ab_schedule_and_waves.txt; gene-wise stage by HIP events, two -> three
+    // waves): 1.5 M x 8 1.02 -> 1.05 ms, 2 M x 8 1.26 -> 1.30, 3 M x 8 1.78 -> 1.69; 1 M x 4 0.663 -> 0.675, 2 M x 4 1.087 -> 1.071: three
+    // waves still empty the queue 0.13 ms earlier at 2 M x 8 and still end no earlier (last wave out at 1.37 ms against 1.33) — the
+    // boundary stays where it was.
     const bool lds3 = (int64_t)(160 * 1024 / (lds + 2048)) * waves_per_block >= 12;
     const bool three = lds3 && (map ? d.n >= 750000 : (d.n >= 3000000 || (d.S <= 4 && d.n >= 1500000)));
     const int min_waves = (o.min_waves >= 2 && o.min_waves <= 4) ? o.min_waves : (three ? 3 : 2);
@@ -1541,10 +1595,13 @@ static void launch_disp(bool map, const int32_t *counts, const double *nf, FitDi
     // 0.666 -> 0.644 at 250 k x 16 (2.5); NOT at 2 M x 8 (15 rows per lane: the queue balances better than any deal: 1.356 -> 1.44),
     // 1 M x 16 (10: + 1.5 %), 200 k x 4 (1.5: + 1.5 %), 150 k x 8 (1.1: + 2 %).  Groups of 8 (the automatic size for so many entries)
     // gave nothing: 2 or 4.
+    // (Round 7: under the default order "all but the last" ends in front of the minDisp starts, which now sit before the score >= 3.16 rows:
+    // those two groups go through the queue.  Whole steps against the parent, which dealt the 3.16 - 10 rows too: 250 k x 8 1.254 -> 1.256 ms,
+    // 1 M x 8 2.314 -> 2.247; profiles/r07_ab_bench_shapes.jsonl.)
     const double rows_per_lane = (double)d.n / (double)(blocks * threads);
-    const bool deal_most = !map && o.schedule == 1 && o.classes_a == 0 && rows_per_lane >= 1.8 && rows_per_lane <= 8.0;
+    const bool deal_most = !map && o.schedule != 2 && o.classes_a == 0 && rows_per_lane >= 1.8 && rows_per_lane <= 8.0;
     const int classes_a = o.schedule == 2 ? 0 : (o.classes_a > 0 ? o.classes_a : (deal_most ? 5 : kSchedClassesA));
-    if (sched) launch_order_build(d, w, classes_a, true, st);
+    if (sched) launch_order_build(d, w, sched_classes_a(classes_a, o.schedule), true, st, true);
     DispArgs A{counts, nf, d, w, o, nullptr, o.spread, sched ? w.order : nullptr, (deal_most && o.deal == 0) ? 4 : o.deal, 1, kChunk,
                w.gridlist, reinterpret_cast<unsigned int *>(w.queue + (map ? 24 : 16)), o.prio};
 #ifdef CHICDIFF_DIAG

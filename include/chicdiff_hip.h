@@ -81,8 +81,10 @@ int32_t chicdiff_hip_last_refits(const chicdiff_hip_ctx *ctx);
 /* Tuning / test options; results never depend on them, the defaults are what bench.py measures.
  *   "line_search_spread"        1 (default) | 0: evaluate straggler rows (line searches and IRLS) with their samples spread across lanes
  *   "line_search_min_waves"     2 (default) .. 4: waves per SIMD the line-search kernel variant is built for
- *   "line_search_schedule"      1 (default) | 0: the gene-wise line search visits the rows likely to need DESeq2's full 100
- *                               iterations first (score alpha_init * smaller group mean); 0 = natural row order
+ *   "line_search_schedule"      1 (default) | 0 | 3 | 4: the gene-wise line search visits the rows likely to need DESeq2's full 100
+ *                               iterations first (score alpha_init * smaller group mean, in classes of 1/8 decade; the rows that
+ *                               start at minDisp in front of the score >= 3.16 rows); 0 = natural row order; 3 = the six
+ *                               half-decade classes of earlier releases (minDisp starts last); 4 = as 1, minDisp starts last
  *   "line_search_deal"          0 (default: chosen from the rows per wave), 1 .. 64: schedule entries per group of the static deal
  *   "theta_grid_concurrency"    5 (default), 1 .. 16: fits of the theta grid in flight at once (single rank only)
  *   "host_copy_threads"         12 (default), 1 .. 64: host threads staging caller buffers in chicdiff_hip_nbglm_fit
@@ -376,6 +378,11 @@ int chicdiff_hip_selftest_chinput(const char *path, int32_t nthreads, int64_t ca
                                   int64_t *nrows, char *err, int32_t errcap);
 int chicdiff_hip_selftest_r_random(int32_t kind, uint32_t seed, double a, double b, int64_t n, double *out);
 int chicdiff_hip_selftest_prior_mc(int32_t df, const double *hist40, double *dens_out, double *prior_var_out);
+/* _sched_class (host only): the class the gene-wise line search's schedule ("line_search_schedule" = mode, 1 .. 4) puts a row in,
+ * from its start value alpha_init and its smaller group mean — cls_out[n], lower = visited earlier; bounds[7] (may be NULL): the
+ * first class that goes through the queue when 0 .. 6 of the half-decade classes are dealt out statically. */
+int chicdiff_hip_selftest_sched_class(int32_t mode, double min_disp, const double *alpha_init, const double *group_mean, int64_t n,
+                                      int32_t *cls_out, int32_t *bounds);
 
 /* Timing of the last *_dev call's kernels, measured with HIP events on the context's stream:
  * fills up to `cap` (name, milliseconds, launches) records; returns the number available. */
