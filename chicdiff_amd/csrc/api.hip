@@ -46,6 +46,7 @@ struct chicdiff_hip_ctx {
     // tuning / test options (chicdiff_hip_set_option); the defaults are what the benchmarks run
     int opt_chunk = 0;  // line search: rows per dequeue (0 = automatic)
     int opt_prio = 0;   // line search: s_setprio by search age (0 = off)
+    int opt_fillers = -1, opt_filler_stop = -1;  // gene-wise line search: filler waves (-1 = launch_disp's rule), the share at which they stop claiming (-1 = default)
     int opt_classes_a = 0;  // gene-wise line search: classes of the schedule dealt out statically (0 = default)
     int opt_spread = 1, opt_min_waves = 0, opt_select_rounds = 0, opt_trend_multilaunch = 0, opt_schedule = 1, opt_deal = 0;
     int opt_trend_gather = 1;  // sharded fits: gather the rows of the trend on every rank (two collectives) instead of one all-reduce per IRLS pass
@@ -187,6 +188,8 @@ int chicdiff_hip_set_option(chicdiff_hip_ctx *c, const char *name, int64_t value
     if (k == "line_search_spread" && value >= 0 && value <= 3) c->opt_spread = (int)value;  // 2: samples across lanes without the lean tick of the launch's end (bit-identity tests)
     else if (k == "line_search_min_waves" && (value == 0 || (value >= 2 && value <= 4))) c->opt_min_waves = (int)value;
     else if (k == "line_search_prio" && value >= 0 && value <= 100) c->opt_prio = (int)value;
+    else if (k == "line_search_fillers" && value >= -1 && value <= 1) c->opt_fillers = (int)value;
+    else if (k == "line_search_filler_stop" && value >= -1 && value <= 100) c->opt_filler_stop = (int)value;
     else if (k == "line_search_chunk" && (value == 0 || (value >= 8 && value <= 64))) c->opt_chunk = (int)value;
     else if (k == "line_search_classes_a" && value >= 0 && value <= 6) c->opt_classes_a = (int)value;
     else if (k == "line_search_schedule" && value >= 0 && value <= 4 && value != 2) c->opt_schedule = (int)value;  // (2 is what the theta grid's concurrent fits get)
@@ -489,7 +492,7 @@ static int ensure_workspace(chicdiff_hip_ctx *c, int64_t n, int S) {
     const size_t selcnt = align256(sizeof(double) * (size_t)kSelMaxWorld * kMaxS * 2);
     const size_t rowpack = align256((size_t)row_stride(S) * (size_t)n);
     const size_t start4 = align256(sizeof(double) * 4 * (size_t)n);
-    const size_t total = nd * n_double_arrays + ni * n_int_arrays + partials + 2 * hist + selcnt + align256(sizeof(FitScalars)) + kQueueBytes + 1024 + nfbytes + rowpack + start4;
+    const size_t total = nd * n_double_arrays + ni * n_int_arrays + partials + 2 * hist + selcnt + align256(sizeof(FitScalars)) + kQueueBytes + 1024 + kPlaceWords * 8 + nfbytes + rowpack + start4;
     hipError_t e = hipMalloc(&c->ws, total);
     if (e != hipSuccess) return fail(c, CHICDIFF_E_NOMEM, "workspace of %zu bytes: %s", total, hipGetErrorString(e));
     c->ws_bytes = total;
@@ -512,6 +515,7 @@ static int ensure_workspace(chicdiff_hip_ctx *c, int64_t n, int S) {
     w.logfact = c->d_logfact;
     w.queue = (unsigned long long *)p; p += kQueueBytes;
     w.barrier = (unsigned int *)p; p += 1024;
+    w.place = (unsigned long long *)p; p += kPlaceWords * 8;
     c->d_nf_tmp = (double *)p; p += nfbytes;
     w.rowpack = p; p += rowpack;
     w.start = (double *)p;
@@ -748,6 +752,8 @@ static Opts make_opts(const chicdiff_hip_ctx *c, const chicdiff_nbglm_opts *in, 
     r.spread = c->opt_spread;
     r.min_waves = c->opt_min_waves;
     r.prio = c->opt_prio;
+    r.fillers = c->opt_fillers;
+    r.filler_stop = c->opt_filler_stop;
     r.schedule = c->opt_schedule;
     r.deal = c->opt_deal;
     r.chunk = c->opt_chunk;
@@ -1654,6 +1660,8 @@ int chicdiff_hip_theta_grid_dev(chicdiff_hip_ctx *c, const int32_t *d_counts, co
         l->opt_spread = c->opt_spread;
         l->opt_min_waves = c->opt_min_waves;
         l->opt_prio = c->opt_prio;
+        l->opt_fillers = c->opt_fillers;  // (schedule 2 has no boundary to give: launch_disp keeps fillers off for these fits whatever this says)
+        l->opt_filler_stop = c->opt_filler_stop;
         l->opt_schedule = c->opt_schedule ? 2 : 0;  // concurrent fits: class order through the queue, nothing dealt out statically
         l->opt_deal = c->opt_deal;
         l->opt_chunk = c->opt_chunk;
@@ -1739,6 +1747,15 @@ extern "C" int chicdiff_hip_selftest_sched_class(int32_t mode, double min_disp, 
     for (int64_t i = 0; i < n; i++) cls_out[i] = cd::sched_class(alpha_init[i], group_mean[i], min_disp, mode);
     if (bounds) for (int a = 0; a <= 6; a++) bounds[a] = cd::sched_classes_a(a, mode);
     return CHICDIFF_OK;
+}
+// the claim rule of the gene-wise line search's two-ended queue (common.h: queue_claim, filler_claims, filler_stop_f), evaluated on the host
+extern "C" int chicdiff_hip_selftest_queue_claim(uint64_t old, int32_t back, uint32_t chunks, uint32_t first_back, int32_t stop_percent, int32_t claimed,
+                                                 uint32_t *chunk_out, int32_t *again_out) {
+    uint32_t chunk = 0;
+    const bool valid = cd::queue_claim(old, back != 0, chunks, chunk);
+    if (chunk_out) *chunk_out = chunk;
+    if (again_out) *again_out = cd::filler_claims(claimed != 0, old, chunks, first_back, cd::filler_stop_f(stop_percent, chunks, first_back));
+    return valid ? 1 : 0;
 }
 extern "C" int chicdiff_hip_selftest_prior_mc(int32_t df, const double *hist40, double *dens_out, double *prior_var_out) {
     if (df < 1 || df > 3) return CHICDIFF_E_INVALID;

@@ -36,13 +36,46 @@ struct FitWork {
     double *hist;                 // kMaxS*2 x kSelBins doubles (f64 so it can ride the all-reduce)
     double *hist_local;           // same size: this rank's round-2 histogram, kept aside for the sharded shortcut
     double *selcnt;               // kSelMaxWorld x kMaxS*2 doubles: per-rank candidate counts
-    unsigned long long *queue;    // work-queue heads (kQueueBytes): [0] gene-wise, [1] MAP, [8..15] spare, [16] / [24] lengths of the gene-wise / MAP grid lists, [32 + 8 h] the IRLS's eight heads, 64 bytes apart, [192 + 8 h] the MAP line search's
+    unsigned long long *queue;    // work-queue heads (kQueueBytes): [0] gene-wise, [1] MAP, [8..15] spare, [16] / [24] lengths of the gene-wise / MAP grid lists, [32 + 8 h] the IRLS's eight heads, 64 bytes apart, [192 + 8 h] the MAP line search's; [104], [112]: role counters of the gene-wise launch's filler waves (kRoleFront, kRoleFill)
+    unsigned long long *place;    // kPlaceWords words: where the waves of a gene-wise launch with fillers landed, one word per compute unit; zeroed by disp_init when such a launch follows
     unsigned int *barrier;        // 9 x 64 B: grid-barrier counters of the persistent trend kernel
     FitScalars *sc;
     const double *logfact;        // log(k!) for k < kLogFactN
 };
 constexpr int kLogFactN = 1024;
 constexpr int kQueueBytes = 2048;  // FitWork::queue
+// ---- filler waves of the gene-wise line search (disp_kernels.hip, "front waves and fillers") ----
+constexpr int kPlaceWords = 2048;  // FitWork::place[cu]: one word per compute unit (XCC, SE, SH, CU ids of HW_ID), arrivals per SIMD in its four 16-bit fields
+constexpr int kRoleFront = 104, kRoleFill = 112;     // queue[104] / queue[112] (cache lines of their own): waves that took a front index / asked to be a filler so far
+// The two-ended queue.  One 64-bit word counts the claims from the head (low half, f) and from the end (high half, b); a claim is one
+// atomic add of kClaimFront or kClaimBack, and `old` is what it returned.  The claim is valid exactly while f + b < chunks — every atomic
+// raises f + b by one, so the valid claims are the first `chunks` atomics, whoever makes them — and then names chunk f (from the head)
+// or chunks - 1 - b (from the end): disjoint, and together every chunk once.  A valid claim is always worked by the wave that made it.
+constexpr unsigned long long kClaimFront = 1ull, kClaimBack = 1ull << 32;
+__host__ __device__ inline bool queue_claim(unsigned long long old, bool back, uint32_t chunks, uint32_t &chunk) {
+    const uint32_t f = (uint32_t)old, b = (uint32_t)(old >> 32);
+    chunk = back ? chunks - 1u - b : f;
+    return f < chunks && b < chunks - f;  // f + b < chunks, in 32-bit compares (the scalar unit has no ordered 64-bit one)
+}
+// Whether a filler may claim (again).  `old` is the word its last claim returned, `claimed` whether it has made one (before the first
+// claim it has seen nothing, and only the launch-wide facts count).  It stops for good once its last chunk was the boundary chunk or
+// in front of it — first_back is the first chunk that lies wholly inside the rows that cannot be long; first_back >= chunks: there is
+// none — or once the front counter it saw has reached stop_f (the set share of the front's own chunks; 0 = fillers never claim,
+// 0xffffffff = no such stop).  So fillers overshoot the boundary by at most one chunk per wave, and nothing ever waits.
+__host__ __device__ inline bool filler_claims(bool claimed, unsigned long long old, uint32_t chunks, uint32_t first_back, uint32_t stop_f) {
+    if (first_back >= chunks || stop_f == 0u) return false;
+    if (!claimed) return true;
+    uint32_t chunk;
+    if (!queue_claim(old, true, chunks, chunk)) return false;  // the queue is empty
+    return chunk > first_back && (uint32_t)old < stop_f;
+}
+// stop_f from the option's percentage: share of the front's own chunks [0, first_back)
+__host__ __device__ inline uint32_t filler_stop_f(int percent, uint32_t chunks, uint32_t first_back) {
+    if (percent >= 100) return 0xffffffffu;
+    if (percent <= 0) return 0u;
+    const uint32_t own = first_back < chunks ? first_back : chunks;
+    return (uint32_t)(((unsigned long long)own * (unsigned)percent + 99ull) / 100ull);
+}
 // bytes between rows of FitWork::rowpack: 12 S rounded up so that a row never straddles more 128-byte lines than it must
 constexpr int kRowHdr = 32;  // four doubles in front of every row: group mean A (its sign bit set: the row is all zero), group mean B, two
                              // spare (the per-stage start values moved to FitWork::start)
@@ -66,6 +99,8 @@ struct Opts {
     int32_t classes_a = 0;  // gene-wise line search: score classes dealt out statically (0 = the default, 2; 1 .. 6)
     int32_t xim_here = 0;   // (set by the fit driver, not an option) single rank: disp_init forms xim from the column sums itself, no xim_kernel launch
     int32_t prio = 0;       // line search: issue priority by search age, one level per `prio` iterations (0 = off); option "line_search_prio"
+    int32_t fillers = -1;   // gene-wise line search: a third wave per SIMD at priority 0 that takes only rows which cannot be long (0 off, 1 on, -1 = by launch_disp's rule); option "line_search_fillers"
+    int32_t filler_stop = -1;  // ... fillers stop claiming once the front waves have claimed this share (percent) of their own chunks (100 = never, -1 = kFillerStopDefault); option "line_search_filler_stop"
     int32_t trend_blocks = 0;  // persistent trend kernel: at most this many workgroups (0 = one per CU); option "trend_persistent_blocks"
 };
 

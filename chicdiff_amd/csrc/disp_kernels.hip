@@ -357,7 +357,7 @@ __global__ __launch_bounds__(256) void order_hist_kernel(const uint8_t *__restri
 template <int NC>
 __global__ __launch_bounds__(256) void order_scatter_kernel(const uint8_t *__restrict__ cls, int64_t n, int64_t tile,
                                                             const unsigned int *__restrict__ hist, int32_t *__restrict__ order,
-                                                            FitScalars *sc, int classesA) {
+                                                            FitScalars *sc, int classesA, int classesB) {
     static_assert(NC <= 32 && kSchedBlocks == 4 * 256, "8 threads per class sum 256 partial counts; class_peers() tells 32 classes apart");
     __shared__ unsigned int s_m[NC][256];    // thread t's four tiles (4 t .. 4 t + 3), summed, by class
     __shared__ unsigned int s_edge[NC];      // ... of the thread that holds this block's own tile: the tiles in front of it only
@@ -421,12 +421,14 @@ __global__ __launch_bounds__(256) void order_scatter_kernel(const uint8_t *__res
         s_wbase[w][c] = base;
     }
     if (blk == 0 && t == 0) {
-        unsigned long long na = 0, all = 0;
+        unsigned long long na = 0, nb = 0, all = 0;
         for (int c = 0; c < NC; c++) {
             na += c < classesA ? s_tot[c] : 0u;
+            nb += c < classesB ? s_tot[c] : 0u;
             all += s_tot[c];
         }
         sc->ord_na = (int64_t)na;
+        sc->ord_nb = (int32_t)nb;  // (the order holds < 2^31 rows)
         sc->ord_n = (int64_t)all;
     }
     __syncthreads();
@@ -444,8 +446,9 @@ __global__ __launch_bounds__(256) void order_scatter_kernel(const uint8_t *__res
 // tile > 0 (gene-wise launch with the schedule on): block b owns rows [b tile, (b + 1) tile) and leaves its class counts in
 // hist (the first half of order_*); tile == 0: rows grid-strided
 template <bool MAP>
-__global__ __launch_bounds__(256) void disp_init_kernel(FitDims d, FitWork w, Opts o, int64_t tile, unsigned int *hist, int xim_here) {
+__global__ __launch_bounds__(256) void disp_init_kernel(FitDims d, FitWork w, Opts o, int64_t tile, unsigned int *hist, int xim_here, int clear_place) {
     const FitScalars *sc = w.sc;
+    if (clear_place && blockIdx.x < kPlaceWords / 256) w.place[blockIdx.x * 256 + threadIdx.x] = 0ull;  // (gene-wise launch with filler waves: its placement table)
     const double c0 = sc->coefs[0], c1 = sc->coefs[1];
     // xim = mean_j 1 / (colsum_j / nnz) (momentsDispEstimate).  xim_here (single rank, round 6): formed here from the column sums, by every
     // thread with xim_kernel's own operations (same bits), instead of by a one-thread launch of its own in front of this one (~4 us)
@@ -618,6 +621,8 @@ struct DispArgs {
     int32_t *gridlist;           // rows whose line search did not converge: fitDispGrid's two stages run in disp_grid_kernel (round 6)
     unsigned int *gridcount;     // ... and their number
     int prio;                    // > 0: a wave raises its issue priority (s_setprio) by one level per `prio` iterations of its oldest search
+    unsigned int nfront;         // gene-wise launch with filler waves: the number of front waves (the rest of the grid are fillers); 0 = no fillers
+    int filler_stop;             // ... fillers stop claiming at this share (percent) of the front's own chunks
 };
 // make ISA_MARK=1 (tools/isa_account.py): comment lines in the generated assembly that delimit the parts of a tick; a volatile asm
 // statement also keeps the compiler from moving code across it, so the marked build is for counting, not for running
@@ -628,7 +633,7 @@ struct DispArgs {
 #endif
 #ifdef CHICDIFF_DIAG
 #define DIAG(...) __VA_ARGS__
-constexpr int kStampSlots = 34;  // start, queue-empty, exit (s_memrealtime), live rows at queue-empty, ticks after queue-empty: row-per-lane / spread / burst, all ticks, s_memtime cycles after queue-empty in row / spread / burst ticks, spare
+constexpr int kStampSlots = 36;  // start, queue-empty, exit (s_memrealtime), live rows at queue-empty, ticks after queue-empty: row-per-lane / spread / burst, all ticks, s_memtime cycles after queue-empty in row / spread / burst ticks, ..., [34] role (0 front / no roles, 1 filler), [35] where the wave ran (XCC_ID << 16 | HW_ID's low half)
 #else
 #define DIAG(...)
 #endif
@@ -1018,10 +1023,58 @@ __global__ __launch_bounds__(256, MINW) void disp_fit_kernel(DispArgs A) {
     // the scalar unit has no ordered 64-bit compare, with 64-bit positions the whole bookkeeping moves to the vector unit)
     const uint32_t nA = order ? (uint32_t)sc->ord_na : 0u;
     const uint32_t nTot = order ? (uint32_t)sc->ord_n : (uint32_t)n;
-    const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
-    const uint32_t mywave = blockIdx.x * (blockDim.x >> 6) + (uint32_t)wave;
+    uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
+    uint32_t mywave = blockIdx.x * (blockDim.x >> 6) + (uint32_t)wave;
+    // ---- front waves and fillers (gene-wise launch, A.nfront > 0) ------------------------------------------------------------------------
+    // Two waves per SIMD leave issue slots unused (VALU busy 0.70) and a third wave fills them, but it slows every wave's tick, and the
+    // launch ends with ~105 dependent ticks of a flat-likelihood row at the pace of the wave that holds it.  So: A.nfront "front" waves are
+    // the two-wave launch as it was — the static deal over THEIR number, the queue from its head — at user priority 3, which the
+    // instruction arbiter honours (measured: 8.6 us per bulk tick against 7.97 in the two-wave launch); the remaining third of the grid are "fillers" at
+    // priority 0, which take only chunks from the END of the schedule, backwards, down to the first chunk that lies wholly in
+    // order[ord_nb, ord_n): rows of score >= 3.16, none of which is long (queue_claim / filler_claims: common.h).
+    // Roles by placement, not by chance: a wave adds one to its SIMD's field of its compute unit's word (ids from HW_ID / XCC_ID, read
+    // once); the first two arrivals on a SIMD ask to be front waves, later ones to be fillers.  The static deal needs exactly A.nfront
+    // front waves with dense indices, whatever the placement turned out to be, so the two role counters decide: a wave that asks to be
+    // front takes the next front index and is a filler if that is >= nfront; a wave that asks to be a filler is one while fewer than
+    // nwaves - nfront have asked, else it takes the next front index — which is then < nfront: with P waves asking for front, P < nfront
+    // exactly when more than nwaves - nfront ask to fill, and the nfront - P of those that are turned away complete the indices.
+    // Either way exactly nfront front waves, every index once.  A SIMD with three front waves or two fillers is slower, never wrong.
+    bool filler = false;
+    DIAG(unsigned int where = 0;)
+    if (!MAP && A.nfront > 0u) {
+        const unsigned int hw = __builtin_amdgcn_s_getreg(4 | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (31 << 11));  // HW_ID: SIMD_ID [5:4], CU_ID [11:8], SH_ID [12], SE_ID [15:13]; XCC_ID [3:0]
+        const unsigned int simd = (hw >> 4) & 3u, cu = ((xcc & 7u) << 8) | ((hw >> 8) & 0xffu);  // cu < kPlaceWords
+        DIAG(where = (xcc << 16) | (hw & 0xffffu);)
+        unsigned int role = 0;  // bit 31: filler; front waves: their index
+        if (lane == 0) {
+            const unsigned long long arrivals = (atomicAdd(A.w.place + cu, 1ull << (16 * simd)) >> (16 * simd)) & 0xffffull;
+            const unsigned int nfill = nwaves - A.nfront;
+            if (arrivals >= 2ull) {
+                if ((unsigned int)atomicAdd(A.w.queue + kRoleFill, 1ull) < nfill) role = 0x80000000u;
+                else role = (unsigned int)atomicAdd(A.w.queue + kRoleFront, 1ull);
+            } else {
+                role = (unsigned int)atomicAdd(A.w.queue + kRoleFront, 1ull);
+                if (role >= A.nfront) role = 0x80000000u;
+            }
+        }
+        role = __builtin_amdgcn_readfirstlane(role);
+        filler = (role & 0x80000000u) != 0u;
+        nwaves = A.nfront;  // the deal is the front waves' alone
+        mywave = role & 0x7fffffffu;
+        if (!filler) __builtin_amdgcn_s_setprio(3);
+    }
+    // the queue in chunks (gene-wise launch: both ends; MAP: the heads count rows as before)
+    const uint32_t nchunks = MAP ? 0u : (nTot - nA + (uint32_t)A.chunk - 1u) / (uint32_t)A.chunk;
+    uint32_t first_back = nchunks, stop_f = 0u;
+    if (!MAP && A.nfront > 0u) {
+        const uint32_t nb = (uint32_t)sc->ord_nb < nA ? nA : (uint32_t)sc->ord_nb;
+        first_back = (nb - nA + (uint32_t)A.chunk - 1u) / (uint32_t)A.chunk;
+        stop_f = filler_stop_f(A.filler_stop, nchunks, first_back);
+    }
+    bool fclaimed = false;
+    unsigned long long fold = 0ull;  // what this filler's last claim returned
     uint32_t a_k = 0;
-    bool a_done = nA == 0;
+    bool a_done = nA == 0 || filler;
     unsigned int pf_val = 0, pf_acc = 0;
     // entries per group of the deal: eight while every wave gets several groups (neighbouring rows, neighbouring lanes), down to
     // one when rows are few, so that the likely-long rows spread evenly over the waves
@@ -1230,10 +1283,29 @@ __global__ __launch_bounds__(256, MINW) void disp_fit_kernel(DispArgs A) {
                     // one atomic on the global head per kChunk rows (a single hot word saturates near 90 dequeues/us, which one
                     // atomic per tick per wave hit)
                     unsigned int kq = 0;
-                    if (lane == 0) kq = (unsigned int)atomicAdd(heads + 8 * cur_head, 1ull);
-                    kq = __builtin_amdgcn_readfirstlane(kq);
-                    b = nA + (kq * (uint32_t)kHeads + (uint32_t)cur_head) * chunk_rows;
-                    if (b >= nTot) {  // this head is dry: on to the next one that is not known to be (uses up one attempt)
+                    bool dry;
+                    if (MAP) {
+                        if (lane == 0) kq = (unsigned int)atomicAdd(heads + 8 * cur_head, 1ull);
+                        kq = __builtin_amdgcn_readfirstlane(kq);
+                        b = nA + (kq * (uint32_t)kHeads + (uint32_t)cur_head) * chunk_rows;
+                        dry = b >= nTot;
+                    } else {
+                        // the two-ended queue (common.h: queue_claim): front waves — every wave of a launch without fillers — claim from the
+                        // head, fillers from the end while filler_claims() lets them; a valid claim is worked, an invalid one ends the wave's
+                        // refills, and so does a filler's turn not to claim: it finishes its live rows and leaves.  Nothing waits.
+                        if (filler && !filler_claims(fclaimed, fold, nchunks, first_back, stop_f)) {
+                            queue_empty = true;
+                            continue;
+                        }
+                        unsigned long long oldw = 0ull;
+                        if (lane == 0) oldw = atomicAdd(heads, filler ? kClaimBack : kClaimFront);
+                        oldw = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned int)(oldw >> 32)) << 32) | __builtin_amdgcn_readfirstlane((unsigned int)oldw);
+                        fold = oldw;
+                        fclaimed = true;
+                        dry = !queue_claim(oldw, filler, nchunks, kq);
+                        b = nA + kq * chunk_rows;  // (dry: not used)
+                    }
+                    if (dry) {  // this head is dry: on to the next one that is not known to be (uses up one attempt)
                         heads_left &= ~(1u << cur_head);
                         if (MAP)
                             for (int t = 1; t <= 8; t++) {
@@ -1409,6 +1481,8 @@ __global__ __launch_bounds__(256, MINW) void disp_fit_kernel(DispArgs A) {
     }
     if (A.prefetch == 0x7fffffff) A.w.queue[8 + (pf_acc & 7)] = pf_acc;  // (never: keeps the warming loads alive)
     DIAG(if (A.stamps && lane == 0) {
+        A.stamps[gwave * kStampSlots + 34] = filler ? 1ull : 0ull;
+        A.stamps[gwave * kStampSlots + 35] = where;
         A.stamps[gwave * kStampSlots + 2] = __builtin_amdgcn_s_memrealtime();
         A.stamps[gwave * kStampSlots + 4] = tk_row;
         A.stamps[gwave * kStampSlots + 5] = tk_spread;
@@ -1527,24 +1601,36 @@ void launch_order_build(FitDims d, FitWork w, int classesA, bool have_hist, hipS
     unsigned int *hist = reinterpret_cast<unsigned int *>(w.hist);
     if (fine) {
         if (!have_hist) order_hist_kernel<kSchedClassesFine><<<(unsigned)nblk, 256, 0, st>>>(w.cls, d.n, tile, hist);
-        order_scatter_kernel<kSchedClassesFine><<<(unsigned)nblk, 256, 0, st>>>(w.cls, d.n, tile, hist, w.order, w.sc, classesA);
+        order_scatter_kernel<kSchedClassesFine><<<(unsigned)nblk, 256, 0, st>>>(w.cls, d.n, tile, hist, w.order, w.sc, classesA, kSchedMinDispSlot + 1);  // (filler waves: the classes from score 3.16 on, whatever the order's mode)
     } else {
         if (!have_hist) order_hist_kernel<kSchedClasses><<<(unsigned)nblk, 256, 0, st>>>(w.cls, d.n, tile, hist);
-        order_scatter_kernel<kSchedClasses><<<(unsigned)nblk, 256, 0, st>>>(w.cls, d.n, tile, hist, w.order, w.sc, classesA);
+        order_scatter_kernel<kSchedClasses><<<(unsigned)nblk, 256, 0, st>>>(w.cls, d.n, tile, hist, w.order, w.sc, classesA, kSchedClasses);
     }
 }
 
+#ifndef CHICDIFF_FILLER_RULE  // (A/B builds set the three: -DCHICDIFF_FILLER_RULE=0 -DCHICDIFF_FILLER_MIN_ROWS=... -DCHICDIFF_FILLER_STOP=...)
+#define CHICDIFF_FILLER_RULE 1
+#endif
+#ifndef CHICDIFF_FILLER_MIN_ROWS
+#define CHICDIFF_FILLER_MIN_ROWS 1750000
+#endif
+#ifndef CHICDIFF_FILLER_STOP
+#define CHICDIFF_FILLER_STOP 85
+#endif
+constexpr bool kFillerRule = CHICDIFF_FILLER_RULE != 0;  // filler waves where launch_disp's measurements say they pay (0: only on request)
+constexpr int64_t kFillerMinRows = CHICDIFF_FILLER_MIN_ROWS;
+constexpr int kFillerStopDefault = CHICDIFF_FILLER_STOP;
 static void launch_disp(bool map, const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o,
                         hipStream_t st) {
     // (no schedule for a fit every row of which starts at once — n <= 65 536 is half the lanes of two waves per SIMD —: the order then
     // decides nothing, and building it is a launch and a pass: 30 k x 4 gene-wise stage 0.309 -> 0.301 ms, round 6)
     const bool sched = !map && o.schedule && (d.n > 65536 || o.schedule == 2);
-    if (map) disp_init_kernel<true><<<kRedBlocks, 256, 0, st>>>(d, w, o, 0, nullptr, 0);
-    else if (!sched) disp_init_kernel<false><<<kRedBlocks, 256, 0, st>>>(d, w, o, 0, nullptr, o.xim_here);
+    if (map) disp_init_kernel<true><<<kRedBlocks, 256, 0, st>>>(d, w, o, 0, nullptr, 0, 0);
+    else if (!sched) disp_init_kernel<false><<<kRedBlocks, 256, 0, st>>>(d, w, o, 0, nullptr, o.xim_here, 0);
     else {
         int64_t nblk, tile;
         order_tiles(d.n, nblk, tile);
-        disp_init_kernel<false><<<(unsigned)nblk, 256, 0, st>>>(d, w, o, tile, reinterpret_cast<unsigned int *>(w.hist), o.xim_here);
+        disp_init_kernel<false><<<(unsigned)nblk, 256, 0, st>>>(d, w, o, tile, reinterpret_cast<unsigned int *>(w.hist), o.xim_here, 1);  // (nblk >= 257 > kPlaceWords / 256 blocks: sched means n > 65 536)
     }
     const size_t lds_per_wave = disp_lds_per_wave(d.S);
     // 128-thread blocks while two waves' rows fit comfortably in LDS, else 64-thread blocks
@@ -1576,6 +1662,21 @@ static void launch_disp(bool map, const int32_t *counts, const double *nf, FitDi
     const bool lds3 = (int64_t)(160 * 1024 / (lds + 2048)) * waves_per_block >= 12;
     const bool three = lds3 && (map ? d.n >= 750000 : (d.n >= 3000000 || (d.S <= 4 && d.n >= 1500000)));
     const int min_waves = (o.min_waves >= 2 && o.min_waves <= 4) ? o.min_waves : (three ? 3 : 2);
+    // Filler waves (kernel: "front waves and fillers"; option "line_search_fillers"): the two-wave launch below, unchanged, as front waves
+    // at priority, plus half as many waves again at priority 0 that take rows from the schedule's end only.  Never without a class order
+    // to give the boundary (natural order, schedule 2, the small fits), and only where LDS lets the third wave in (S <= 8).
+    // Measured on one box, two waves -> two front waves + a filler per SIMD (profiles/r08_*): every SIMD got exactly two front waves and one
+    // filler (stamps: 1 024 x (2, 1)); a front wave ticks at 8.6 us beside one front wave and one filler (7.97 in the two-wave launch, 7.1 for
+    // a lone priority wave between two priority-0 waves), a filler at 18.8 us; the queue is empty at 1.04 instead of 1.18 ms and the last
+    // wave leaves at 1.29 instead of 1.36 ms (DIAG clock).  Gene-wise stage by HIP events, fillers off -> on: 2 M x 8 1.300 -> 1.237 ms
+    // (stop share 100 / 85 / 70 / 40: 1.246 / 1.237 / 1.243 / 1.279), 2.5 M x 8 1.53 -> 1.46; nothing at 1.5 M x 8 (1.036 -> 1.027) and
+    // 2 M x 4 (1.08 -> 1.10 beside the two-wave build, which the rule does not pick there); slower where the launch is all chain: 1 M x 8
+    // 0.81 -> 0.83, 500 k x 8 0.61 -> 0.61, 250 k x 8 0.49 -> 0.51.  Against the three-wave build the rule picks from 3 M rows: 3 M x 8
+    // 1.73 -> 1.68, 4 M x 8 2.16 -> 2.18 — not taken there (not measured in whole steps).  So: on from 1.75 M rows (half-way between the
+    // two measured sizes on either side) up to where three uniform waves take over, at 4 < S <= 8; whole steps at 2 M x 8, six alternating runs:
+    // 3.555 (3.551 - 3.564) -> 3.483 ms (3.476 - 3.495); the other shapes of DESIGN.md section 5 within their spread (profiles/r08_ab_summary.txt).
+    const bool fill_can = sched && o.schedule != 2 && lds3 && min_waves == 2;
+    const bool fill = fill_can && (o.fillers == 1 || (o.fillers < 0 && kFillerRule && d.S > 4 && d.n >= kFillerMinRows));
     const int64_t by_regs = (int64_t)(4 * min_waves) / waves_per_block;
     if (blocks_per_cu > by_regs) blocks_per_cu = by_regs;
     if (blocks_per_cu > 8) blocks_per_cu = 8;
@@ -1583,6 +1684,8 @@ static void launch_disp(bool map, const int32_t *counts, const double *nf, FitDi
     const int64_t max_blocks = 256 * blocks_per_cu;
     if (blocks > max_blocks) blocks = max_blocks;
     if (blocks < 1) blocks = 1;
+    const unsigned int nfront = fill ? (unsigned int)(blocks * waves_per_block) : 0u;  // (the deal's "rows per lane" below are the front waves' too)
+    const int64_t front_blocks = blocks;
     // the gene-wise launch visits the rows likely-long first; schedule 2 (a fit that shares the GPU with other fits: the theta
     // grid's lanes) keeps the class order but deals nothing out statically — its waves are not all resident at once, and a wave
     // that starts late must not be the owner of likely-long rows
@@ -1603,7 +1706,9 @@ static void launch_disp(bool map, const int32_t *counts, const double *nf, FitDi
     const int classes_a = o.schedule == 2 ? 0 : (o.classes_a > 0 ? o.classes_a : (deal_most ? 5 : kSchedClassesA));
     if (sched) launch_order_build(d, w, sched_classes_a(classes_a, o.schedule), true, st, true);
     DispArgs A{counts, nf, d, w, o, nullptr, o.spread, sched ? w.order : nullptr, (deal_most && o.deal == 0) ? 4 : o.deal, 1, kChunk,
-               w.gridlist, reinterpret_cast<unsigned int *>(w.queue + (map ? 24 : 16)), o.prio};
+               w.gridlist, reinterpret_cast<unsigned int *>(w.queue + (map ? 24 : 16)), o.prio, nfront,
+               o.filler_stop >= 0 ? o.filler_stop : kFillerStopDefault};
+    if (fill) blocks = front_blocks + (front_blocks + 1) / 2;  // (<= 256 x 6 workgroups: one resident round of the three-wave build)
 #ifdef CHICDIFF_DIAG
     const char *stamp_file = getenv("CHICDIFF_DISP_STAMPS");  // diagnostic build only: blocking, never timed
     const size_t stamp_words = (size_t)blocks * (threads / 64) * kStampSlots;
@@ -1619,7 +1724,7 @@ static void launch_disp(bool map, const int32_t *counts, const double *nf, FitDi
     // (option "line_search_chunk" overrides; the rule is on the row count, not on rows per wave: the 3-waves-per-SIMD MAP build at
     // 200 k x 4 has 65 rows per wave and lost 0.157 -> 0.204 ms to 16-row chunks)
     A.chunk = o.chunk > 0 ? o.chunk : (d.n <= 65536 ? 16 : kChunk);
-    const int variant = min_waves;
+    const int variant = fill ? 3 : min_waves;
 #define LAUNCH(M, W) disp_fit_kernel<M, W><<<(unsigned)blocks, threads, lds, st>>>(A)
     if (map) {
         if (variant >= 4) LAUNCH(true, 4); else if (variant == 3) LAUNCH(true, 3); else LAUNCH(true, 2);

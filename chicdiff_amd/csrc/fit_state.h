@@ -55,7 +55,8 @@ struct FitScalars {
     int64_t ord_na, ord_n;
     // sharded selects run optimistically (no host look at sel_fast_done): a candidate list that did not fit (massive ties)
     // leaves this set, the host sees it with the fit's final scalars and refits with every histogram round
-    int32_t sel_overflow, _pad3;
+    int32_t sel_overflow;
+    int32_t ord_nb;  // gene-wise schedule: order[ord_nb, ord_n) are the rows that cannot be long (score >= 3.16 and what is behind them): the filler waves' end of the queue
     // what the host reads when a fit ends, gathered here by the fit's last kernel so that ONE copy brings everything back:
     // [0] deviance sum, [1] non-converged rows, [2] all-zero rows, then four verdicts of this rank (all seven summed over the ranks
     // of a sharded fit): [3] trend kernel's grid barrier timed out, [4] negative / NA count, [5] a select's candidate list overflowed

@@ -86,6 +86,12 @@ int32_t chicdiff_hip_last_refits(const chicdiff_hip_ctx *ctx);
  *                               start at minDisp in front of the score >= 3.16 rows); 0 = natural row order; 3 = the six
  *                               half-decade classes of earlier releases (minDisp starts last); 4 = as 1, minDisp starts last
  *   "line_search_deal"          0 (default: chosen from the rows per wave), 1 .. 64: schedule entries per group of the static deal
+ *   "line_search_fillers"       -1 (default: by the launcher's rule) | 0 | 1: the gene-wise line search runs its two waves per SIMD at
+ *                               issue priority and adds a third at priority 0 that takes only rows from the schedule's end (score >= 3.16:
+ *                               never long); always off where the schedule has no class order ("line_search_schedule" 0, small fits, the
+ *                               theta grid's concurrent fits) and at S > 8
+ *   "line_search_filler_stop"   -1 (default: 100) | 0 .. 100: fillers stop claiming once the other waves have claimed this share (percent) of
+ *                               their own part of the queue (100 = never, 0 = fillers claim nothing)
  *   "theta_grid_concurrency"    5 (default), 1 .. 16: fits of the theta grid in flight at once (single rank only)
  *   "host_copy_threads"         12 (default), 1 .. 64: host threads staging caller buffers in chicdiff_hip_nbglm_fit
  *   "select_all_rounds"         0 (default) | 1: exact medians by histogram rounds only (no candidate-sort shortcut)
@@ -383,6 +389,13 @@ int chicdiff_hip_selftest_prior_mc(int32_t df, const double *hist40, double *den
  * first class that goes through the queue when 0 .. 6 of the half-decade classes are dealt out statically. */
 int chicdiff_hip_selftest_sched_class(int32_t mode, double min_disp, const double *alpha_init, const double *group_mean, int64_t n,
                                       int32_t *cls_out, int32_t *bounds);
+/* _queue_claim (host only): the claim rule of the gene-wise line search's two-ended queue, as the kernel applies it.  `old` is the
+ * queue word before the claim (claims from the head in its low half, from the end in its high half).  Returns 1 if a claim that found
+ * `old` is valid, 0 if not, and the chunk it names in *chunk_out; *again_out (may be NULL): whether a filler wave whose claim found
+ * `old` (claimed != 0; claimed == 0: a filler that has not claimed yet) may claim once more, given the first chunk that lies wholly
+ * in the rows fillers may take (first_back; >= chunks: none) and the stop share in percent ("line_search_filler_stop"). */
+int chicdiff_hip_selftest_queue_claim(uint64_t old, int32_t back, uint32_t chunks, uint32_t first_back, int32_t stop_percent, int32_t claimed,
+                                      uint32_t *chunk_out, int32_t *again_out);
 
 /* Timing of the last *_dev call's kernels, measured with HIP events on the context's stream:
  * fills up to `cap` (name, milliseconds, launches) records; returns the number available. */

@@ -9,6 +9,9 @@ drain tick: it put the three-waves launch of the six-class order at 1.22 ms wher
 ORDERS for a shape (other S, other class edges), not to predict a time.
 
 usage: python tools/queue_model.py [--rows 200000] [--samples 8] [--tile-to 2000000] [--waves-per-simd 2] [--edges e1,e2,...]
+                                   [--fillers FRONT ALONE FILLER [--filler-stop 100 85 ...]]
+  --fillers: also the two-ended queue of the front-waves-and-fillers launch (two front waves + one filler per SIMD), with a tick
+             length per role in us, for the stop shares given — the order of the settings before GPU time is spent on them
   --edges: score edges of an order to try besides the built-in ones (rows at minDisp and scores above the last edge go last)"""
 import argparse
 import os
@@ -75,6 +78,78 @@ def simulate(cost, order, n_deal, waves, tick_bulk, tick_drain):
     return tick_empty, tick, (tick_empty * tick_bulk + (tick - tick_empty) * tick_drain) / 1e3, evals
 
 
+def simulate_two_ended(cost, order, n_deal, n_back, fronts, fillers, pace_front, pace_front_alone, pace_fill, tick_drain, stop_share):
+    """Front waves and fillers (disp_kernels.hip): `fronts` waves take the static deal and the queue from its head and tick every
+    pace_front us while any filler is at work (pace_front_alone after that, tick_drain once the queue is empty); `fillers` waves tick
+    every pace_fill us and take rows from the queue's END, down to schedule position n_back (the first row that cannot be long), while
+    the head has not passed stop_share of the front's own rows.  Rows, not chunks; each group ticks in step.  Returns the time the
+    queue ran empty, the time the last front wave / the last filler finished (us) and the share of the evaluations the fillers did."""
+    L = 64
+    queue = cost[order[n_deal:]].astype(np.int32)
+    kb = max(n_back - n_deal, 0)
+    stop_head = len(queue) + 1 if stop_share >= 100 else int(np.ceil(min(kb, len(queue)) * stop_share / 100.0))
+    dealt = cost[order[:n_deal]].astype(np.int32)
+    g = np.arange(len(dealt)) // DEAL_GROUP
+    deal_of = [dealt[g % fronts == w] for w in range(fronts)] if n_deal else [np.zeros(0, np.int32)] * fronts
+    deal_len = np.array([len(x) for x in deal_of])
+    deal = np.zeros((fronts, max(int(deal_len.max()), 1)), np.int32)
+    for w, x in enumerate(deal_of):
+        deal[w, :len(x)] = x
+    deal_pos = np.zeros(fronts, np.int64)
+    rem_f, rem_b = np.zeros((fronts, L), np.int32), np.zeros((max(fillers, 1), L), np.int32)
+    head, tail = 0, len(queue)
+    t_f = t_b = 0.0
+    t_empty = None
+    end_f = end_b = 0.0
+    ev_f = ev_b = 0
+    fill_on = fillers > 0 and stop_head > 0 and kb < len(queue)
+    while True:
+        if fill_on and t_b <= t_f:  # the fillers' tick
+            free = rem_b == 0
+            can = max(tail - max(head, kb), 0) if head < stop_head else 0
+            take = min(int(free.sum()), can)
+            if take:
+                idx = np.flatnonzero(free.ravel())[:take]
+                rem_b.ravel()[idx] = queue[tail - take:tail][::-1]
+                tail -= take
+            busy = rem_b > 0
+            if not busy.any():
+                fill_on = False
+                continue
+            ev_b += int(busy.sum())
+            rem_b -= busy
+            t_b += pace_fill
+            end_b = t_b
+            continue
+        free = rem_f == 0
+        nfree = free.sum(1)
+        from_deal = np.minimum(nfree, deal_len - deal_pos)
+        rank = np.cumsum(free, 1) - 1
+        take_deal = free & (rank < from_deal[:, None])
+        rem_f = np.where(take_deal, np.take_along_axis(deal, np.minimum(deal_pos[:, None] + rank, deal.shape[1] - 1), 1), rem_f)
+        deal_pos += from_deal
+        need = nfree - from_deal
+        start = head + np.cumsum(need) - need
+        qi = start[:, None] + rank - from_deal[:, None]
+        take_q = free & ~take_deal & (qi < tail)
+        if len(queue):
+            rem_f = np.where(take_q, queue[np.minimum(qi, len(queue) - 1)], rem_f)
+        head = min(head + int(need.sum()), tail)
+        if t_empty is None and head >= tail and np.all(deal_pos >= deal_len):
+            t_empty = t_f
+        busy = rem_f > 0
+        if not busy.any():
+            if not fill_on:
+                break
+            t_f = t_b + 1e-9  # (front waves are done: only the fillers' ticks are left)
+            continue
+        ev_f += int(busy.sum())
+        rem_f -= busy
+        t_f += tick_drain if t_empty is not None else (pace_front if fill_on else pace_front_alone)
+        end_f = t_f
+    return t_empty, end_f, end_b, ev_b / max(ev_f + ev_b, 1)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rows", type=int, default=200000, help="rows the oracle fits")
@@ -83,6 +158,10 @@ def main():
     ap.add_argument("--waves-per-simd", type=int, default=2)
     ap.add_argument("--tick-us", type=float, nargs=2, default=None, help="bulk and drain tick (default 8.0 / 10.56 for two / three waves, 4.4)")
     ap.add_argument("--edges", type=str, default=None)
+    ap.add_argument("--fillers", type=float, nargs=3, default=None, metavar=("FRONT", "ALONE", "FILLER"),
+                    help="also model two front waves + one filler per SIMD on the default order: us per tick of a front wave beside a filler, of a front "
+                         "wave once the fillers are gone, and of a filler (measured at 2 M x 8: 8.6 7.97 18.8)")
+    ap.add_argument("--filler-stop", type=int, nargs="*", default=[100, 85, 70, 40], help="stop shares (percent) to model with --fillers")
     a = ap.parse_args()
     from chicdiff_amd import synth
     from oracle import oracle
@@ -124,6 +203,16 @@ def main():
             n_deal = int(((cost >= 50) | ((score < DEAL_BELOW) & ~at_min)).sum())
         te, t, ms, evals = simulate(cost, order, n_deal, waves, bulk, drain)
         print(f"  {name:45s} queue empty at tick {te:4d}, end {t:4d}  (~{ms:.2f} ms), {evals} evaluations")
+    if a.fillers:
+        cls = orders["1/8 decade, minDisp starts before 3.16"]
+        order = np.argsort(cls, kind="stable")
+        n_deal = int(((score < DEAL_BELOW) & ~at_min).sum())
+        n_back = int((at_min | (score < 3.16)).sum())  # schedule position of the first row of score >= 3.16
+        pf, pa, pb = a.fillers
+        print(f"front waves and fillers (2 + 1 per SIMD), ticks {pf} / {pa} / {pb} us, drain {drain} us; rows fillers may take: {len(cost) - n_back}:")
+        for share in [0] + list(a.filler_stop):
+            te, ef, eb, part = simulate_two_ended(cost, order, n_deal, n_back, 256 * 8, 256 * 4, pf, pa, pb, drain, share)
+            print(f"  stop share {share:3d}: queue empty at {te / 1e3:.3f} ms, last front wave out {ef / 1e3:.3f}, last filler out {eb / 1e3:.3f}, fillers did {part * 100:.1f} % of the evaluations")
 
 
 if __name__ == "__main__":

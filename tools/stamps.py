@@ -17,7 +17,7 @@ dk, dn = ctx.to_device(d["counts"], np.int32), ctx.to_device(d["nf"], np.float64
 ctx.nbglm_fit(dk, dn, d["group"])
 raw = np.fromfile("gpurun_out/stamps.bin", dtype=np.uint64)
 pos = 0
-K = 34
+K = 36
 while pos < len(raw):
     kind, nw = int(raw[pos]), int(raw[pos + 1]); pos += 2
     st = raw[pos:pos + nw * K].reshape(nw, K).astype(np.int64); pos += nw * K
@@ -50,6 +50,23 @@ while pos < len(raw):
     print("  s_memtime cycles per tick (tick start to next tick start): row-per-lane %.0f, spread %.0f, burst %.0f  (100 MHz clock? ratio to us: %.1f)" % (*per, np.nansum(cy) / max(dr.sum(), 1e-9)))
     bulk = us(st[qe, 1]) / np.maximum(st[qe, 7] - tot, 1)
     print("  us per tick before q-empty: med %.2f; total ticks per wave: med %d" % (np.median(bulk), np.median(st[qe, 7])))
+    role = st[:, 34]
+    if kind == 0 and (role[ran] == 1).any():  # front waves and fillers (option line_search_fillers): pace, queue-empty and exit per role, and where the roles landed
+        allt = np.maximum(st[:, 7], 1)
+        for nm, m in (("front waves", ran & (role == 0)), ("fillers", ran & (role == 1))):
+            e = m & qe
+            print("    %-11s %4d: us per bulk tick med %.2f, ticks per wave med %d, q-empty med %.1f max %.1f us, exit med %.1f p99 %.1f max %.1f us" %
+                  (nm, m.sum(), np.median((us(st[e, 1]) / np.maximum(st[e, 7] - st[e, 4:7].sum(1), 1))), np.median(allt[m]), np.median(us(st[e, 1])), us(st[e, 1]).max(),
+                   np.median(us(st[m, 2])), np.percentile(us(st[m, 2]), 99), us(st[m, 2]).max()))
+        simd = st[:, 35] >> 4 & 3 | (st[:, 35] >> 8 & 0xff) << 2 | (st[:, 35] >> 16 & 7) << 10  # (XCC, SE / SH / CU, SIMD)
+        per = {}
+        for sd, r in zip(simd[ran], role[ran]):
+            f, b = per.get(int(sd), (0, 0))
+            per[int(sd)] = (f + int(r == 0), b + int(r == 1))
+        shapes = {}
+        for fb in per.values():
+            shapes[fb] = shapes.get(fb, 0) + 1
+        print("    SIMDs by (front waves, fillers) resident: " + ", ".join("%s x %d" % (k, v) for k, v in sorted(shapes.items())))
     if os.environ.get("STAMPS_SPLIT3"):  # (experiment: every third workgroup's waves run at s_setprio(3): option line_search_prio = 100)
         wv = np.nonzero(qe)[0]
         hi = (wv // 2) % 3 == 0
