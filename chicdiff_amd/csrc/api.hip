@@ -74,6 +74,7 @@ struct chicdiff_hip_ctx {
     int opt_fake_world = 0;
     int opt_mad_in_kernel = 1; // the persistent trend kernel also takes the median / MAD of the residuals (0: separate launches, as round 3)
     int opt_fault = 0;
+    int opt_assemble_generic = 0;  // test option "region_assemble_generic": every tile of region_assemble takes the generic path
     int refits = 0;               // refits the last call went through (select overflow / barrier timeout / local substitute), for the tests
     bool sf_overflow_seen = false;  // fit_dev_impl: some rank's size-factor select (run by the caller just before) overflowed
     int32_t *d_carry = nullptr;   // device word that survives the fit's clearing of its scalars: sel_overflow of the size-factor select
@@ -211,6 +212,7 @@ int chicdiff_hip_set_option(chicdiff_hip_ctx *c, const char *name, int64_t value
         c->opt_fake_world = (int)value;
     }
     else if (k == "trend_mad_in_kernel" && (value == 0 || value == 1)) c->opt_mad_in_kernel = (int)value;
+    else if (k == "region_assemble_generic" && (value == 0 || value == 1)) c->opt_assemble_generic = (int)value;
     else return fail(c, CHICDIFF_E_INVALID, "set_option: unknown option or value (%s = %lld)", name, (long long)value);
     return CHICDIFF_OK;
 }
@@ -1982,6 +1984,49 @@ extern "C" int chicdiff_hip_count_join_multi_dev(chicdiff_hip_ctx *c, const int3
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     timing_collect(c);
+    return CHICDIFF_OK;
+}
+
+// a1 + a3 + a2 fused (chicdiff.R:843-858, 628-703, 894-896, 1540-1547; chinput branch): region-level N and FullMean without the two
+// per-fragment matrices — bit for bit count_join_multi -> fragment_background -> window_sums
+extern "C" int chicdiff_hip_region_assemble_dev(chicdiff_hip_ctx *c, const int32_t *d_ru_bait, const int32_t *d_ru_oe, int64_t nru,
+                                                const int64_t *d_region_ptr, int64_t n, int32_t S, const int64_t *const *d_keys,
+                                                const int32_t *const *d_vals, const int64_t *nkeys, int32_t id_min, int32_t nid,
+                                                const int64_t *d_midsum, const double *d_sj, const double *d_si, const int32_t *d_tblb,
+                                                const int32_t *d_tlb, const double *d_T, int32_t ntblb, int32_t ntlb,
+                                                const double *distfun_host, int32_t *d_N, double *d_FullMean) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (S < 1 || S > kMaxS) return fail(c, CHICDIFF_E_INVALID, "region_assemble: need 1 <= S <= %d (S = %d)", kMaxS, (int)S);
+    if (!d_region_ptr || n < 1 || nru < 0 || (nru > 0 && (!d_ru_bait || !d_ru_oe)))
+        return fail(c, CHICDIFF_E_INVALID, "region_assemble: bad arguments (region_ptr / n / nru / RU rows)");
+    if (!d_N && !d_FullMean) return fail(c, CHICDIFF_E_INVALID, "region_assemble: neither N nor FullMean is asked for");
+    if (d_N) {
+        if (!d_keys || !d_vals || !nkeys) return fail(c, CHICDIFF_E_INVALID, "region_assemble: N needs the key tables");
+        for (int s = 0; s < S; s++)
+            if (nkeys[s] < 0 || (nkeys[s] > 0 && (!d_keys[s] || !d_vals[s])))
+                return fail(c, CHICDIFF_E_INVALID, "region_assemble: bad table %d", s);
+    }
+    if (d_FullMean && (!d_midsum || !d_sj || !d_si || !d_tblb || !d_tlb || !d_T || !distfun_host || nid < 1 || ntblb < 1 || ntlb < 1))
+        return fail(c, CHICDIFF_E_INVALID, "region_assemble: FullMean needs the background tables");
+    HIPCHK(c, hipSetDevice(c->device));
+    // the context's scratch: the distance functions, then the coarse levels of the key tables
+    const size_t df_bytes = sizeof(double) * 10 * kMaxS;
+    if (int rc = ensure_aux(c, df_bytes + (d_N ? count_join_multi_scratch_bytes(S, nkeys) : 0))) return rc;
+    double *d_df = reinterpret_cast<double *>(c->aux);
+    hipError_t e = hipSuccess;
+    if (d_FullMean) e = hipMemcpyAsync(d_df, distfun_host, sizeof(double) * 10 * S, hipMemcpyHostToDevice, c->stream);
+    timing_reset(c);
+    hipError_t le = hipSuccess;
+    if (e == hipSuccess) {
+        Scope t(c, "region_assemble");
+        le = launch_region_assemble(d_ru_bait, d_ru_oe, nru, d_region_ptr, n, S, d_keys, d_vals, nkeys, id_min, nid, d_midsum, d_sj, d_si,
+                                    d_tblb, d_tlb, d_T, ntblb, ntlb, d_df, d_N, d_FullMean, c->aux + df_bytes, c->opt_assemble_generic,
+                                    c->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // distfun_host may be a temporary
+    timing_collect(c);
+    if (le != hipSuccess) return fail(c, CHICDIFF_E_HIP, "region_assemble: launch of region_assemble_kernel failed: %s", hipGetErrorString(le));
+    if (e != hipSuccess) return fail(c, CHICDIFF_E_HIP, "region_assemble: %s", hipGetErrorString(e));
     return CHICDIFF_OK;
 }
 

@@ -288,6 +288,11 @@ void launch_region_avdist(const int32_t *bait, const int32_t *oe, const int64_t 
 size_t count_join_multi_scratch_bytes(int S, const int64_t *nkeys);
 void launch_count_join_multi(const int32_t *bait, const int32_t *oe, int64_t nru, int S, const int64_t *const *keys, const int32_t *const *vals,
                              const int64_t *nkeys, int32_t *out, void *scratch, hipStream_t st);
+hipError_t launch_region_assemble(const int32_t *bait, const int32_t *oe, int64_t nru, const int64_t *rptr, int64_t n, int S,
+                                  const int64_t *const *keys, const int32_t *const *vals, const int64_t *nkeys, int32_t id_min, int32_t nid,
+                                  const int64_t *midsum, const double *sj, const double *si, const int32_t *tblb, const int32_t *tlb,
+                                  const double *T, int32_t ntblb, int32_t ntlb, const double *distfun_dev, int32_t *N, double *FM,
+                                  void *scratch, int force_generic, hipStream_t st);
 void launch_count_join_inner(const int32_t *bait, const int32_t *oe, int64_t nru, int S, const int64_t *const *keys,
                              const int32_t *const *vals, const int64_t *nkeys, int32_t *out, hipStream_t st);
 void launch_math_selftest(int op, const double *x, int64_t n, double *out, hipStream_t st);

@@ -1792,42 +1792,59 @@ struct BgArgs {
 // fragment IDs, the two midpoints and log|distance| are the same for every replicate — S - 1 of every S logarithms, ID loads and
 // midpoint gathers were repeats — and a caller that wants FullMean alone (chicdiff.R:896: the one column DESeq2Wrap reads) passes
 // NULL for the other two and saves two thirds of the stores.  Same expressions in the same order: same bits.
+// The body of a3, shared by fragment_background_kernel and region_assemble_kernel (the library is built with -ffp-contract=off: the
+// same expressions in the same order give the same bits wherever they are inlined).
+// bg_row_geometry: what is the same for every replicate — the two fragments' indices into the dense tables, whether both are on
+// the map, and log|distance| (0 where they are not: never read).
+__device__ __forceinline__ bool bg_row_geometry(const BgArgs &a, int32_t bait, int32_t oe, int32_t &b, int32_t &o, double &ld) {
+    b = bait - a.id_min;
+    o = oe - a.id_min;
+    const bool on_map = b >= 0 && b < a.nid && o >= 0 && o < a.nid;
+    ld = 0.0;
+    if (on_map) {
+        const double dist = rint((double)(a.midsum[o] - a.midsum[b]) / 2.0);  // R round(): half to even
+        ld = log(fabs(dist));
+    }
+    return on_map;
+}
+// bg_row_replicate: Bmean and Tmean of one row for replicate s; p = the replicate's ten distance-function parameters
+__device__ __forceinline__ void bg_row_replicate(const BgArgs &a, const double *p, int s, int32_t b, int32_t o, bool on_map, double ld,
+                                                 double &B, double &Tm) {
+    B = NAN;
+    Tm = NAN;
+    if (on_map) {
+        const double s_j = a.sj[(int64_t)s * a.nid + b];
+        double s_i = a.si[(int64_t)s * a.nid + o];
+        if (s_i != s_i) s_i = 1.0;
+        double e;
+        if (ld > p[9]) e = p[6] + ld * p[7];
+        else if (ld < p[8]) e = p[4] + ld * p[5];
+        else e = p[0] + p[1] * ld + p[2] * (ld * ld) + p[3] * (ld * ld * ld);
+        B = s_j * s_i * exp(e);
+        const int32_t tb = a.tblb[(int64_t)s * a.nid + b], tl = a.tlb[(int64_t)s * a.nid + o];
+        if (tb >= 0 && tl >= 0) {
+            Tm = a.T[((int64_t)s * a.ntblb + tb) * a.ntlb + tl];
+        } else if (tb >= 0) {
+            double m = INFINITY;
+            for (int k = 0; k < a.ntlb; k++) {
+                const double v = a.T[((int64_t)s * a.ntblb + tb) * a.ntlb + k];
+                if (v == v && v < m) m = v;
+            }
+            Tm = isfinite(m) ? m : NAN;
+        }
+    }
+}
 __global__ __launch_bounds__(256) void fragment_background_kernel(BgArgs a) {
     extern __shared__ double s_df[];  // S x 10: the replicates' distance functions
     for (int k = threadIdx.x; k < 10 * a.S; k += 256) s_df[k] = a.distfun[k];
     __syncthreads();
     for (int64_t r = blockIdx.x * 256 + threadIdx.x; r < a.nru; r += (int64_t)gridDim.x * 256) {
-        const int32_t b = a.bait[r] - a.id_min, o = a.oe[r] - a.id_min;
-        const bool on_map = b >= 0 && b < a.nid && o >= 0 && o < a.nid;
-        double ld = 0.0;
-        if (on_map) {
-            const double dist = rint((double)(a.midsum[o] - a.midsum[b]) / 2.0);  // R round(): half to even
-            ld = log(fabs(dist));
-        }
+        int32_t b, o;
+        double ld;
+        const bool on_map = bg_row_geometry(a, a.bait[r], a.oe[r], b, o, ld);
         for (int s = 0; s < a.S; s++) {
-            double B = NAN, Tm = NAN;
-            if (on_map) {
-                const double *p = s_df + 10 * s;
-                const double s_j = a.sj[(int64_t)s * a.nid + b];
-                double s_i = a.si[(int64_t)s * a.nid + o];
-                if (s_i != s_i) s_i = 1.0;
-                double e;
-                if (ld > p[9]) e = p[6] + ld * p[7];
-                else if (ld < p[8]) e = p[4] + ld * p[5];
-                else e = p[0] + p[1] * ld + p[2] * (ld * ld) + p[3] * (ld * ld * ld);
-                B = s_j * s_i * exp(e);
-                const int32_t tb = a.tblb[(int64_t)s * a.nid + b], tl = a.tlb[(int64_t)s * a.nid + o];
-                if (tb >= 0 && tl >= 0) {
-                    Tm = a.T[((int64_t)s * a.ntblb + tb) * a.ntlb + tl];
-                } else if (tb >= 0) {
-                    double m = INFINITY;
-                    for (int k = 0; k < a.ntlb; k++) {
-                        const double v = a.T[((int64_t)s * a.ntblb + tb) * a.ntlb + k];
-                        if (v == v && v < m) m = v;
-                    }
-                    Tm = isfinite(m) ? m : NAN;
-                }
-            }
+            double B, Tm;
+            bg_row_replicate(a, s_df + 10 * s, s, b, o, on_map, ld, B, Tm);
             if (a.bmean) a.bmean[(int64_t)s * a.nru + r] = B;
             if (a.tmean) a.tmean[(int64_t)s * a.nru + r] = Tm;
             if (a.fullmean) a.fullmean[(int64_t)s * a.nru + r] = B + Tm;
@@ -1843,6 +1860,240 @@ void launch_fragment_background(const int32_t *bait, const int32_t *oe, int64_t 
     if (blocks > 8192) blocks = 8192;
     if (blocks < 1) blocks = 1;
     fragment_background_kernel<<<(unsigned)blocks, 256, sizeof(double) * 10 * S, st>>>(a);
+}
+
+// a1 + a3 + a2 in one kernel (chinput branch only: chicdiff.R:843-858, 628-703, 894-896, 1540-1547): region-level N and FullMean
+// straight from the RU rows, the replicates' key tables and the Chicago background tables.  Neither per-fragment matrix exists:
+// per region 8 F bytes read for the RU rows (F = fragments per region) + 12 nkeys / n per replicate for the tables, 12 S written,
+// against 8 F + 12 S F written and 12 S F read again by count_join_multi -> fragment_background -> window_sums.
+// Equal to those three calls bit for bit: the join is join_tile_table (its result does not depend on which lane holds which
+// query), FullMean is bg_row_geometry / bg_row_replicate, and a lane adds up its region's rows one after the other in ascending
+// row order from 0 / 0.0, as window_sums_kernel does.  The branch without chinput files (count_join_inner: Reduce(merge) semantics,
+// a pair counts only where every replicate holds it) is NOT covered; it keeps the three calls.
+// Work unit: a wave owns a tile of kAsmRegions consecutive regions = the consecutive RU rows rptr[i0] .. rptr[i1].
+//   * kAsmRegions = 46: with the default RUexpand = 5 a region has at most 11 rows, so 46 regions (506 rows) fill the 512-row
+//     join tile; the tiling is fixed (region i belongs to tile i / 46), so no scan and no host read decides it.
+//   * tile path (the tile's rows fit the join tile): row f0 + 64 k + lane goes to query k of the lane (coalesced dword loads — region
+//     starts are not 16-byte aligned), log|distance| is formed once per row; then per replicate FullMean of the rows, and after
+//     that per replicate the join: either to the wave's LDS slice, where lane k < 46 adds up region i0 + k and stores.  The value
+//     buffer (512 x 12 bytes) overlays the key window (768 x 12 bytes), which is dead once join_tile_table has returned, and
+//     log|distance| waits in the window's other half while FullMean is formed: 36 864 bytes per workgroup + the distance
+//     functions, four workgroups = 16 waves per CU as count_join_multi_kernel (107 registers, no scratch).
+//   * generic path (a tile with more rows — a caller's own CSR with long regions — or the test option region_assemble_generic):
+//     lane k walks region i0 + k row by row, one binary search over the whole table per row and replicate.  The choice is
+//     wave-uniform and made here from rptr.
+// Row indices come from the caller's rptr: rows outside [0, nru) are never read (they count as absent).
+constexpr int kAsmRegions = 46;
+__device__ __forceinline__ int64_t uniform64(int64_t x) {  // a wave-uniform value, moved to scalar registers
+    const uint32_t l = __builtin_amdgcn_readfirstlane((uint32_t)x), h = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
+    return (int64_t)(((uint64_t)h << 32) | l);
+}
+struct RegionAssembleArgs {
+    const int32_t *bait, *oe;
+    int64_t nru;
+    const int64_t *rptr;
+    int64_t n;
+    JoinTables tb;  // the tables of this launch: replicates s0 .. s0 + tb.T - 1
+    BgArgs bg;      // the background tables of ALL replicates (bait / oe / nru / outputs unused); distfun = S x 10 on the device
+    int32_t s0, force_generic;
+    int32_t *N;  // n x S column-major, either may be NULL
+    double *FM;
+};
+__global__ __launch_bounds__(256, 4) void region_assemble_kernel(RegionAssembleArgs a) {
+    __shared__ __align__(16) char s_slice[4][kJoinCap * 12];
+    __shared__ double s_df[kJoinMaxTables * 10];
+    static_assert(2 * kJoinTile * 8 <= kJoinCap * 12 && kJoinTile * 4 <= kJoinCap * 4, "the value buffers overlay the key window");
+    const int T = a.tb.T;
+    if (a.FM)
+        for (int k = threadIdx.x; k < 10 * T; k += 256) s_df[k] = a.bg.distfun[10 * a.s0 + k];
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // scalar: so are the tile, its regions and its row range below
+    char *const slice = s_slice[wave];
+    int64_t *const sk = reinterpret_cast<int64_t *>(slice);  // key window: keys, then values
+    int32_t *const sv = reinterpret_cast<int32_t *>(slice + kJoinCap * 8);
+    double *const vf = reinterpret_cast<double *>(slice);    // value buffer, over it: FullMean where the keys were, N where the values were
+    int32_t *const vn = sv;
+    double *const vl = vf + kJoinTile;                       // ... and, until the joins start, the rows' log|distance| after FullMean
+    const int64_t ntile = (a.n + kAsmRegions - 1) / kAsmRegions;
+    // one contiguous share of the tiles per XCD, as count_join_kernel (blocks b and b + 8 share an XCD)
+    const int64_t per_xcd = (ntile + 7) / 8, t_begin = (int64_t)(blockIdx.x & 7) * per_xcd;
+    const int64_t t_end = t_begin + per_xcd < ntile ? t_begin + per_xcd : ntile;
+    // ONE tile per wave, no loop over tiles: around such a loop the compiler keeps the loop-invariant lane addresses and the
+    // constants of log / exp in registers across the joins — 128 registers and spills to scratch; without it 107 and none
+    const int64_t tile = t_begin + (int64_t)(blockIdx.x >> 3) * 4 + wave;
+    if (tile < t_end) {
+        const int lane = threadIdx.x & 63;
+        const int64_t i0 = tile * kAsmRegions;
+        const int nreg = a.n - i0 < kAsmRegions ? (int)(a.n - i0) : kAsmRegions;
+        int64_t lo = 0, hi = 0;
+        if (lane < nreg) {
+            lo = a.rptr[i0 + lane];
+            hi = a.rptr[i0 + lane + 1];
+        }
+        const int64_t f0 = a.rptr[i0], f1 = a.rptr[i0 + nreg];  // (wave-uniform: scalar loads)
+        const int64_t rows = f1 - f0;
+        if (!a.force_generic && rows >= 0 && rows <= kJoinTile) {
+            int64_t q[kJoinPerLane], kmin = INT64_MAX, kmax = INT64_MIN;
+            unsigned on_map = 0;
+#pragma unroll
+            for (int k = 0; k < kJoinPerLane; k++) {
+                const int64_t r = f0 + k * 64 + lane;
+                const bool v = k * 64 + lane < rows && r >= 0 && r < a.nru;
+                const int32_t qb = v ? a.bait[r] : 0, qo = v ? a.oe[r] : 0;
+                q[k] = ((int64_t)qb << 32) | (uint32_t)qo;
+                if (v) {
+                    kmin = q[k] < kmin ? q[k] : kmin;
+                    kmax = q[k] > kmax ? q[k] : kmax;
+                }
+                if (a.FM) {  // log|distance| waits in the lane's own words of the slice (the key window is idle until the joins)
+                    int32_t b, o;
+                    double ld = 0.0;
+                    if (v && bg_row_geometry(a.bg, qb, qo, b, o, ld)) on_map |= 1u << k;
+                    vl[k * 64 + lane] = ld;
+                }
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                const int64_t x = __shfl_xor(kmin, off), y = __shfl_xor(kmax, off);
+                kmin = x < kmin ? x : kmin;
+                kmax = y > kmax ? y : kmax;
+            }
+            kmin = uniform64(kmin);  // (the same in every lane: scalar registers from here on)
+            kmax = uniform64(kmax);
+            // the lane's region as a range of the value buffer
+            int64_t l64 = lo < f0 ? f0 : lo, h64 = hi > f1 ? f1 : hi;
+            const int l_ = (int)(l64 - f0), lh = l_ | ((h64 < l64 ? l_ : (int)(h64 - f0)) << 16);  // both <= 512: one register
+            // the replicates twice, FullMean first and then the joins: the joins' key windows need the whole slice and most of the
+            // 128 registers that 16 waves per CU leave a lane
+            if (a.FM) {
+#pragma unroll 1
+                for (int t = 0; t < T; t++) {
+#pragma unroll
+                    for (int k = 0; k < kJoinPerLane; k++) {
+                        double B, Tm;
+                        bg_row_replicate(a.bg, s_df + 10 * t, a.s0 + t, (int32_t)(q[k] >> 32) - a.bg.id_min, (int32_t)q[k] - a.bg.id_min,
+                                         (on_map >> k) & 1u, vl[k * 64 + lane], B, Tm);
+                        vf[k * 64 + lane] = B + Tm;
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    if (lane < nreg) {
+                        double s = 0;
+                        for (int f = lh & 0xffff, h = lh >> 16; f < h; f++) s += vf[f];
+                        a.FM[(int64_t)(a.s0 + t) * a.n + i0 + lane] = s;
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();  // the buffer is rewritten by the next replicate
+                }
+            }
+            if (a.N) {
+#pragma unroll 1
+                for (int t = 0; t < T; t++) {
+                    int32_t res[kJoinPerLane];
+                    if (kmin <= kmax) {  // (wave-uniform; a tile of empty regions asks nothing)
+                        const int64_t nk = a.tb.nkeys[t];
+                        join_tile_table(q, kmin, kmax, a.tb.keys[t], a.tb.vals[t], nk, a.tb.index[t], (nk + 63) / 64, sk, sv, lane, res);
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < kJoinPerLane; k++) res[k] = 0;
+                    }
+#pragma unroll
+                    for (int k = 0; k < kJoinPerLane; k++) vn[k * 64 + lane] = res[k];
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    if (lane < nreg) {
+                        int32_t s = 0;
+                        for (int f = lh & 0xffff, h = lh >> 16; f < h; f++) s += vn[f];
+                        a.N[(int64_t)(a.s0 + t) * a.n + i0 + lane] = s;
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();  // the slice is rewritten by the next replicate's key window
+                }
+            }
+        } else if (lane < nreg) {
+            const int64_t l = lo < 0 ? 0 : lo, h = hi > a.nru ? a.nru : hi;
+#pragma unroll 1
+            for (int t = 0; t < T; t++) {
+                const int64_t col = (int64_t)(a.s0 + t) * a.n + i0 + lane;
+                const int64_t *const keys = a.tb.keys[t];
+                const int64_t nk = a.tb.nkeys[t];
+                int32_t sN = 0;
+                double sF = 0;
+                for (int64_t r = l; r < h; r++) {
+                    const int32_t qb = a.bait[r], qo = a.oe[r];
+                    if (a.N) {
+                        const int64_t key = ((int64_t)qb << 32) | (uint32_t)qo;
+                        int64_t at = 0, len = nk;
+                        while (len > 0) {
+                            const int64_t half = len >> 1;
+                            if (keys[at + half] < key) {
+                                at += half + 1;
+                                len -= half + 1;
+                            } else {
+                                len = half;
+                            }
+                        }
+                        sN += (at < nk && keys[at] == key) ? a.tb.vals[t][at] : 0;
+                    }
+                    if (a.FM) {
+                        int32_t b, o;
+                        double ldr, B, Tm;
+                        const bool on = bg_row_geometry(a.bg, qb, qo, b, o, ldr);
+                        bg_row_replicate(a.bg, s_df + 10 * t, a.s0 + t, b, o, on, ldr, B, Tm);
+                        sF += B + Tm;
+                    }
+                }
+                if (a.N) a.N[col] = sN;
+                if (a.FM) a.FM[col] = sF;
+            }
+        }
+    }
+}
+// keys / vals / nkeys: host arrays of S entries (device pointers inside), NULL when N is; the background tables when FM is not NULL;
+// scratch: count_join_multi_scratch_bytes.  Returns the first launch error (hipGetLastError right after each launch).
+hipError_t launch_region_assemble(const int32_t *bait, const int32_t *oe, int64_t nru, const int64_t *rptr, int64_t n, int S,
+                                  const int64_t *const *keys, const int32_t *const *vals, const int64_t *nkeys, int32_t id_min, int32_t nid,
+                                  const int64_t *midsum, const double *sj, const double *si, const int32_t *tblb, const int32_t *tlb,
+                                  const double *T, int32_t ntblb, int32_t ntlb, const double *distfun_dev, int32_t *N, double *FM,
+                                  void *scratch, int force_generic, hipStream_t st) {
+    const int64_t ntile = (n + kAsmRegions - 1) / kAsmRegions;
+    const int64_t blocks = 8 * (((ntile + 7) / 8 + 3) / 4);  // a wave per tile; blocks b, b + 8, ... serve one XCD's contiguous share
+    int64_t *index = (int64_t *)scratch;
+    for (int s0 = 0; s0 < S; s0 += kJoinMaxTables) {
+        RegionAssembleArgs a{};
+        a.bait = bait;
+        a.oe = oe;
+        a.nru = nru;
+        a.rptr = rptr;
+        a.n = n;
+        a.tb.T = S - s0 < kJoinMaxTables ? S - s0 : kJoinMaxTables;
+        a.bg = BgArgs{nullptr, nullptr, 0, id_min, nid, S, ntblb, ntlb, midsum, sj, si, tblb, tlb, T, distfun_dev, nullptr, nullptr, nullptr};
+        a.s0 = s0;
+        a.force_generic = force_generic;
+        a.N = N;
+        a.FM = FM;
+        if (N) {
+            int64_t maxidx = 0;
+            for (int t = 0; t < a.tb.T; t++) {
+                a.tb.keys[t] = keys[s0 + t];
+                a.tb.vals[t] = vals[s0 + t];
+                a.tb.nkeys[t] = nkeys[s0 + t];
+                a.tb.index[t] = index;
+                const int64_t nidx = (nkeys[s0 + t] + 63) / 64;
+                index += nidx + 1;
+                maxidx = nidx > maxidx ? nidx : maxidx;
+            }
+            if (maxidx > 0) {
+                const int64_t bx = (maxidx + 255) / 256;
+                join_index_multi_kernel<<<dim3((unsigned)(bx > 1024 ? 1024 : bx), a.tb.T), 256, 0, st>>>(a.tb);
+                if (hipError_t e = hipGetLastError()) return e;
+            }
+        }
+        region_assemble_kernel<<<(unsigned)blocks, 256, 0, st>>>(a);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
 }
 
 // device-math self test (tests/test_gpu_parity.py::test_device_math): out[i] = f_op(x[i])

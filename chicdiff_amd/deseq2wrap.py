@@ -131,7 +131,9 @@ def DESeq2Wrap(chicdiff_settings, RU, FullRegionData, suffix="", theta=None, ctx
         group = np.array([levels.index(c) for c in conds], dtype=np.int32)
 
         # window sums (a2) -> counts and FullMean matrices, resident in HBM from here on
-        if region_ptr is None:
+        if region_ptr is None and "regionN" in FullRegionData:   # pipeline.getFullRegionData(assemble=True): already summed
+            d_N, d_FM = FullRegionData["regionN"], FullRegionData["regionFullMean"]
+        elif region_ptr is None:
             d_N, d_FM = ctx.window_sums(FullRegionData["fragN"], FullRegionData["fragFullMean"], FullRegionData["region_ptr"])
         else:
             d_N, d_FM = ctx.window_sums(ctx.to_device(fragN, np.int32), ctx.to_device(fragFM, np.float64),

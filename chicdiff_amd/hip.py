@@ -28,7 +28,7 @@ EXPORTS = [
     "chicdiff_hip_fragment_background_dev", "chicdiff_hip_bh_adjust_dev", "chicdiff_hip_ihw_apply_dev",
     "chicdiff_hip_region_universe_count_dev", "chicdiff_hip_region_universe_fill_dev", "chicdiff_hip_region_universe_dev", "chicdiff_hip_count_table_dev",
     "chicdiff_hip_chinput_read", "chicdiff_hip_chinput_table_dev", "chicdiff_hip_region_avdist_dev",
-    "chicdiff_hip_count_join_inner_dev", "chicdiff_hip_count_join_multi_dev",
+    "chicdiff_hip_count_join_inner_dev", "chicdiff_hip_count_join_multi_dev", "chicdiff_hip_region_assemble_dev",
     "chicdiff_hip_malloc", "chicdiff_hip_free", "chicdiff_hip_outstanding_allocations", "chicdiff_hip_memcpy_h2d", "chicdiff_hip_memcpy_d2h",
     "chicdiff_hip_rccl_unique_id", "chicdiff_hip_rccl_init", "chicdiff_hip_cooks_filter_dev",
     "chicdiff_hip_independent_filtering_dev",
@@ -129,6 +129,8 @@ def load_library() -> C.CDLL:
     L.chicdiff_hip_region_avdist_dev.argtypes = [vp, vp, vp, i64, vp, i64, i32, i32, vp, vp, vp]
     L.chicdiff_hip_count_join_inner_dev.argtypes = [vp, vp, vp, i64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp]
     L.chicdiff_hip_count_join_multi_dev.argtypes = [vp, vp, vp, i64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp]
+    L.chicdiff_hip_region_assemble_dev.argtypes = [vp, vp, vp, i64, vp, i64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), i32, i32,
+                                                   vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(dbl), vp, vp]
     L.chicdiff_hip_ihw_apply_dev.argtypes = [vp, vp, vp, i64, C.POINTER(dbl), C.POINTER(dbl), i32, vp, vp, vp, vp]
     L.chicdiff_hip_region_universe_count_dev.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp, vp, vp, C.POINTER(i64)]
     L.chicdiff_hip_region_universe_fill_dev.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp, vp, vp, vp]
@@ -337,6 +339,74 @@ class HipContext:
         self._check(self.lib.chicdiff_hip_count_join_multi_dev(self.h, d_bait.data_ptr(), d_oe.data_ptr(), nru, S, kp, vp_, nk,
                                                                out.data_ptr()))
         return out
+
+    def _check_tensor(self, name, t, dtype, shape=None):
+        """ValueError unless ``t`` is a contiguous tensor of ``dtype`` on this context's device (and of ``shape``, -1 = any)."""
+        torch = self.torch
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: a torch tensor is required, got {type(t).__name__}")
+        if t.dtype != dtype:
+            raise ValueError(f"{name}: dtype {dtype} is required, got {t.dtype}")
+        if t.device != self.device:
+            raise ValueError(f"{name}: must be on {self.device}, is on {t.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: must be contiguous")
+        if shape is not None and (t.dim() != len(shape) or any(w != -1 and w != g for w, g in zip(shape, t.shape))):
+            raise ValueError(f"{name}: shape {tuple(shape)} is required (-1 = any), got {tuple(t.shape)}")
+
+    def region_assemble(self, d_bait, d_oe, d_region_ptr, tables, id_min, d_midsum, d_sj, d_si, d_tblb, d_tlb, d_T, distfun,
+                        want_N=True, want_FullMean=True):
+        """Region-level N and FullMean (S, n) of the chinput branch in one kernel (chicdiff.R:843-858, 628-703, 894-896, 1540-1547):
+        bit for bit ``count_join_multi`` -> ``fragment_background(only_fullmean=True)`` -> ``window_sums`` on the same tensors, without
+        the two (S, nru) matrices in between.  ``tables`` = [(keys, vals)] per replicate; the other arguments as those three take
+        them.  Returns (N, FullMean); the one not wanted is None and its inputs are not read."""
+        torch = self.torch
+        if not (want_N or want_FullMean):
+            raise ValueError("region_assemble: neither N nor FullMean is wanted")
+        try:
+            S = len(tables)
+        except TypeError:
+            raise ValueError("region_assemble: tables must be a sequence of (keys, vals) pairs") from None
+        if not 1 <= S <= 64:
+            raise ValueError(f"region_assemble: 1 <= S <= 64 replicates are supported, got {S}")
+        self._check_tensor("d_bait", d_bait, torch.int32, (-1,))
+        self._check_tensor("d_oe", d_oe, torch.int32, (d_bait.numel(),))
+        self._check_tensor("d_region_ptr", d_region_ptr, torch.int64, (-1,))
+        nru, n = d_bait.numel(), d_region_ptr.numel() - 1
+        if n < 1:
+            raise ValueError("region_assemble: region_ptr must hold at least one region (two entries)")
+        for s, kv in enumerate(tables):
+            if not isinstance(kv, (tuple, list)) or len(kv) != 2:
+                raise ValueError(f"tables[{s}]: a (keys, vals) pair is required")
+            self._check_tensor(f"tables[{s}] keys", kv[0], torch.int64, (-1,))
+            self._check_tensor(f"tables[{s}] vals", kv[1], torch.int32, (-1,))
+            if kv[0].numel() != kv[1].numel():
+                raise ValueError(f"tables[{s}]: {kv[0].numel()} keys but {kv[1].numel()} vals")
+        self._check_tensor("d_midsum", d_midsum, torch.int64, (-1,))
+        nid = d_midsum.numel()
+        if nid < 1:
+            raise ValueError("d_midsum: empty restriction map")
+        self._check_tensor("d_sj", d_sj, torch.float64, (S, nid))
+        self._check_tensor("d_si", d_si, torch.float64, (S, nid))
+        self._check_tensor("d_tblb", d_tblb, torch.int32, (S, nid))
+        self._check_tensor("d_tlb", d_tlb, torch.int32, (S, nid))
+        self._check_tensor("d_T", d_T, torch.float64, (S, -1, -1))
+        if d_T.shape[1] < 1 or d_T.shape[2] < 1:
+            raise ValueError(f"d_T: shape (S, ntblb >= 1, ntlb >= 1) is required, got {tuple(d_T.shape)}")
+        df = np.ascontiguousarray(distfun, dtype=np.float64)
+        if df.shape != (S, 10):
+            raise ValueError(f"distfun: shape ({S}, 10) is required, got {df.shape}")
+        N = torch.empty((S, n), dtype=torch.int32, device=self.device) if want_N else None
+        FM = torch.empty((S, n), dtype=torch.float64, device=self.device) if want_FullMean else None
+        kp = (C.c_void_p * S)(*[k.data_ptr() for k, _ in tables])
+        vp_ = (C.c_void_p * S)(*[v.data_ptr() for _, v in tables])
+        nk = (C.c_int64 * S)(*[k.numel() for k, _ in tables])
+        self._check(self.lib.chicdiff_hip_region_assemble_dev(
+            self.h, d_bait.data_ptr(), d_oe.data_ptr(), nru, d_region_ptr.data_ptr(), n, S, kp, vp_, nk, int(id_min), nid,
+            d_midsum.data_ptr(), d_sj.data_ptr(), d_si.data_ptr(), d_tblb.data_ptr(), d_tlb.data_ptr(), d_T.data_ptr(),
+            d_T.shape[1], d_T.shape[2], df.ctypes.data_as(C.POINTER(C.c_double)),
+            N.data_ptr() if want_N else None, FM.data_ptr() if want_FullMean else None))
+        return N, FM
 
     def count_join_inner(self, d_bait, d_oe, tables):
         """No-chinput branch (chicdiff.R:774-807): ``tables`` = [(keys, vals)] per replicate (device tensors as

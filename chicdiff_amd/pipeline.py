@@ -218,13 +218,19 @@ def _countput(xs, conditions, rmap):
     return pd.concat(out, ignore_index=True)
 
 
-def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, read_chicago=None):
+def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, read_chicago=None, assemble=False):
     """chicdiff.R:1460-1478 with the device path behind it: list(test block, control block, countput).  Every Chicago
     data set and every chinput file is read ONCE for both universes (what ``parallel = TRUE`` -> getFullRegionData2,
     :948-1456, does in the reference; the result does not depend on it).  The long "recast" table (one row per region,
     fragment and sample) is never built: a block holds the per-sample fragment columns N and FullMean on the device in
-    (regionID, otherEndID) order, the region offsets, and IHWcorrection()'s per-region avDist."""
+    (regionID, otherEndID) order, the region offsets, and IHWcorrection()'s per-region avDist.
+    ``assemble=True`` (chinput branch only): a block holds the region-level ``regionN`` / ``regionFullMean`` (S, n) that DESeq2Wrap
+    would sum from the fragment columns — from one kernel (HipContext.region_assemble), same bits — and no fragment columns."""
     s = asChicdiffSettings(chicdiff_settings)
+    if assemble and s["countData"] is None:
+        raise ValueError("getFullRegionData(assemble=True) covers the chinput branch only: without countData the counts are "
+                         "reconstructed from the Chicago data sets and inner-merged (chicdiff.R:774-807), which keeps "
+                         "count_join_inner -> fragment_background -> window_sums; call it with assemble=False")
     if read_chicago is None:
         raise ValueError("read_chicago: a reader of the Chicago data sets is required (readRDSorRDA stays R)")
     torch = ctx.torch
@@ -273,6 +279,13 @@ def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, rea
         message("Reading data for significant interactions" if not is_control else "\nReading data for control interactions")
         d_bait, d_oe, ptr = u["csr_baitID"], u["csr_otherEndID"], u["region_ptr"]
         nfrag, n = d_bait.numel(), ptr.numel() - 1
+        if assemble:   # :843-858, :628-703 + :894-896 and DESeq2Wrap's sums (:1540-1547) in one kernel: no (S, nfrag) matrix exists
+            regN, regFM = ctx.region_assemble(d_bait, d_oe, ptr, tables, id_min, d_midsum, d_bg["sj"], d_bg["si"], d_bg["tblb"],
+                                              d_bg["tlb"], d_bg["T"], bg["distfun"])
+            avDist = ctx.region_avdist(d_bait, d_oe, ptr, id_min, d_midsum, d_chr)
+            blocks.append(post.HipRegionData(samples=names, condition=list(conditions), S=S, n=n, regionN=regN, regionFullMean=regFM,
+                                             region_ptr=ptr, avDist=avDist, dispersions=dispersions, is_control=is_control))
+            continue
         if countData is not None:
             fragN = ctx.count_join_multi(d_bait, d_oe, tables)   # the replicate loop of :843-858 as one pass over the RU rows
         else:
@@ -354,8 +367,8 @@ def IHWcorrection(chicdiff_settings, DESeqOut, FullRegionData, DESeqOutControl, 
     return out
 
 
-def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, rng=None):
-    """chicdiff.R:301-347, same stage order and messages."""
+def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, rng=None, assemble=False):
+    """chicdiff.R:301-347, same stage order and messages.  ``assemble``: passed to getFullRegionData."""
     from . import hip
     from .settings import hipDevice
     own = ctx is None
@@ -368,7 +381,8 @@ def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, r
         message("\n*** Running getControlRegionUniverse\n")
         RUcontrol = getControlRegionUniverse(chicdiff_settings, RU, ctx, rng=rng)
         message("\n*** Running getFullRegionData\n")
-        FullRegionData = getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=ctx, read_chicago=read_chicago)
+        FullRegionData = getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=ctx, read_chicago=read_chicago,
+                                           assemble=assemble)
         message("\n*** Running DESeq2Wrap for FullRegion\n")
         DESeqOut = DESeq2Wrap(chicdiff_settings, RU, FullRegionData[0], ctx=ctx)
         message("\n*** Running DESeq2Wrap for FullControlRegion\n")

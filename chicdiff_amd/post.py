@@ -65,7 +65,8 @@ def applyIHWweights(ctx, avDist, pvalue, minLogDist, maxLogDist, avWeights):
 
 class HipRegionData(dict):
     """Device-resident fragment block: ``samples, condition, S, n, fragN (S, nfrag) int32, fragFullMean (S, nfrag)
-    float64, region_ptr (n + 1) int64`` — what r/R/getFullRegionData_hip.R calls a chicdiffHipRegionData object."""
+    float64, region_ptr (n + 1) int64`` — what r/R/getFullRegionData_hip.R calls a chicdiffHipRegionData object.  A block of
+    pipeline.getFullRegionData(assemble=True) holds ``regionN`` / ``regionFullMean`` (S, n) in place of the two fragment columns."""
 
 
 def getFullRegionDataHip(ctx, RU, chinput_files, condition, background):

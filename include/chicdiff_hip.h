@@ -103,6 +103,7 @@ int32_t chicdiff_hip_last_refits(const chicdiff_hip_ctx *ctx);
  *                               coefficients then differ in summation order only (1e-13)
  *   "trend_mad_in_kernel"       1 (default) | 0: the single-launch trend kernel goes on to the residuals, their exact median and MAD
  *                               and the closed-form prior variance; 0 = separate launches (residuals, two radix selects): same bits
+ *   "region_assemble_generic"   0 (default) | 1: test option of chicdiff_hip_region_assemble_dev (see there): same bits
  *   "fault_inject"              0 (default); test hook, one-shot bits consumed by the next call: 1 = this rank reports a select
  *                               overflow in its next fit, 2 = a grid-barrier timeout of its trend kernel, 4 = an overflow of its
  *                               next size-factor select — to prove that all ranks of a sharded fit refit together
@@ -215,6 +216,28 @@ int chicdiff_hip_count_join_dev(chicdiff_hip_ctx *ctx, const int32_t *d_ru_bait,
 int chicdiff_hip_count_join_multi_dev(chicdiff_hip_ctx *ctx, const int32_t *d_ru_bait, const int32_t *d_ru_oe, int64_t nru,
                                       int32_t S, const int64_t *const *d_keys, const int32_t *const *d_vals,
                                       const int64_t *nkeys, int32_t *d_out);
+
+/* a1 + a3 + a2 in one kernel, chinput branch (chicdiff.R:843-858 the joins, :628-703 and :894-896 FullMean = Bmean + Tmean,
+ * :1540-1547 the per-region sums): region-level N and FullMean straight from the RU rows, the replicates' key tables and the
+ * Chicago background tables.  Nothing of size S x nru is allocated or written.
+ * CONTRACT: equal, bit for bit, to chicdiff_hip_count_join_multi_dev -> chicdiff_hip_fragment_background_dev (FullMean) ->
+ * chicdiff_hip_window_sums_dev on the same arguments, which stay for callers who want per-fragment values.
+ * d_ru_bait / d_ru_oe / nru, d_keys / d_vals / nkeys (HOST arrays of S entries, device pointers inside): as in
+ * chicdiff_hip_count_join_multi_dev; d_region_ptr / n: as in chicdiff_hip_window_sums_dev (an empty region gives 0 / 0.0; rows
+ * outside [0, nru) are never read); id_min .. distfun_host (S x 10, host): as in chicdiff_hip_fragment_background_dev.
+ * d_N (int32) and d_FullMean (double) are n x S column-major (column s = replicate s); either may be NULL, and then the key
+ * tables respectively the background tables are not read and may be NULL too.  1 <= S <= 64.
+ * The branch without chinput files (chicdiff_hip_count_join_inner_dev: a pair counts only where every replicate holds it) is
+ * NOT covered: it keeps the three calls.
+ * Test option "region_assemble_generic" (chicdiff_hip_set_option) 0 (default) | 1: every tile of regions takes the kernel's
+ * generic path (one region per lane, a search of the whole table per row), which otherwise serves tiles whose 46 regions hold
+ * more than 512 rows: same bits. */
+int chicdiff_hip_region_assemble_dev(chicdiff_hip_ctx *ctx, const int32_t *d_ru_bait, const int32_t *d_ru_oe, int64_t nru,
+                                     const int64_t *d_region_ptr, int64_t n, int32_t S, const int64_t *const *d_keys,
+                                     const int32_t *const *d_vals, const int64_t *nkeys, int32_t id_min, int32_t nid,
+                                     const int64_t *d_midsum, const double *d_sj, const double *d_si, const int32_t *d_tblb,
+                                     const int32_t *d_tlb, const double *d_T, int32_t ntblb, int32_t ntlb,
+                                     const double *distfun_host, int32_t *d_N, double *d_FullMean);
 
 /* a1, branch without chinput files (chicdiff.R:774-807, = :1202-1260 in getFullRegionData2): N comes from the
  * replicates' Chicago objects.  tempForCounts[[i]] = x[, c("baitID", "otherEndID", "N")] per replicate;
