@@ -40,16 +40,34 @@ struct KTimer {
     double bytes = 0;  // collectives: payload this rank handed to the transport
 };
 
+// options only the host reads (chicdiff_hip_set_option; the others are the tuning tail of cd::Opts); the defaults are what the benchmarks run
+struct HostOpts {
+    int select_all_rounds = 0;
+    int trend_one_launch_per_pass = 0;
+    int sharded_trend_gather = 1;  // sharded fits: gather the rows of the trend on every rank (two collectives) instead of one all-reduce per IRLS pass
+    int trend_mad_in_kernel = 1;   // the persistent trend kernel also takes the median / MAD of the residuals (0: separate launches)
+    int local_trend_substitute = 1;  // 0: a failed parametric trend is reported (CHICDIFF_ST_TREND_FAILED), not replaced by the local fit
+    int fuse_offsets = 1;  // 0 = offsets always as a launch of their own, 2 = always inside prep: the bit-identity test
+    int theta_grid_concurrency = 5;  // theta grid: fits in flight at once (1 = one after the other)
+    int host_copy_threads = 12;      // host threads that move caller buffers to / from the pinned staging area
+    // bench hook (a 1-rank communicator only): the trend's rows are gathered as if N ranks had each sent this rank's block — the
+    // single-launch trend + MAD kernel then runs on N x n rows, which is what EVERY rank of an N-GPU fit does (bench.py's rehearsal
+    // of a rank's step at its share of the rows; the coefficients are those of the n rows up to rounding)
+    int bench_fake_world = 0;
+    // test hook (one-shot bits, consumed by the next call that reaches the step): 1 = this rank's fit reports a select candidate-list
+    // overflow, 2 = this rank's persistent trend kernel reports a grid-barrier timeout, 4 = this rank's size-factor select reports an
+    // overflow.  Each verdict is all-reduced, so every rank of a sharded fit must re-enter together.
+    int fault_inject = 0;
+    int region_assemble_generic = 0;  // test option: every tile of region_assemble takes the generic path
+};
+
 struct chicdiff_hip_ctx {
     int device = 0;
     bool no_persistent_trend = false;  // set after a grid-barrier timeout (see fit_dev_impl)
-    // tuning / test options (chicdiff_hip_set_option); the defaults are what the benchmarks run
-    int opt_chunk = 0;  // line search: rows per dequeue (0 = automatic)
-    int opt_prio = 0;   // line search: s_setprio by search age (0 = off)
-    int opt_fillers = -1, opt_filler_stop = -1;  // gene-wise line search: filler waves (-1 = launch_disp's rule), the share at which they stop claiming (-1 = default)
-    int opt_classes_a = 0;  // gene-wise line search: classes of the schedule dealt out statically (0 = default)
-    int opt_spread = 1, opt_min_waves = 0, opt_select_rounds = 0, opt_trend_multilaunch = 0, opt_schedule = 1, opt_deal = 0;
-    int opt_trend_gather = 1;  // sharded fits: gather the rows of the trend on every rank (two collectives) instead of one all-reduce per IRLS pass
+    // tuning / test options (chicdiff_hip_set_option, the only writer): `tune` is what make_opts starts from, its tuning tail
+    // (spread .. trend_blocks) is the storage of those options
+    Opts tune{};
+    HostOpts host;
     char *tg_buf = nullptr;    // ... the gathered rows (grow-only)
     size_t tg_bytes = 0;
     double shard_n[kSelMaxWorld] = {0};  // rows of every rank's shard, exchanged with the argument verdicts at the start of a sharded call
@@ -59,29 +77,15 @@ struct chicdiff_hip_ctx {
     double *tg_x = nullptr, *tg_y = nullptr, *tg_resid = nullptr;
     int32_t *tg_flags = nullptr;
     int32_t *h_flag = nullptr;  // pinned: sel_overflow of the size-factor select (read with the call's last synchronisation)
-    int opt_no_local_substitute = 0;  // 1: a failed parametric trend is reported (CHICDIFF_ST_TREND_FAILED), not replaced by the local fit
-    // test hook (option "fault_inject", one-shot bits, consumed by the next call that reaches the step): 1 = this rank's fit reports a
-    // select candidate-list overflow, 2 = this rank's persistent trend kernel reports a grid-barrier timeout, 4 = this rank's
-    // size-factor select reports an overflow.  Each verdict is all-reduced, so every rank of a sharded fit must re-enter together.
-    int opt_trend_blocks = 0;  // persistent trend kernel: cap on its workgroups (0 = one per CU)
     // set by an entry point for the fit it is about to make (d_nf = d_nf_tmp): the offsets are formed from FullMean inside the fit's
     // first kernel instead of by a launch of their own (common.h FusedOffsets); cleared when the fit returns
     FusedOffsets fuse;
-    int opt_fuse_offsets = 1;  // (option "fuse_offsets": 0 = offsets always as a launch of their own, 2 = always inside prep: the bit-identity test)
-    // bench hook (option "bench_fake_world", a 1-rank communicator only): the trend's rows are gathered as if N ranks had each sent
-    // this rank's block — the single-launch trend + MAD kernel then runs on N x n rows, which is what EVERY rank of an N-GPU fit
-    // does (bench.py's rehearsal of a rank's step at its share of the rows; the coefficients are those of the n rows up to rounding)
-    int opt_fake_world = 0;
-    int opt_mad_in_kernel = 1; // the persistent trend kernel also takes the median / MAD of the residuals (0: separate launches, as round 3)
-    int opt_fault = 0;
-    int opt_assemble_generic = 0;  // test option "region_assemble_generic": every tile of region_assemble takes the generic path
     int refits = 0;               // refits the last call went through (select overflow / barrier timeout / local substitute), for the tests
     bool sf_overflow_seen = false;  // fit_dev_impl: some rank's size-factor select (run by the caller just before) overflowed
     int32_t *d_carry = nullptr;   // device word that survives the fit's clearing of its scalars: sel_overflow of the size-factor select
     // host-buffer entry point: device arena + pinned staging, both grow-only (no allocation per call once warm)
     char *io_dev = nullptr, *io_pin = nullptr;
     size_t io_dev_bytes = 0, io_pin_bytes = 0;
-    int opt_host_threads = 12;              // host threads that move caller buffers to / from the pinned staging area
     ChinputCols *chin = nullptr;            // columns of the .chinput file read last (chicdiff_hip_chinput_read)
     // host-buffer entry point: columns that are final once the MAP dispersions exist leave for the host on a second
     // stream while the Wald stage runs (set for the duration of one chicdiff_hip_nbglm_fit call)
@@ -94,7 +98,6 @@ struct chicdiff_hip_ctx {
     hipStream_t copy_stream = nullptr;      // also the second stream of the independent-filtering sorts
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::vector<chicdiff_hip_ctx *> lanes;  // theta grid: child contexts (own stream + workspace), one per concurrent fit
-    int opt_grid_lanes = 5;                 // theta grid: fits in flight at once (1 = one after the other)
     int cu_count = 0;  // compute units of the device (the persistent trend kernel needs one resident workgroup per CU it launches)
     hipStream_t own_stream = nullptr, stream = nullptr;
     chicdiff_allreduce_fn allreduce = nullptr;
@@ -136,7 +139,7 @@ struct chicdiff_hip_ctx {
 };
 
 static char g_create_err[512];
-constexpr int64_t kFuseOffsetsMaxRows = 1 << 18;  // fits up to this many rows form their offsets inside prep (see wald_test_dev)
+constexpr int64_t kFuseOffsetsMaxRows = 1 << 18;  // fits up to this many rows form their offsets inside prep (see form_offsets)
 
 // simulated residual densities + loess operator of one d.f. (prior_mc.h): constants, built once per process
 static const PmcTable &pmc_table(int df) {
@@ -183,38 +186,52 @@ void chicdiff_hip_default_opts(chicdiff_nbglm_opts *o) {
     o->_pad = 0;
 }
 
+// Every option of chicdiff_hip_set_option, in the order of the list in include/chicdiff_hip.h (tests/test_cabi.py compares the
+// two): where its value is stored (a field of ctx->tune or of ctx->host), the range it accepts, and the values inside that
+// range it refuses (no_lo .. no_hi; none where no_lo > no_hi).  Retiring an option is deleting its line here and there.
+struct OptionDef {
+    const char *name;
+    int32_t Opts::*tune;
+    int HostOpts::*host;
+    int64_t lo, hi, no_lo, no_hi;
+};
+static const OptionDef kOptions[] = {
+    {"line_search_spread", &Opts::spread, nullptr, 0, 3, 1, 0},  // 2: samples across lanes without the lean tick of the launch's end (bit-identity tests)
+    {"line_search_min_waves", &Opts::min_waves, nullptr, 0, 4, 1, 1},  // 0 (by rule) or 2 .. 4
+    {"line_search_chunk", &Opts::chunk, nullptr, 0, 64, 1, 7},         // 0 (automatic) or 8 .. 64
+    {"line_search_prio", &Opts::prio, nullptr, 0, 100, 1, 0},
+    {"line_search_schedule", &Opts::schedule, nullptr, 0, 4, 2, 2},    // 0, 1, kSchedSix, kSchedMinDispLast; 2 is not a mode
+    {"line_search_deal", &Opts::deal, nullptr, 0, 64, 1, 0},
+    {"line_search_classes_a", &Opts::classes_a, nullptr, 0, 6, 1, 0},
+    {"line_search_fillers", &Opts::fillers, nullptr, -1, 1, 1, 0},
+    {"line_search_filler_stop", &Opts::filler_stop, nullptr, -1, 100, 1, 0},
+    {"theta_grid_concurrency", nullptr, &HostOpts::theta_grid_concurrency, 1, 16, 1, 0},
+    {"host_copy_threads", nullptr, &HostOpts::host_copy_threads, 1, 64, 1, 0},
+    {"select_all_rounds", nullptr, &HostOpts::select_all_rounds, 0, 1, 1, 0},
+    {"trend_one_launch_per_pass", nullptr, &HostOpts::trend_one_launch_per_pass, 0, 1, 1, 0},
+    {"sharded_trend_gather", nullptr, &HostOpts::sharded_trend_gather, 0, 1, 1, 0},
+    {"trend_persistent_blocks", &Opts::trend_blocks, nullptr, 0, 256, 1, 0},
+    {"trend_mad_in_kernel", nullptr, &HostOpts::trend_mad_in_kernel, 0, 1, 1, 0},
+    {"fuse_offsets", nullptr, &HostOpts::fuse_offsets, 0, 2, 1, 0},
+    {"region_assemble_generic", nullptr, &HostOpts::region_assemble_generic, 0, 1, 1, 0},
+    {"fault_inject", nullptr, &HostOpts::fault_inject, 0, 7, 1, 0},
+    {"bench_fake_world", nullptr, &HostOpts::bench_fake_world, 0, kGatherMaxWorld, 1, 0},
+    {"local_trend_substitute", nullptr, &HostOpts::local_trend_substitute, 0, 1, 1, 0},
+};
+
 int chicdiff_hip_set_option(chicdiff_hip_ctx *c, const char *name, int64_t value) {
     if (!c || !name) return CHICDIFF_E_INVALID;
-    const std::string k(name);
-    if (k == "line_search_spread" && value >= 0 && value <= 3) c->opt_spread = (int)value;  // 2: samples across lanes without the lean tick of the launch's end (bit-identity tests)
-    else if (k == "line_search_min_waves" && (value == 0 || (value >= 2 && value <= 4))) c->opt_min_waves = (int)value;
-    else if (k == "line_search_prio" && value >= 0 && value <= 100) c->opt_prio = (int)value;
-    else if (k == "line_search_fillers" && value >= -1 && value <= 1) c->opt_fillers = (int)value;
-    else if (k == "line_search_filler_stop" && value >= -1 && value <= 100) c->opt_filler_stop = (int)value;
-    else if (k == "line_search_chunk" && (value == 0 || (value >= 8 && value <= 64))) c->opt_chunk = (int)value;
-    else if (k == "line_search_classes_a" && value >= 0 && value <= 6) c->opt_classes_a = (int)value;
-    else if (k == "line_search_schedule" && value >= 0 && value <= 4 && value != 2) c->opt_schedule = (int)value;  // (2 is what the theta grid's concurrent fits get)
-    else if (k == "line_search_deal" && value >= 0 && value <= 64) c->opt_deal = (int)value;
-    else if (k == "local_trend_substitute" && (value == 0 || value == 1)) c->opt_no_local_substitute = value ? 0 : 1;
-    else if (k == "sharded_trend_gather" && (value == 0 || value == 1)) c->opt_trend_gather = (int)value;
-    else if (k == "theta_grid_concurrency" && value >= 1 && value <= 16) c->opt_grid_lanes = (int)value;
-    else if (k == "host_copy_threads" && value >= 1 && value <= 64) c->opt_host_threads = (int)value;
-    else if (k == "select_all_rounds" && (value == 0 || value == 1)) c->opt_select_rounds = (int)value;
-    else if (k == "trend_one_launch_per_pass" && (value == 0 || value == 1)) c->opt_trend_multilaunch = (int)value;
-    else if (k == "fault_inject" && value >= 0 && value <= 7) c->opt_fault = (int)value;
-    else if (k == "trend_persistent_blocks" && value >= 0 && value <= 256) c->opt_trend_blocks = (int)value;
-    else if (k == "fuse_offsets" && value >= 0 && value <= 2) c->opt_fuse_offsets = (int)value;
-    else if (k == "bench_fake_world" && value >= 0 && value <= kGatherMaxWorld) {
+    for (const OptionDef &d : kOptions) {
+        if (strcmp(name, d.name) != 0 || value < d.lo || value > d.hi || (value >= d.no_lo && value <= d.no_hi)) continue;
         // a rehearsal hook of bench.py, not an option of the product: refused unless the process says it is that rehearsal
         // (it makes a 1-rank fit's trend run on N copies of its rows — a fit nobody asked for)
-        if (value > 1 && !getenv("CHICDIFF_BENCH_FAKE_WORLD"))
+        if (d.host == &HostOpts::bench_fake_world && value > 1 && !getenv("CHICDIFF_BENCH_FAKE_WORLD"))
             return fail(c, CHICDIFF_E_INVALID, "set_option: bench_fake_world is a rehearsal hook of bench.py (CHICDIFF_BENCH_FAKE_WORLD unset)");
-        c->opt_fake_world = (int)value;
+        if (d.tune) c->tune.*d.tune = (int32_t)value;
+        else c->host.*d.host = (int)value;
+        return CHICDIFF_OK;
     }
-    else if (k == "trend_mad_in_kernel" && (value == 0 || value == 1)) c->opt_mad_in_kernel = (int)value;
-    else if (k == "region_assemble_generic" && (value == 0 || value == 1)) c->opt_assemble_generic = (int)value;
-    else return fail(c, CHICDIFF_E_INVALID, "set_option: unknown option or value (%s = %lld)", name, (long long)value);
-    return CHICDIFF_OK;
+    return fail(c, CHICDIFF_E_INVALID, "set_option: unknown option or value (%s = %lld)", name, (long long)value);
 }
 
 int chicdiff_hip_create(chicdiff_hip_ctx **out, int32_t device) {
@@ -610,6 +627,7 @@ struct HipBackend {
     SelArgs sa;  // key source of the running select
     int err = 0;
     bool local = false;  // a sharded fit whose rows are all on this rank for this step (MAD over the gathered trend rows): single-rank path
+    bool all_rounds = false;  // this pass of the call takes every histogram round (option "select_all_rounds", or the retry after an overflow)
     bool sharded() const { return c->allreduce && !local; }
     int world() const { return sharded() ? (c->world > 1 ? c->world : 2) : 1; }  // callback set => sharded protocol
     int allreduce(double *buf, int64_t n) { return sharded() ? do_allreduce(c, buf, n) : 0; }
@@ -642,7 +660,7 @@ struct HipBackend {
         launch_sel_step(sa, c->w, c->stream);
     }
     bool sel_shortcut(const SelSpec &) {
-        if (sharded() || c->opt_select_rounds) return false;  // sharded: candidates live on other ranks too
+        if (sharded() || all_rounds) return false;  // sharded: candidates live on other ranks too
         Scope t(c, "select_shortcut");
         sa.shift = 40;
         launch_sel_shortcut(sa, c->w, c->stream);
@@ -655,7 +673,7 @@ struct HipBackend {
     }
     // sharded shortcut
     int world_size() const { return c->world; }
-    bool sel_can_gather() const { return c->world <= kSelMaxWorld && !c->opt_select_rounds; }
+    bool sel_can_gather() const { return c->world <= kSelMaxWorld && !all_rounds; }
     double *sel_counts() { return c->w.selcnt; }
     void sel_keep_local_hist(const SelSpec &) { launch_sel_keep_local(sa, c->w, c->stream); }
     void sel_gather_counts(const SelSpec &) { launch_sel_gather_counts(sa, c->w, c->world, c->rank, c->stream); }
@@ -671,9 +689,10 @@ struct HipBackend {
 };
 
 // exact medians by radix select; results land in w.sc (see sel_finish_kernel)
-static int run_select(chicdiff_hip_ctx *c, SelArgs a, bool local = false) {
+static int run_select(chicdiff_hip_ctx *c, SelArgs a, bool all_rounds, bool local = false) {
     HipBackend be{c, FitDims{}, Opts{}, a};
     be.local = local;
+    be.all_rounds = all_rounds;
     SelSpec spec{a.mode, a.ncol};
     const int rc = drive_select(be, spec);
     if (rc) return c->err[0] ? CHICDIFF_E_COMM : fail(c, CHICDIFF_E_COMM, "select: all-reduce failed");
@@ -744,23 +763,13 @@ static int shard_consensus(chicdiff_hip_ctx *c, int local_rc, int64_t n = 0) {
 static Opts make_opts(const chicdiff_hip_ctx *c, const chicdiff_nbglm_opts *in, int S) {
     chicdiff_nbglm_opts o;
     if (in) o = *in; else chicdiff_hip_default_opts(&o);
-    Opts r;
+    Opts r = c->tune;
     r.minDisp = o.minDisp; r.dispTol = o.dispTol; r.kappa0 = o.kappa0; r.betaTol = o.betaTol; r.minmu = o.minmu;
     r.outlierSD = o.outlierSD; r.dispPriorVarIn = o.dispPriorVar; r.maxit = o.maxit; r.betaMaxit = o.betaMaxit;
     r.maxDisp = S > 10 ? (double)S : 10.0;
     r.trendIn[0] = o.trendCoef[0];
     r.trendIn[1] = o.trendCoef[1];
     r.fit_type = o.fitType;
-    r.spread = c->opt_spread;
-    r.min_waves = c->opt_min_waves;
-    r.prio = c->opt_prio;
-    r.fillers = c->opt_fillers;
-    r.filler_stop = c->opt_filler_stop;
-    r.schedule = c->opt_schedule;
-    r.deal = c->opt_deal;
-    r.chunk = c->opt_chunk;
-    r.classes_a = c->opt_classes_a;
-    r.trend_blocks = c->opt_trend_blocks;
     return r;
 }
 
@@ -886,7 +895,7 @@ static int gathered_trend(chicdiff_hip_ctx *c, FitDims d, const Opts &o) {
     hipStream_t st = c->stream;
     FitWork &w = c->w;
     const int real_world = c->world > 0 ? c->world : 1, rank = c->rank;
-    const int fake = (real_world == 1 && c->opt_fake_world > 1 && c->allgather != nullptr) ? c->opt_fake_world : 0;  // bench hook, see opt_fake_world
+    const int fake = (real_world == 1 && c->host.bench_fake_world > 1 && c->allgather != nullptr) ? c->host.bench_fake_world : 0;  // bench hook, see HostOpts
     const int world = fake ? fake : real_world;
     std::vector<double> cnt((size_t)world, 0.0);
     int rc;
@@ -958,7 +967,7 @@ static int gathered_trend(chicdiff_hip_ctx *c, FitDims d, const Opts &o) {
     wg.dispGene = yg;
     wg.allZero = flags;  // all zero: a row that does not take part carries y = NaN
     wg.resid = c->tg_resid;
-    launch_trend_persistent(dg, wg, o, st, c->opt_mad_in_kernel != 0);
+    launch_trend_persistent(dg, wg, o, st, c->host.trend_mad_in_kernel != 0);
     return CHICDIFF_OK;
 }
 
@@ -985,11 +994,38 @@ struct WorkRedirect {
     ~WorkRedirect() { c->w = saved; }
 };
 
-static int fit_dev_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, const double *d_nf, FitDims d, Opts o,
-                        const chicdiff_nbglm_out *d_out, chicdiff_nbglm_scalars *scalars) {
+// the prior variance is matched by simulation (prior_mc.h) instead of taken in closed form
+static bool prior_by_simulation(const FitDims &d, const Opts &o) { return !(o.dispPriorVarIn == o.dispPriorVarIn) && d.S - d.p <= 3 && d.S > d.p; }
+
+// residual d.f. <= 3: DESeq2 matches the prior variance by simulation (prior_mc.h).  The 200 x 40 simulated densities are
+// constants (built once per process and d.f.); the matching itself runs on the device, on the histogram of the residuals in wm.resid
+static int prior_mc(chicdiff_hip_ctx *c, FitDims d, FitDims dm, const FitWork &wm, bool mad_local) {
+    Scope t(c, "prior_mc");
+    double *d_hist = sums_of(c->w) + 32;
+    launch_resid_hist(dm, wm, d_hist, c->stream);
+    if (!mad_local)
+        if (int rc = do_allreduce(c, d_hist, kPmcBins)) return rc;
+    const int df = d.S - d.p;
+    if (!c->d_pmc[df]) {  // built once per process, uploaded once per context
+        HIPCHK(c, hipMalloc((void **)&c->d_pmc[df], sizeof(PmcTable)));
+        HIPCHK(c, hipMemcpy(c->d_pmc[df], &pmc_table(df), sizeof(PmcTable), hipMemcpyHostToDevice));
+    }
+    launch_prior_mc(d, c->w, d_hist, c->d_pmc[df], c->stream);
+    return CHICDIFF_OK;
+}
+
+// the fit's scalars (sums and size factors included) to c->h_sc; blocks
+static int read_scalars(chicdiff_hip_ctx *c) {
+    HIPCHK(c, hipMemcpyAsync(c->h_sc, c->w.sc, sizeof(FitScalars), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CHICDIFF_OK;
+}
+
+// one pass of a fit, from the counts to the scalars on the host (c->h_sc); fit_dev_impl reads the verdicts and repeats it if need be
+static int fit_pass(chicdiff_hip_ctx *c, const int32_t *d_counts, const double *d_nf, FitDims d, const Opts &o,
+                    const chicdiff_nbglm_out *d_out, bool all_rounds) {
     int rc;
     hipStream_t st = c->stream;
-    WorkRedirect redirect(c, d_out);
     FitWork &w = c->w;
     c->tg_total = 0;
     // the scalars, the queue heads and the barrier counters sit next to each other in the workspace: one fill
@@ -1051,7 +1087,7 @@ static int fit_dev_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, const doub
         HIPCHK(c, hipMemcpyAsync(w.sc->coefs, coefs, sizeof coefs, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipStreamSynchronize(st));
     } else if (o.fit_type == 2) {
-        // fitType = "local": on request, or — from the re-entry at the end of this function — DESeq2's own substitute for
+        // fitType = "local": on request, or — on fit_dev_impl's second pass — DESeq2's own substitute for
         // a parametric fit that failed ("a local regression fit was automatically substituted")
         Scope t(c, "trend_fit");
         launch_trend_init(d, w, o, st);
@@ -1062,15 +1098,15 @@ static int fit_dev_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, const doub
             HIPCHK(c, hipStreamSynchronize(st));
         } else if (rc)
             return rc;
-    } else if (!c->allreduce && !c->no_persistent_trend && c->cu_count >= trend_persistent_blocks() && !c->opt_trend_multilaunch) {
+    } else if (!c->allreduce && !c->no_persistent_trend && c->cu_count >= trend_persistent_blocks() && !c->host.trend_one_launch_per_pass) {
         Scope t(c, "trend_fit");  // single rank: one persistent launch (LDS-resident rows, grid barrier per IRLS pass)
-        launch_trend_persistent(d, w, o, st, c->opt_mad_in_kernel != 0);  // no host round trip: `failed` comes back with the final scalars
-        mad_in_kernel = c->opt_mad_in_kernel != 0;
-    } else if (c->allreduce && c->opt_trend_gather && !c->no_persistent_trend && c->cu_count >= trend_persistent_blocks() &&
-               !c->opt_trend_multilaunch) {
+        launch_trend_persistent(d, w, o, st, c->host.trend_mad_in_kernel != 0);  // no host round trip: `failed` comes back with the final scalars
+        mad_in_kernel = c->host.trend_mad_in_kernel != 0;
+    } else if (c->allreduce && c->host.sharded_trend_gather && !c->no_persistent_trend && c->cu_count >= trend_persistent_blocks() &&
+               !c->host.trend_one_launch_per_pass) {
         Scope t(c, "trend_fit");
         if ((rc = gathered_trend(c, d, o))) return rc;
-        mad_in_kernel = c->opt_mad_in_kernel != 0;
+        mad_in_kernel = c->host.trend_mad_in_kernel != 0;
     } else {
         Scope t(c, "trend_fit");
         HipBackend be{c, d, o, SelArgs{}};
@@ -1079,12 +1115,10 @@ static int fit_dev_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, const doub
         if (trc == -1) return CHICDIFF_E_COMM;
         if (trc == -2) return fail(c, CHICDIFF_E_NUMERIC, "trend state machine did not finish");
     }
-    if (c->opt_fault & 2) {  // test hook: this rank's trend kernel "lost its grid barrier"
-        c->opt_fault &= ~2;
+    if (c->host.fault_inject & 2) {  // test hook: this rank's trend kernel "lost its grid barrier"
+        c->host.fault_inject &= ~2;
         launch_poke(&w.sc->failed, 3, st);
     }
-    int status = 0;
-    const bool prior_by_simulation = !(o.dispPriorVarIn == o.dispPriorVarIn) && d.S - d.p <= 3 && d.S > d.p;
     // MAD of the log residuals.  A sharded fit that gathered the trend's rows has every rank's (baseMean, dispGeneEst) on this
     // rank already: the residuals of ALL rows are formed here and the two medians (and the residual histogram of the d.f. <= 3
     // prior) are taken locally, single-rank path — no collective at all instead of eight (nine) latency-bound ones, and the
@@ -1100,48 +1134,23 @@ static int fit_dev_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, const doub
         wm.resid = c->tg_resid;
     }
     if (mad_in_kernel) {
-        if (prior_by_simulation) {  // the residuals are in wm.resid: their histogram, then the simulation-matched prior variance
-            Scope t(c, "prior_mc");
-            double *d_hist = sums_of(w) + 32;
-            launch_resid_hist(dm, wm, d_hist, st);
-            const int df = d.S - d.p;
-            if (!c->d_pmc[df]) {  // built once per process, uploaded once per context
-                HIPCHK(c, hipMalloc((void **)&c->d_pmc[df], sizeof(PmcTable)));
-                HIPCHK(c, hipMemcpy(c->d_pmc[df], &pmc_table(df), sizeof(PmcTable), hipMemcpyHostToDevice));
-            }
-            launch_prior_mc(d, w, d_hist, c->d_pmc[df], st);
-        }
+        if (prior_by_simulation(d, o) && (rc = prior_mc(c, d, dm, wm, mad_local))) return rc;  // (the residuals are in wm.resid)
     } else {
         launch_dispfit_resid(dm, wm, o, st);
         SelArgs sa{};
         sa.n = dm.n;
         sa.ncol = 1;
         sa.resid = wm.resid;
-        {
-            Scope t(c, "mad_select");
-            sa.mode = SEL_RESID;
-            if ((rc = run_select(c, sa, mad_local))) return rc;
-            sa.mode = SEL_ABSDEV;
-            if ((rc = run_select(c, sa, mad_local))) return rc;
-            if (prior_by_simulation) {
-                // residual d.f. <= 3: DESeq2 matches the prior variance by simulation (prior_mc.h).  The 200 x 40 simulated
-                // densities are constants (built once per process and d.f.); the matching itself runs on the device
-                double *d_hist = sums_of(w) + 32;
-                launch_resid_hist(dm, wm, d_hist, st);
-                if (!mad_local && (rc = do_allreduce(c, d_hist, kPmcBins))) return rc;
-                const int df = d.S - d.p;
-                if (!c->d_pmc[df]) {  // built once per process, uploaded once per context
-                    HIPCHK(c, hipMalloc((void **)&c->d_pmc[df], sizeof(PmcTable)));
-                    HIPCHK(c, hipMemcpy(c->d_pmc[df], &pmc_table(df), sizeof(PmcTable), hipMemcpyHostToDevice));
-                }
-                launch_prior_mc(d, w, d_hist, c->d_pmc[df], st);
-            } else {
-                launch_prior_var(d, w, o, st);
-            }
-        }
+        Scope t(c, "mad_select");
+        sa.mode = SEL_RESID;
+        if ((rc = run_select(c, sa, all_rounds, mad_local))) return rc;
+        sa.mode = SEL_ABSDEV;
+        if ((rc = run_select(c, sa, all_rounds, mad_local))) return rc;
+        if (!prior_by_simulation(d, o)) launch_prior_var(d, w, o, st);
+        else if ((rc = prior_mc(c, d, dm, wm, mad_local))) return rc;
     }
-    if (c->opt_fault & 1) {  // test hook: this rank's select "could not fit its candidate list"
-        c->opt_fault &= ~1;
+    if (c->host.fault_inject & 1) {  // test hook: this rank's select "could not fit its candidate list"
+        c->host.fault_inject &= ~1;
         launch_poke(&w.sc->sel_overflow, 1, st);
     }
     {
@@ -1179,45 +1188,48 @@ static int fit_dev_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, const doub
     // a select's candidate list overflowed in this fit, ... in the size-factor select the caller ran before it
     if ((rc = do_allreduce(c, w.sc->final_sums, 7))) return rc;
     // one read brings the scalars, the sums and the size factors back (the per-row columns the caller asked for were written in place)
-    HIPCHK(c, hipMemcpyAsync(c->h_sc, w.sc, sizeof(FitScalars), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    if ((rc = read_scalars(c))) return rc;
     HIPCHK(c, hipGetLastError());
+    return CHICDIFF_OK;
+}
+
+// A fit: fit_pass, repeated while the verdicts of a pass ask for it.  all_rounds: the selects take every histogram round from the
+// first pass on (option "select_all_rounds", or the caller's own retry after an overflow of the size-factor select).
+static int fit_dev_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, const double *d_nf, FitDims d, Opts o,
+                        const chicdiff_nbglm_out *d_out, chicdiff_nbglm_scalars *scalars, bool all_rounds) {
+    WorkRedirect redirect(c, d_out);
     const double *hs = c->h_sc->final_sums;
-    // hs[4] is all-reduced like the other sums: a negative / NA count on ANY rank has entered everybody's size factors, trend and
-    // prior, so every rank refuses the fit together (and none goes on to the retry below, whose collectives the others would miss)
-    if (hs[4] > 0)
-        return fail(c, CHICDIFF_E_INVALID, c->h_sc->neg_counts ? "counts contain a negative value or NA_integer_"
-                                                               : "counts contain a negative value or NA_integer_ (on another rank of the sharded fit)");
-    // The verdicts below are sums over the ranks (hs[3..6]): whatever ONE rank saw, every rank takes the same branch and re-enters
-    // the fit together — none is left waiting in a collective its peers never issue.
-    c->sf_overflow_seen = hs[6] > 0;  // the caller (wald_test_dev) repeats size factors + fit with every histogram round
-    if (c->sf_overflow_seen && !c->opt_select_rounds) return CHICDIFF_OK;  // (results of this pass are discarded there)
-    if (hs[5] > 0 && !c->opt_select_rounds) {  // a sharded select's candidate list did not fit: every histogram round instead
-        c->opt_select_rounds = 1;
+    for (;;) {
+        if (int rc = fit_pass(c, d_counts, d_nf, d, o, d_out, all_rounds)) return rc;
+        // hs[4] is all-reduced like the other sums: a negative / NA count on ANY rank has entered everybody's size factors, trend and
+        // prior, so every rank refuses the fit together (and none goes on to a retry below, whose collectives the others would miss)
+        if (hs[4] > 0)
+            return fail(c, CHICDIFF_E_INVALID, c->h_sc->neg_counts ? "counts contain a negative value or NA_integer_"
+                                                                   : "counts contain a negative value or NA_integer_ (on another rank of the sharded fit)");
+        // The verdicts below are sums over the ranks (hs[3..6]): whatever ONE rank saw, every rank takes the same branch and repeats
+        // the pass together — none is left waiting in a collective its peers never issue.
+        c->sf_overflow_seen = hs[6] > 0;  // the caller (wald_test_dev) repeats size factors + fit with every histogram round
+        if (c->sf_overflow_seen && !all_rounds) return CHICDIFF_OK;  // (results of this pass are discarded there)
+        if (hs[5] > 0 && !all_rounds) {
+            all_rounds = true;  // a sharded select's candidate list did not fit: every histogram round instead
+        } else if (c->h_sc->failed == 3 || hs[3] > 0) {
+            // the persistent trend kernel's workgroups were not all resident within the barrier's patience (a GPU shared
+            // with other work): fit again with one launch per IRLS pass, and stay with that for this context
+            if (c->no_persistent_trend) return fail(c, CHICDIFF_E_HIP, "trend fit: grid barrier timed out");
+            c->no_persistent_trend = true;
+        } else if (c->h_sc->failed && o.fit_type == 0 && !(o.trendIn[0] == o.trendIn[0]) && c->host.local_trend_substitute) {
+            // estimateDispersionsFit: the parametric fit failed -> fitType <- "local", and the fit is done again from the trend on
+            // (everything before it is recomputed too: a rare path, kept simple)
+            o.fit_type = 2;
+        } else
+            break;
         c->refits++;
-        rc = fit_dev_impl(c, d_counts, d_nf, d, o, d_out, scalars);
-        c->opt_select_rounds = 0;  // (it was 0: checked above)
-        return rc;
     }
-    if (c->h_sc->failed == 3 || hs[3] > 0) {
-        // the persistent trend kernel's workgroups were not all resident within the barrier's patience (a GPU shared
-        // with other work): fit again with one launch per IRLS pass, and stay with that for this context
-        if (c->no_persistent_trend) return fail(c, CHICDIFF_E_HIP, "trend fit: grid barrier timed out");
-        c->no_persistent_trend = true;
-        c->refits++;
-        return fit_dev_impl(c, d_counts, d_nf, d, o, d_out, scalars);
-    }
-    if (c->h_sc->failed && o.fit_type == 0 && !(o.trendIn[0] == o.trendIn[0]) && !c->opt_no_local_substitute) {
-        // estimateDispersionsFit: the parametric fit failed -> fitType <- "local", and the fit is done again from the trend on
-        // (everything before it is recomputed too: a rare path, kept simple)
-        o.fit_type = 2;
-        c->refits++;
-        return fit_dev_impl(c, d_counts, d_nf, d, o, d_out, scalars);
-    }
-    if (c->h_sc->failed) status |= CHICDIFF_ST_TREND_FAILED;
-    if (c->h_sc->trend_local) status |= CHICDIFF_ST_TREND_LOCAL;
     if (scalars) {
         const FitScalars *s = c->h_sc;
+        int status = 0;
+        if (s->failed) status |= CHICDIFF_ST_TREND_FAILED;
+        if (s->trend_local) status |= CHICDIFF_ST_TREND_LOCAL;
         scalars->trendCoef[0] = s->coefs[0];
         scalars->trendCoef[1] = s->coefs[1];
         scalars->varLogDispEsts = s->varLogDispEsts;
@@ -1227,10 +1239,36 @@ static int fit_dev_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, const doub
         scalars->trendOuterIter = s->outer_it;
         if (hs[2] > 0) status |= CHICDIFF_ST_ALLZERO_ROWS;
         if (hs[1] > 0) status |= CHICDIFF_ST_BETA_NONCONV;
-        if (prior_by_simulation) status |= CHICDIFF_ST_PRIORVAR_MC;
+        if (prior_by_simulation(d, o)) status |= CHICDIFF_ST_PRIORVAR_MC;
         scalars->status = status;
     }
     return CHICDIFF_OK;
+}
+
+// what a fit / size-factor / Wald-test call starts with: the ranks' verdicts on their arguments (rc: this rank's), the workspace
+static int begin_call(chicdiff_hip_ctx *c, int rc, int64_t n, int32_t S) {
+    timing_reset(c);  // (before the verdicts' collective: it is one of the call's)
+    if ((rc = shard_consensus(c, rc, n))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = ensure_workspace(c, n, S))) return rc;
+    c->refits = 0;
+    return CHICDIFF_OK;
+}
+
+// The offsets of the fit that c is about to make on c->d_nf_tmp: formed from FullMean inside the fit's first kernel (c->fuse; the
+// caller clears it when the fit returns) where a launch is worth more than the arithmetic, else by a launch of their own.  Measured
+// (round 5), offsets + prep against the fused prep: 18.5 + 28 -> 47 us at 250 k x 8 (and one launch, ~5 us + its gap, less), 30 + 40 ->
+// 76 at 500 k, 67 + 130 -> 291 at 2 M (the fused kernel carries 2 S logarithms per row at the four waves per SIMD its LDS tiles allow)
+static void form_offsets(chicdiff_hip_ctx *c, const double *d_fullMean, int64_t n, int32_t S, double theta, int mix) {
+    if (d_fullMean && S <= 16 && c->host.fuse_offsets && (c->host.fuse_offsets == 2 || n <= kFuseOffsetsMaxRows)) {
+        c->fuse.fm = d_fullMean;
+        c->fuse.sf = c->d_sf;
+        c->fuse.theta = theta;
+        c->fuse.mix = mix;
+    } else {
+        Scope t(c, "offsets");
+        launch_offsets(d_fullMean, c->d_sf, n, S, theta, mix, c->d_nf_tmp, c->stream);
+    }
 }
 
 extern "C" {
@@ -1242,13 +1280,9 @@ int chicdiff_hip_nbglm_fit_dev(chicdiff_hip_ctx *c, const int32_t *d_counts, con
     FitDims d;
     int rc = (!d_counts || !d_nf) ? fail(c, CHICDIFF_E_INVALID, "counts / nf pointer is NULL") : check_counts_group(c, n, S, group, d);
     if (!rc) rc = check_opts(c, opts);
-    timing_reset(c);  // (before the verdicts' collective: it is one of the call's)
-    if ((rc = shard_consensus(c, rc, n))) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = ensure_workspace(c, n, S))) return rc;
-    c->refits = 0;
+    if ((rc = begin_call(c, rc, n, S))) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_carry, 0, sizeof(int32_t), c->stream));  // no size-factor select belongs to this call
-    rc = fit_dev_impl(c, d_counts, d_nf, d, make_opts(c, opts, S), d_out, scalars);
+    rc = fit_dev_impl(c, d_counts, d_nf, d, make_opts(c, opts, S), d_out, scalars, c->host.select_all_rounds != 0);
     timing_collect(c);
     return rc;
 }
@@ -1312,7 +1346,7 @@ int chicdiff_hip_nbglm_fit(chicdiff_hip_ctx *c, const int32_t *counts, const dou
         pieces.push_back({(const char *)counts + off, c->io_pin + off, (char *)d_counts + off, cb - off < slice ? cb - off : slice, true});
     for (size_t off = 0; off < fb; off += slice)
         pieces.push_back({(const char *)nf + off, c->io_pin + align256(cb) + off, (char *)d_nf + off, fb - off < slice ? fb - off : slice, false});
-    int nthreads = c->opt_host_threads;
+    int nthreads = c->host.host_copy_threads;
     if ((size_t)nthreads > pieces.size()) nthreads = (int)pieces.size();
     if (nthreads < 1) nthreads = 1;
     std::vector<int64_t> bad(nthreads, -1);
@@ -1381,7 +1415,7 @@ int chicdiff_hip_nbglm_fit(chicdiff_hip_ctx *c, const int32_t *counts, const dou
     }
     if (e == hipSuccess && !cols.empty()) {
         std::sort(cols.begin(), cols.end(), [](const Col &x, const Col &y) { return x.early > y.early; });  // those already on the host first
-        int nt = c->opt_host_threads < (int)cols.size() ? c->opt_host_threads : (int)cols.size();
+        int nt = c->host.host_copy_threads < (int)cols.size() ? c->host.host_copy_threads : (int)cols.size();
         std::vector<std::thread> th;
         for (int t = 0; t < nt; t++)
             th.emplace_back([&, t]() {
@@ -1400,7 +1434,7 @@ int chicdiff_hip_nbglm_fit(chicdiff_hip_ctx *c, const int32_t *counts, const dou
 
 // size factors -> c->d_sf (device) ; no host synchronisation.  The select's overflow verdict is left in c->d_carry (a device word
 // the fit does not clear), from where the fit's last all-reduce — or sf_overflow_consensus — makes it every rank's verdict.
-static int size_factors_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, int64_t n, int32_t S) {
+static int size_factors_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, int64_t n, int32_t S, bool all_rounds) {
     Scope t(c, "size_factors");
     // (the offsets buffer is free until the size factors exist; the same kernel clears the select's overflow flag, c->d_carry — a
     // device word the fit does not clear: the fit's last kernel carries it into the all-reduced verdicts)
@@ -1413,10 +1447,10 @@ static int size_factors_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, int64
     sa.S = S;
     sa.sf_out = c->d_sf;  // the finishing step of the select writes the size factors there
     sa.overflow_out = c->d_carry;
-    const int rc = run_select(c, sa);
+    const int rc = run_select(c, sa, all_rounds);
     if (rc) return rc;
-    if (c->opt_fault & 4) {  // test hook: this rank's size-factor select "could not fit its candidate list"
-        c->opt_fault &= ~4;
+    if (c->host.fault_inject & 4) {  // test hook: this rank's size-factor select "could not fit its candidate list"
+        c->host.fault_inject &= ~4;
         launch_poke(c->d_carry, 1, c->stream);
     }
     return CHICDIFF_OK;
@@ -1438,28 +1472,15 @@ static int sf_overflow_consensus(chicdiff_hip_ctx *c, bool *overflow) {
 int chicdiff_hip_size_factors_dev(chicdiff_hip_ctx *c, const int32_t *d_counts, int64_t n, int32_t S, double *sf_host) {
     if (!c) return CHICDIFF_E_INVALID;
     int rc = (!d_counts || !sf_host || n < 1 || S < 1 || S > kMaxS) ? fail(c, CHICDIFF_E_INVALID, "size_factors: bad arguments") : CHICDIFF_OK;
-    timing_reset(c);  // (before the verdicts' collective: it is one of the call's)
-    if ((rc = shard_consensus(c, rc, n))) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = ensure_workspace(c, n, S))) return rc;
-    c->refits = 0;
-    const int saved_rounds = c->opt_select_rounds;
-    auto body = [&]() -> int {
-        for (int attempt = 0; attempt < 2; attempt++) {
-            int r = size_factors_impl(c, d_counts, n, S);
-            if (r) return r;
-            bool overflow = false;
-            if ((r = sf_overflow_consensus(c, &overflow))) return r;
-            if (!overflow || c->opt_select_rounds) break;
-            c->opt_select_rounds = 1;  // a candidate list of the sharded select did not fit on some rank: every histogram round instead
-            c->refits++;
-        }
-        HIPCHK(c, hipMemcpyAsync(c->h_sc, c->w.sc, sizeof(FitScalars), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return CHICDIFF_OK;
-    };
-    rc = body();
-    c->opt_select_rounds = saved_rounds;  // whatever happened above, error returns included
+    if ((rc = begin_call(c, rc, n, S))) return rc;
+    bool all_rounds = c->host.select_all_rounds != 0, overflow = false;
+    for (;;) {
+        if ((rc = size_factors_impl(c, d_counts, n, S, all_rounds)) || (rc = sf_overflow_consensus(c, &overflow))) break;
+        if (!overflow || all_rounds) break;
+        all_rounds = true;  // a candidate list of the sharded select did not fit on some rank: every histogram round instead
+        c->refits++;
+    }
+    if (!rc) rc = read_scalars(c);
     timing_collect(c);
     if (rc) return rc;
     for (int j = 0; j < S; j++) {
@@ -1479,41 +1500,21 @@ int chicdiff_hip_wald_test_dev(chicdiff_hip_ctx *c, const int32_t *d_counts, con
     FitDims d;
     int rc = !d_counts ? fail(c, CHICDIFF_E_INVALID, "counts pointer is NULL") : check_counts_group(c, n, S, group, d);
     if (!rc) rc = check_opts(c, opts);
-    timing_reset(c);  // (before the verdicts' collective: it is one of the call's)
-    if ((rc = shard_consensus(c, rc, n))) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = ensure_workspace(c, n, S))) return rc;
-    c->refits = 0;
-    const int saved_rounds = c->opt_select_rounds;  // restored below whatever happens (a user's "select_all_rounds" included)
-    auto body = [&]() -> int {
-        for (int attempt = 0; attempt < 2; attempt++) {
-            int r = size_factors_impl(c, d_counts, n, S);
-            if (r) return r;
-            const int mix = theta == theta;
-            // the offsets formed inside the fit's first kernel — where a launch is worth more than the arithmetic: measured (round 5), offsets +
-            // prep against the fused prep: 18.5 + 28 -> 47 us at 250 k x 8 (and one launch, ~5 us + its gap, less), 30 + 40 -> 76 at 500 k,
-            // 67 + 130 -> 291 at 2 M (the fused kernel carries 2 S logarithms per row at the four waves per SIMD its LDS tiles allow)
-            if (d_fullMean && S <= 16 && c->opt_fuse_offsets && (c->opt_fuse_offsets == 2 || n <= kFuseOffsetsMaxRows)) {
-                c->fuse.fm = d_fullMean;
-                c->fuse.sf = c->d_sf;
-                c->fuse.theta = mix ? theta : 0.0;
-                c->fuse.mix = mix;
-            } else {
-                Scope t(c, "offsets");
-                launch_offsets(d_fullMean, c->d_sf, n, S, mix ? theta : 0.0, mix, c->d_nf_tmp, c->stream);
-            }
-            r = fit_dev_impl(c, d_counts, c->d_nf_tmp, d, make_opts(c, opts, S), d_out, scalars);  // ends with a stream sync; the size factors come back with its scalars
-            c->fuse = FusedOffsets();
-            // the sharded size-factor select ran without a host look at its candidate lists: one that did not fit on ANY rank (massive
-            // ties) shows in the fit's last all-reduce, on every rank alike, and the call is repeated with every histogram round
-            if (r || !c->sf_overflow_seen || c->opt_select_rounds) return r;
-            c->opt_select_rounds = 1;
-            c->refits++;
-        }
-        return CHICDIFF_OK;
-    };
-    rc = body();
-    c->opt_select_rounds = saved_rounds;
+    if ((rc = begin_call(c, rc, n, S))) return rc;
+    const Opts o = make_opts(c, opts, S);
+    const int mix = theta == theta;
+    bool all_rounds = c->host.select_all_rounds != 0;
+    for (;;) {
+        if ((rc = size_factors_impl(c, d_counts, n, S, all_rounds))) break;
+        form_offsets(c, d_fullMean, n, S, mix ? theta : 0.0, mix);
+        rc = fit_dev_impl(c, d_counts, c->d_nf_tmp, d, o, d_out, scalars, all_rounds);  // ends with a stream sync; the size factors come back with its scalars
+        c->fuse = FusedOffsets();
+        // the sharded size-factor select ran without a host look at its candidate lists: one that did not fit on ANY rank (massive
+        // ties) shows in the fit's last all-reduce, on every rank alike, and the call is repeated with every histogram round
+        if (rc || !c->sf_overflow_seen || all_rounds) break;
+        all_rounds = true;
+        c->refits++;
+    }
     timing_collect(c);
     if (rc) return rc;
     for (int j = 0; j < S; j++) {
@@ -1586,13 +1587,14 @@ int chicdiff_hip_theta_grid_dev(chicdiff_hip_ctx *c, const int32_t *d_counts, co
     if ((rc = shard_consensus(c, rc, n))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
-    const Opts o = make_opts(c, opts, S);
+    const Opts o = make_opts(c, opts, S);  // (the parent's: the concurrent fits below run with it too)
+    const bool all_rounds = c->host.select_all_rounds != 0;
     // Single rank: the |Grid| fits are independent, so they run on child contexts (own stream + workspace), up to
-    // opt_grid_lanes at once, each driven by its own host thread: one fit's straggler tail and its latency-bound
+    // theta_grid_concurrency at once, each driven by its own host thread: one fit's straggler tail and its latency-bound
     // global steps (trend barriers, selects) overlap with the other fits' line searches.  Sharded: one after the other
     // (every rank must issue its collectives in the same order).
     const size_t ws_per_lane = sizeof(double) * (size_t)n * (26 + S) + (size_t)row_stride(S) * (size_t)n + (64u << 20);
-    int lanes = c->allreduce ? 1 : (ntheta < c->opt_grid_lanes ? ntheta : c->opt_grid_lanes);
+    int lanes = c->allreduce ? 1 : (ntheta < c->host.theta_grid_concurrency ? ntheta : c->host.theta_grid_concurrency);
     bool squeezed = false;  // the lanes' workspaces do not fit: their memory is given back before the thetas are fitted one after the other
     if (lanes > 1) {
         // the lanes' workspaces must fit what the device has free NOW (a shared GPU, the caller's own tensors, a smaller
@@ -1634,17 +1636,9 @@ int chicdiff_hip_theta_grid_dev(chicdiff_hip_ctx *c, const int32_t *d_counts, co
         HIPCHK(c, hipMemsetAsync(c->d_carry, 0, sizeof(int32_t), c->stream));  // no size-factor select belongs to this call
         HIPCHK(c, hipMemcpyAsync(c->d_sf, sf_host, sizeof(double) * S, hipMemcpyHostToDevice, c->stream));
         for (int t = 0; t < ntheta; t++) {
-            if (S <= 16 && c->opt_fuse_offsets && (c->opt_fuse_offsets == 2 || n <= kFuseOffsetsMaxRows)) {
-                c->fuse.fm = d_fullMean;
-                c->fuse.sf = c->d_sf;
-                c->fuse.theta = thetas[t];
-                c->fuse.mix = 1;
-            } else {
-                Scope s(c, "offsets");
-                launch_offsets(d_fullMean, c->d_sf, n, S, thetas[t], 1, c->d_nf_tmp, c->stream);
-            }
+            form_offsets(c, d_fullMean, n, S, thetas[t], 1);
             chicdiff_nbglm_scalars sc;
-            rc = fit_dev_impl(c, d_counts, c->d_nf_tmp, d, o, nullptr, &sc);
+            rc = fit_dev_impl(c, d_counts, c->d_nf_tmp, d, o, nullptr, &sc, all_rounds);
             c->fuse = FusedOffsets();
             if (rc) return rc;
             deviances_host[t] = sc.sumDeviance;
@@ -1659,20 +1653,8 @@ int chicdiff_hip_theta_grid_dev(chicdiff_hip_ctx *c, const int32_t *d_counts, co
     std::vector<std::thread> workers;
     for (int k = 0; k < lanes; k++) {
         chicdiff_hip_ctx *l = c->lanes[k];
-        l->opt_spread = c->opt_spread;
-        l->opt_min_waves = c->opt_min_waves;
-        l->opt_prio = c->opt_prio;
-        l->opt_fillers = c->opt_fillers;  // (schedule 2 has no boundary to give: launch_disp keeps fillers off for these fits whatever this says)
-        l->opt_filler_stop = c->opt_filler_stop;
-        l->opt_schedule = c->opt_schedule ? 2 : 0;  // concurrent fits: class order through the queue, nothing dealt out statically
-        l->opt_deal = c->opt_deal;
-        l->opt_chunk = c->opt_chunk;
-        l->opt_no_local_substitute = c->opt_no_local_substitute;
-        l->opt_trend_gather = c->opt_trend_gather;
-        l->opt_select_rounds = c->opt_select_rounds;
-        l->opt_trend_multilaunch = c->opt_trend_multilaunch;
-        l->opt_mad_in_kernel = c->opt_mad_in_kernel;
-        l->opt_trend_blocks = c->opt_trend_blocks;
+        l->host = c->host;  // the host-side options; the kernels' (Opts) are the parent's: `o` above
+        l->host.fault_inject = 0;  // (the one-shot bits are the parent's, for a call of its own)
         // a grid barrier needs its workgroups co-resident: not guaranteed beside other fits.  (Measured, round 4: the lanes' trend as
         // the single-launch kernel capped at 16 / 32 / 64 workgroups — 2 M x 8, five thetas: 2 lanes 16.5 -> 18.2 ms, 3 lanes 17.2 ->
         // 17.9, 5 lanes 16.3 ms -> 5-13 SECONDS: the kernel's workgroups wait for LDS that the other lanes' line-search workgroups
@@ -1687,16 +1669,9 @@ int chicdiff_hip_theta_grid_dev(chicdiff_hip_ctx *c, const int32_t *d_counts, co
             if (!r) r = ensure_workspace(l, n, S);
             if (!r && hipMemcpyAsync(l->d_sf, sf_host, sizeof(double) * S, hipMemcpyHostToDevice, l->stream) != hipSuccess) r = CHICDIFF_E_HIP;
             for (int t = k; t < ntheta && !r; t += lanes) {
-                if (S <= 16 && c->opt_fuse_offsets && (c->opt_fuse_offsets == 2 || n <= kFuseOffsetsMaxRows)) {
-                    l->fuse.fm = d_fullMean;
-                    l->fuse.sf = l->d_sf;
-                    l->fuse.theta = thetas[t];
-                    l->fuse.mix = 1;
-                } else {
-                    launch_offsets(d_fullMean, l->d_sf, n, S, thetas[t], 1, l->d_nf_tmp, l->stream);
-                }
+                form_offsets(l, d_fullMean, n, S, thetas[t], 1);
                 chicdiff_nbglm_scalars sc;
-                r = fit_dev_impl(l, d_counts, l->d_nf_tmp, d, o, nullptr, &sc);
+                r = fit_dev_impl(l, d_counts, l->d_nf_tmp, d, o, nullptr, &sc, all_rounds);
                 l->fuse = FusedOffsets();
                 if (!r) deviances_host[t] = sc.sumDeviance;
             }
@@ -2020,7 +1995,7 @@ extern "C" int chicdiff_hip_region_assemble_dev(chicdiff_hip_ctx *c, const int32
     if (e == hipSuccess) {
         Scope t(c, "region_assemble");
         le = launch_region_assemble(d_ru_bait, d_ru_oe, nru, d_region_ptr, n, S, d_keys, d_vals, nkeys, id_min, nid, d_midsum, d_sj, d_si,
-                                    d_tblb, d_tlb, d_T, ntblb, ntlb, d_df, d_N, d_FullMean, c->aux + df_bytes, c->opt_assemble_generic,
+                                    d_tblb, d_tlb, d_T, ntblb, ntlb, d_df, d_N, d_FullMean, c->aux + df_bytes, c->host.region_assemble_generic,
                                     c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // distfun_host may be a temporary
@@ -2075,7 +2050,7 @@ extern "C" int chicdiff_hip_chinput_read(chicdiff_hip_ctx *c, const char *path, 
     if (!c) return CHICDIFF_E_INVALID;
     if (!path || !nrows_host) return fail(c, CHICDIFF_E_INVALID, "chinput_read: bad arguments");
     if (!c->chin) c->chin = new ChinputCols();
-    const int64_t n = chinput_parse(path, nthreads > 0 ? nthreads : c->opt_host_threads, *c->chin);
+    const int64_t n = chinput_parse(path, nthreads > 0 ? nthreads : c->host.host_copy_threads, *c->chin);
     if (n < 0) return fail(c, CHICDIFF_E_INVALID, "chinput_read: %s", c->chin->error.c_str());
     *nrows_host = n;
     return CHICDIFF_OK;

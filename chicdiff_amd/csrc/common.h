@@ -89,11 +89,11 @@ struct Opts {
     double minDisp, dispTol, kappa0, betaTol, minmu, outlierSD, dispPriorVarIn, maxDisp, trendIn[2];
     int32_t maxit, betaMaxit;
     int32_t fit_type = 0;  // 0 parametric trend, 1 mean (chicdiff_nbglm_opts.fitType)
-    // tuning (chicdiff_hip_set_option): not part of the algorithm, results do not depend on them
+    // tuning (chicdiff_hip_set_option; the context's `tune` is their storage): not part of the algorithm, results do not depend on them
     int32_t spread = 1;     // line search: samples-across-lanes evaluation for straggler waves (0 = row per lane only)
     int32_t min_waves = 0;  // line search: waves per SIMD (2 .. 4; 0 = by launch_disp's rule)
-    int32_t schedule = 1;   // gene-wise line search / IRLS: visit the rows likely-long first (0 = natural order; 2 = class order through the queue only;
-                            // gene-wise only: 3 = the six half-decade classes of rounds 3-6, 4 = minDisp starts last instead of in front of the score >= 3.16 rows)
+    int32_t schedule = 1;   // gene-wise line search / IRLS: visit the rows likely-long first (0 = natural order; gene-wise only: 3 = the six
+                            // half-decade classes of rounds 3-6, 4 = minDisp starts last instead of in front of the score >= 3.16 rows; 2 is not a mode)
     int32_t deal = 0;       // ... entries per group of its static deal (0 = chosen from the number of entries per wave)
     int32_t chunk = 0;      // line search: rows per dequeue (0 = chosen from the row count; 8 .. 64)
     int32_t classes_a = 0;  // gene-wise line search: score classes dealt out statically (0 = the default, 2; 1 .. 6)
@@ -125,7 +125,7 @@ inline void order_tiles(int64_t n, int64_t &nblk, int64_t &tile) {
 //   22       score >= 10 (and the minDisp starts under kSchedSix and kSchedMinDispLast, where they were up to round 6)
 // mode = Opts::schedule: kSchedSix (3) keeps the six-class order (its classes sit at indices 0, 5, 9, 13, 18, 22).
 constexpr int kSchedClassesFine = 23, kSchedEdgesFine = 21, kSchedMinDispSlot = 17;
-constexpr int kSchedSix = 3, kSchedMinDispLast = 4;  // values of Opts::schedule besides 0 (off), 1 (on), 2 (queue only)
+constexpr int kSchedSix = 3, kSchedMinDispLast = 4;  // values of Opts::schedule besides 0 (off) and 1 (on); 2 is not a mode
 __host__ __device__ inline int sched_class(double a0, double gmin, double minDisp, int mode) {
     constexpr double edge[kSchedEdgesFine] = {0.0316, 0.0422, 0.0562, 0.0750, 0.1, 0.1334, 0.1778, 0.2371, 0.316, 0.4217, 0.5623,
                                               0.7499, 1.0, 1.3335, 1.7783, 2.3714, 3.16, 4.2170, 5.6234, 7.4989, 10.0};

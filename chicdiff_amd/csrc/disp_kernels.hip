@@ -1624,7 +1624,7 @@ static void launch_disp(bool map, const int32_t *counts, const double *nf, FitDi
                         hipStream_t st) {
     // (no schedule for a fit every row of which starts at once — n <= 65 536 is half the lanes of two waves per SIMD —: the order then
     // decides nothing, and building it is a launch and a pass: 30 k x 4 gene-wise stage 0.309 -> 0.301 ms, round 6)
-    const bool sched = !map && o.schedule && (d.n > 65536 || o.schedule == 2);
+    const bool sched = !map && o.schedule && d.n > 65536;
     if (map) disp_init_kernel<true><<<kRedBlocks, 256, 0, st>>>(d, w, o, 0, nullptr, 0, 0);
     else if (!sched) disp_init_kernel<false><<<kRedBlocks, 256, 0, st>>>(d, w, o, 0, nullptr, o.xim_here, 0);
     else {
@@ -1664,7 +1664,7 @@ static void launch_disp(bool map, const int32_t *counts, const double *nf, FitDi
     const int min_waves = (o.min_waves >= 2 && o.min_waves <= 4) ? o.min_waves : (three ? 3 : 2);
     // Filler waves (kernel: "front waves and fillers"; option "line_search_fillers"): the two-wave launch below, unchanged, as front waves
     // at priority, plus half as many waves again at priority 0 that take rows from the schedule's end only.  Never without a class order
-    // to give the boundary (natural order, schedule 2, the small fits), and only where LDS lets the third wave in (S <= 8).
+    // to give the boundary (natural order, the small fits), and only where LDS lets the third wave in (S <= 8).
     // Measured on one box, two waves -> two front waves + a filler per SIMD (profiles/r08_*): every SIMD got exactly two front waves and one
     // filler (stamps: 1 024 x (2, 1)); a front wave ticks at 8.6 us beside one front wave and one filler (7.97 in the two-wave launch, 7.1 for
     // a lone priority wave between two priority-0 waves), a filler at 18.8 us; the queue is empty at 1.04 instead of 1.18 ms and the last
@@ -1675,7 +1675,7 @@ static void launch_disp(bool map, const int32_t *counts, const double *nf, FitDi
     // 1.73 -> 1.68, 4 M x 8 2.16 -> 2.18 — not taken there (not measured in whole steps).  So: on from 1.75 M rows (half-way between the
     // two measured sizes on either side) up to where three uniform waves take over, at 4 < S <= 8; whole steps at 2 M x 8, six alternating runs:
     // 3.555 (3.551 - 3.564) -> 3.483 ms (3.476 - 3.495); the other shapes of DESIGN.md section 5 within their spread (profiles/r08_ab_summary.txt).
-    const bool fill_can = sched && o.schedule != 2 && lds3 && min_waves == 2;
+    const bool fill_can = sched && lds3 && min_waves == 2;
     const bool fill = fill_can && (o.fillers == 1 || (o.fillers < 0 && kFillerRule && d.S > 4 && d.n >= kFillerMinRows));
     const int64_t by_regs = (int64_t)(4 * min_waves) / waves_per_block;
     if (blocks_per_cu > by_regs) blocks_per_cu = by_regs;
@@ -1686,9 +1686,8 @@ static void launch_disp(bool map, const int32_t *counts, const double *nf, FitDi
     if (blocks < 1) blocks = 1;
     const unsigned int nfront = fill ? (unsigned int)(blocks * waves_per_block) : 0u;  // (the deal's "rows per lane" below are the front waves' too)
     const int64_t front_blocks = blocks;
-    // the gene-wise launch visits the rows likely-long first; schedule 2 (a fit that shares the GPU with other fits: the theta
-    // grid's lanes) keeps the class order but deals nothing out statically — its waves are not all resident at once, and a wave
-    // that starts late must not be the owner of likely-long rows
+    // the gene-wise launch visits the rows likely-long first (the theta grid's concurrent fits included: they run this schedule with
+    // its static deal, although their waves are not all resident at once — DESIGN.md section 7)
     // classes dealt out statically: 0-1 (the likely-long 8 % of the rows) — or, when the launch has 1.8 .. 8 rows per lane, all but
     // the last (everything except the minDisp starts and the highest scores), in groups of four.  The queue hands a class out in
     // chunks of 64 consecutive schedule entries: a fifth of the waves each received a whole chunk of class-2 rows (20-50 steps)
@@ -1702,8 +1701,8 @@ static void launch_disp(bool map, const int32_t *counts, const double *nf, FitDi
     // those two groups go through the queue.  Whole steps against the parent, which dealt the 3.16 - 10 rows too: 250 k x 8 1.254 -> 1.256 ms,
     // 1 M x 8 2.314 -> 2.247; profiles/r07_ab_bench_shapes.jsonl.)
     const double rows_per_lane = (double)d.n / (double)(blocks * threads);
-    const bool deal_most = !map && o.schedule != 2 && o.classes_a == 0 && rows_per_lane >= 1.8 && rows_per_lane <= 8.0;
-    const int classes_a = o.schedule == 2 ? 0 : (o.classes_a > 0 ? o.classes_a : (deal_most ? 5 : kSchedClassesA));
+    const bool deal_most = !map && o.classes_a == 0 && rows_per_lane >= 1.8 && rows_per_lane <= 8.0;
+    const int classes_a = o.classes_a > 0 ? o.classes_a : (deal_most ? 5 : kSchedClassesA);
     if (sched) launch_order_build(d, w, sched_classes_a(classes_a, o.schedule), true, st, true);
     DispArgs A{counts, nf, d, w, o, nullptr, o.spread, sched ? w.order : nullptr, (deal_most && o.deal == 0) ? 4 : o.deal, 1, kChunk,
                w.gridlist, reinterpret_cast<unsigned int *>(w.queue + (map ? 24 : 16)), o.prio, nfront,

@@ -210,7 +210,8 @@ class HipContext:
         self._check(self.lib.chicdiff_hip_set_stream(self.h, C.c_void_p(stream.cuda_stream)))
 
     def set_option(self, name: str, value: int):
-        """Tuning / test options of include/chicdiff_hip.h (results never depend on them)."""
+        """Tuning / test options: every name and range is listed above chicdiff_hip_set_option in include/chicdiff_hip.h
+        (results never depend on them); an unknown name or a value outside its range raises ChicdiffHipError."""
         self._check(self.lib.chicdiff_hip_set_option(self.h, name.encode(), int(value)))
 
     def enable_timing(self, on=True):

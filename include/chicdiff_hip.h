@@ -78,19 +78,28 @@ int chicdiff_hip_set_allgather(chicdiff_hip_ctx *ctx, chicdiff_allgather_fn fn, 
  * call reports the same number — each verdict is all-reduced before anybody acts on it. */
 int32_t chicdiff_hip_last_refits(const chicdiff_hip_ctx *ctx);
 
-/* Tuning / test options; results never depend on them, the defaults are what bench.py measures.
- *   "line_search_spread"        1 (default) | 0: evaluate straggler rows (line searches and IRLS) with their samples spread across lanes
- *   "line_search_min_waves"     2 (default) .. 4: waves per SIMD the line-search kernel variant is built for
+/* Tuning / test options; results never depend on them, the defaults are what bench.py measures.  (Every option the library
+ * accepts, in the order of its table — kOptions in chicdiff_amd/csrc/api.hip; any other name or value is CHICDIFF_E_INVALID.)
+ *   "line_search_spread"        1 (default) | 0 | 2 | 3: evaluate straggler rows (line searches and IRLS) with their samples spread across
+ *                               lanes; 0 = row per lane only; 2 = as 1 without the lean tick of the launch's end, 3 = as 1 without the layouts of
+ *                               more than 128 exchange entries (bit-identity tests)
+ *   "line_search_min_waves"     0 (default: by the launcher's rule) | 2 .. 4: waves per SIMD the line-search kernel variant is built for
+ *   "line_search_chunk"         0 (default: chosen from the row count) | 8 .. 64: rows per dequeue of the line searches
+ *   "line_search_prio"          0 (default: off) .. 100: line-search waves raise their issue priority with the age of their search, one
+ *                               level per this many iterations
  *   "line_search_schedule"      1 (default) | 0 | 3 | 4: the gene-wise line search visits the rows likely to need DESeq2's full 100
  *                               iterations first (score alpha_init * smaller group mean, in classes of 1/8 decade; the rows that
  *                               start at minDisp in front of the score >= 3.16 rows); 0 = natural row order; 3 = the six
  *                               half-decade classes of earlier releases (minDisp starts last); 4 = as 1, minDisp starts last
+ *                               (2 is not a mode)
  *   "line_search_deal"          0 (default: chosen from the rows per wave), 1 .. 64: schedule entries per group of the static deal
+ *   "line_search_classes_a"     0 (default: by the launcher's rule) | 1 .. 6: half-decade score classes of the schedule that are dealt
+ *                               out to the waves statically instead of going through the queue
  *   "line_search_fillers"       -1 (default: by the launcher's rule) | 0 | 1: the gene-wise line search runs its two waves per SIMD at
  *                               issue priority and adds a third at priority 0 that takes only rows from the schedule's end (score >= 3.16:
- *                               never long); always off where the schedule has no class order ("line_search_schedule" 0, small fits, the
- *                               theta grid's concurrent fits) and at S > 8
- *   "line_search_filler_stop"   -1 (default: 100) | 0 .. 100: fillers stop claiming once the other waves have claimed this share (percent) of
+ *                               never long); always off where the schedule has no class order ("line_search_schedule" 0, small fits)
+ *                               and at S > 8
+ *   "line_search_filler_stop"   -1 (default: 85) | 0 .. 100: fillers stop claiming once the other waves have claimed this share (percent) of
  *                               their own part of the queue (100 = never, 0 = fillers claim nothing)
  *   "theta_grid_concurrency"    5 (default), 1 .. 16: fits of the theta grid in flight at once (single rank only)
  *   "host_copy_threads"         12 (default), 1 .. 64: host threads staging caller buffers in chicdiff_hip_nbglm_fit
@@ -103,10 +112,16 @@ int32_t chicdiff_hip_last_refits(const chicdiff_hip_ctx *ctx);
  *                               coefficients then differ in summation order only (1e-13)
  *   "trend_mad_in_kernel"       1 (default) | 0: the single-launch trend kernel goes on to the residuals, their exact median and MAD
  *                               and the closed-form prior variance; 0 = separate launches (residuals, two radix selects): same bits
+ *   "fuse_offsets"              1 (default) | 0 | 2: chicdiff_hip_wald_test_dev and the theta grid form the offsets inside the fit's
+ *                               first kernel for fits of up to 2^18 rows at S <= 16; 0 = always by a launch of their own, 2 = always
+ *                               inside (at S <= 16): same bits
  *   "region_assemble_generic"   0 (default) | 1: test option of chicdiff_hip_region_assemble_dev (see there): same bits
- *   "fault_inject"              0 (default); test hook, one-shot bits consumed by the next call: 1 = this rank reports a select
+ *   "fault_inject"              0 (default) .. 7; test hook, one-shot bits consumed by the next call: 1 = this rank reports a select
  *                               overflow in its next fit, 2 = a grid-barrier timeout of its trend kernel, 4 = an overflow of its
  *                               next size-factor select — to prove that all ranks of a sharded fit refit together
+ *   "bench_fake_world"          0 (default) | 1 .. 64: rehearsal hook of bench.py, refused above 1 unless CHICDIFF_BENCH_FAKE_WORLD is set
+ *                               in the environment: on a 1-rank communicator the trend's rows are gathered as if this many ranks had
+ *                               each sent this rank's block (a rank's step of an N-GPU fit at its share of the rows)
  * and one that does change the outcome of a fit whose parametric trend fails (DESeq2 offers the same choice through fitType):
  *   "local_trend_substitute"    1 (default) | 0: report CHICDIFF_ST_TREND_FAILED instead of substituting the local regression */
 int chicdiff_hip_set_option(chicdiff_hip_ctx *ctx, const char *name, int64_t value);

@@ -1202,6 +1202,53 @@ def test_line_search_layouts_agree_bit_for_bit(ctx, n, S, group):
         assert np.array_equal(a[k], e[k], equal_nan=True), f"{k}: schedules differ in {np.sum(~((a[k] == e[k]) | (np.isnan(a[k]) & np.isnan(e[k]))))} rows"
 
 
+# (name, default, lowest, highest, refused inside the range) of every option of chicdiff_hip_set_option
+OPTION_RANGES = [
+    ("line_search_spread", 1, 0, 3, ()), ("line_search_min_waves", 0, 0, 4, (1,)), ("line_search_prio", 0, 0, 100, ()),
+    ("line_search_fillers", -1, -1, 1, ()), ("line_search_filler_stop", -1, -1, 100, ()), ("line_search_chunk", 0, 0, 64, (1, 7)),
+    ("line_search_classes_a", 0, 0, 6, ()), ("line_search_schedule", 1, 0, 4, (2,)), ("line_search_deal", 0, 0, 64, ()),
+    ("local_trend_substitute", 1, 0, 1, ()), ("sharded_trend_gather", 1, 0, 1, ()), ("trend_mad_in_kernel", 1, 0, 1, ()),
+    ("select_all_rounds", 0, 0, 1, ()), ("trend_one_launch_per_pass", 0, 0, 1, ()), ("region_assemble_generic", 0, 0, 1, ()),
+    ("theta_grid_concurrency", 5, 1, 16, ()), ("host_copy_threads", 12, 1, 64, ()), ("trend_persistent_blocks", 0, 0, 256, ()),
+    ("fuse_offsets", 1, 0, 2, ()), ("fault_inject", 0, 0, 7, ()),
+]
+
+
+@pytest.mark.parametrize("name,default,lo,hi,holes", OPTION_RANGES, ids=[r[0] for r in OPTION_RANGES])
+def test_set_option_accepted_ranges(ctx, name, default, lo, hi, holes):
+    """The ranges chicdiff_hip_set_option accepts, option by option: the value below the lowest, the value above the highest and the
+    values it refuses in between raise; the lowest, the highest and the default are accepted (fault_inject: only 0 — a set bit would
+    be consumed by a later test's fit).  The context is left at the default."""
+    from chicdiff_amd import hip
+    try:
+        for bad in (lo - 1, hi + 1) + tuple(holes):
+            with pytest.raises(hip.ChicdiffHipError, match="unknown option or value"):
+                ctx.set_option(name, bad)
+        if name != "fault_inject":
+            ctx.set_option(name, lo)
+            ctx.set_option(name, hi)
+    finally:
+        ctx.set_option(name, default)
+
+
+def test_set_option_bench_fake_world_and_unknown_names(ctx):
+    from chicdiff_amd import hip
+    try:
+        ctx.set_option("bench_fake_world", 0)
+        ctx.set_option("bench_fake_world", 1)
+        if "CHICDIFF_BENCH_FAKE_WORLD" not in os.environ:
+            with pytest.raises(hip.ChicdiffHipError, match="rehearsal hook of bench.py"):
+                ctx.set_option("bench_fake_world", 2)
+        for bad in (-1, 65):
+            with pytest.raises(hip.ChicdiffHipError, match="unknown option or value"):
+                ctx.set_option("bench_fake_world", bad)
+    finally:
+        ctx.set_option("bench_fake_world", 0)
+    for name in ("line_search", "line_search_spread ", "opt_spread", ""):
+        with pytest.raises(hip.ChicdiffHipError, match="unknown option or value"):
+            ctx.set_option(name, 0)
+
+
 def test_kernel_timing_modes(ctx):
     """chicdiff_hip_enable_timing: 1 brackets every stage of a call with HIP events, 2 only the three fit kernels, 3 the gene-wise
     line search alone (what bench.py's timed region uses), 0 nothing; the results do not depend on it.  Since round 5 the fused call
