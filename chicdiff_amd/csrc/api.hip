@@ -1708,6 +1708,43 @@ extern "C" int chicdiff_hip_selftest_math_dev(chicdiff_hip_ctx *c, int32_t op, c
     return CHICDIFF_OK;
 }
 
+// building blocks with a second argument / a second result (header: the op numbers)
+extern "C" int chicdiff_hip_selftest_math3_dev(chicdiff_hip_ctx *c, int32_t op, const double *d_x, const double *d_y, int64_t n, double *d_out,
+                                               double *d_out2) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (!d_x || !d_y || !d_out || !d_out2 || n < 0 || op < 10 || op > 18) return fail(c, CHICDIFF_E_INVALID, "selftest_math3: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n > 0) launch_math3_selftest(op, d_x, d_y, n, c->d_logfact, d_out, d_out2, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CHICDIFF_OK;
+}
+
+// the dispersion objective at chosen points: the fit's own prep, then objective_probe_kernel (disp_kernels.hip)
+extern "C" int chicdiff_hip_selftest_objective_dev(chicdiff_hip_ctx *c, const int32_t *d_counts, const double *d_nf, int64_t n, int32_t S,
+                                                   const int32_t *group, const chicdiff_nbglm_opts *opts, const double *d_log_alpha, int32_t K,
+                                                   const double *d_prior_mean, double prior_var, int32_t live_rows, double *d_lp,
+                                                   double *d_dlp, double *d_alpha, double *d_mu, int32_t *lanes_per_row) {
+    if (!c) return CHICDIFF_E_INVALID;
+    FitDims d;
+    if (!d_counts || !d_nf || !d_log_alpha || !d_lp || !d_dlp || !d_alpha || !d_mu || K < 1 || live_rows < 0 || live_rows > 64 ||
+        (d_prior_mean && !(prior_var > 0)))
+        return fail(c, CHICDIFF_E_INVALID, "selftest_objective: bad arguments");
+    if (int rc = check_counts_group(c, n, S, group, d)) return rc;
+    if (int rc = check_opts(c, opts)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_workspace(c, n, S)) return rc;
+    const Opts o = make_opts(c, opts, S);
+    HIPCHK(c, hipMemsetAsync(c->w.sc, 0, align256(sizeof(FitScalars)) + kQueueBytes + 1024, c->stream));
+    launch_prep(d_counts, const_cast<double *>(d_nf), d, c->w, o, c->stream);  // (not fused: nf is read, never written)
+    ObjectiveProbe pb{d_log_alpha, K, d_prior_mean, d_prior_mean ? 1.0 / prior_var : 0.0, live_rows, d_lp, d_dlp, d_alpha, d_mu};
+    const int lanes = launch_objective_probe(d, c->w, o, pb, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (lanes < 0) return fail(c, CHICDIFF_E_INVALID, "selftest_objective: the line search has no samples-across-lanes layout for %d live rows at S = %d", live_rows, S);
+    HIPCHK(c, hipGetLastError());
+    if (lanes_per_row) *lanes_per_row = lanes;
+    return CHICDIFF_OK;
+}
+
 // host-side self tests of the simulation-matched prior variance (no device involved)
 extern "C" int chicdiff_hip_selftest_r_random(int32_t kind, uint32_t seed, double a, double b, int64_t n, double *out) {
     if (!out || n < 0 || kind < 0 || kind > 3) return CHICDIFF_E_INVALID;

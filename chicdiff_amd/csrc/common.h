@@ -296,6 +296,21 @@ hipError_t launch_region_assemble(const int32_t *bait, const int32_t *oe, int64_
 void launch_count_join_inner(const int32_t *bait, const int32_t *oe, int64_t nru, int S, const int64_t *const *keys,
                              const int32_t *const *vals, const int64_t *nkeys, int32_t *out, hipStream_t st);
 void launch_math_selftest(int op, const double *x, int64_t n, double *out, hipStream_t st);
+void launch_math3_selftest(int op, const double *x, const double *y, int64_t n, const double *logfact, double *out, double *out2, hipStream_t st);
+// the dispersion objective on its own (disp_kernels.hip, objective_probe_kernel): K points a[i * K + k] per row of a prepared fit
+// (w.rowpack: launch_prep), evaluated row per lane (live_rows = 0) or with `live_rows` rows per wave in the samples-across-lanes layout the
+// line search would choose for that many; returns the lanes per row of that layout (1: row per lane), or -1 if the search has no
+// samples-across-lanes layout for that S and number of rows (nothing is launched then)
+struct ObjectiveProbe {
+    const double *a;           // n x K evaluation points, log(alpha)
+    int K;
+    const double *prior_mean;  // per row, or NULL: no prior (the gene-wise search's objective)
+    double prior_isig;         // 1 / prior variance
+    int live_rows;
+    double *lp, *dlp, *alpha;  // n x K
+    double *mu;                // S x n: the means the row's evaluations used
+};
+int launch_objective_probe(FitDims d, FitWork w, Opts o, const ObjectiveProbe &pb, hipStream_t st);
 void launch_pvalues(const double *stat, int64_t n, double *p, hipStream_t st);
 
 }  // namespace cd

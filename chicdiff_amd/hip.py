@@ -33,7 +33,7 @@ EXPORTS = [
     "chicdiff_hip_rccl_unique_id", "chicdiff_hip_rccl_init", "chicdiff_hip_cooks_filter_dev",
     "chicdiff_hip_independent_filtering_dev",
     "chicdiff_hip_nbglm_fit_dev", "chicdiff_hip_nbglm_fit", "chicdiff_hip_wald_test_dev", "chicdiff_hip_theta_grid_dev",
-    "chicdiff_hip_wald_pvalues_dev", "chicdiff_hip_selftest_math_dev", "chicdiff_hip_selftest_r_random", "chicdiff_hip_selftest_sched_class", "chicdiff_hip_selftest_queue_claim",
+    "chicdiff_hip_wald_pvalues_dev", "chicdiff_hip_selftest_math_dev", "chicdiff_hip_selftest_math3_dev", "chicdiff_hip_selftest_objective_dev", "chicdiff_hip_selftest_r_random", "chicdiff_hip_selftest_sched_class", "chicdiff_hip_selftest_queue_claim",
     "chicdiff_hip_selftest_prior_mc", "chicdiff_hip_selftest_chinput", "chicdiff_hip_kernel_times", "chicdiff_hip_enable_timing",
 ]
 
@@ -144,6 +144,9 @@ def load_library() -> C.CDLL:
                                               C.POINTER(Opts), C.POINTER(dbl)]
     L.chicdiff_hip_wald_pvalues_dev.argtypes = [vp, vp, i64, vp]
     L.chicdiff_hip_selftest_math_dev.argtypes = [vp, i32, vp, i64, vp]
+    L.chicdiff_hip_selftest_math3_dev.argtypes = [vp, i32, vp, vp, i64, vp, vp]
+    L.chicdiff_hip_selftest_objective_dev.argtypes = [vp, vp, vp, i64, i32, C.POINTER(i32), C.POINTER(Opts), vp, i32, vp, dbl, i32, vp, vp,
+                                                      vp, vp, C.POINTER(i32)]
     L.chicdiff_hip_kernel_times.argtypes = [vp, C.POINTER(KernelTime), i32]
     L.chicdiff_hip_kernel_times.restype = i32
     L.chicdiff_hip_enable_timing.argtypes = [vp, i32]
@@ -624,6 +627,29 @@ class HipContext:
         out = self.torch.empty_like(d_x)
         self._check(self.lib.chicdiff_hip_selftest_math_dev(self.h, op, d_x.data_ptr(), d_x.numel(), out.data_ptr()))
         return out
+
+    def selftest_math3(self, op: int, d_x, d_y):
+        """Two-argument / two-result building blocks (include/chicdiff_hip.h: the op numbers) -> (out, out2)."""
+        out, out2 = self.torch.empty_like(d_x), self.torch.empty_like(d_x)
+        self._check(self.lib.chicdiff_hip_selftest_math3_dev(self.h, op, d_x.data_ptr(), d_y.data_ptr(), d_x.numel(), out.data_ptr(),
+                                                             out2.data_ptr()))
+        return out, out2
+
+    def selftest_objective(self, d_counts, d_nf, group, d_log_alpha, d_prior_mean=None, prior_var=1.0, live_rows=0,
+                           opts: Opts | None = None):
+        """The dispersion objective at d_log_alpha (n, K): dict of lp, dlp, alpha (n, K), mu (S, n) and lanes_per_row."""
+        S, n = d_counts.shape
+        K = d_log_alpha.shape[1]
+        t = self.torch
+        lp, dlp, alpha = (t.empty((n, K), dtype=t.float64, device=self.device) for _ in range(3))
+        mu = t.empty((S, n), dtype=t.float64, device=self.device)
+        g = (C.c_int32 * S)(*[int(x) for x in group])
+        lanes = C.c_int32(0)
+        self._check(self.lib.chicdiff_hip_selftest_objective_dev(
+            self.h, d_counts.data_ptr(), d_nf.data_ptr(), n, S, g, C.byref(opts) if opts is not None else None,
+            d_log_alpha.data_ptr(), K, d_prior_mean.data_ptr() if d_prior_mean is not None else None, float(prior_var),
+            int(live_rows), lp.data_ptr(), dlp.data_ptr(), alpha.data_ptr(), mu.data_ptr(), C.byref(lanes)))
+        return dict(lp=lp, dlp=dlp, alpha=alpha, mu=mu, lanes_per_row=lanes.value)
 
     def wald_pvalues(self, d_stat):
         out = self.torch.empty_like(d_stat)

@@ -409,6 +409,26 @@ int chicdiff_hip_wald_pvalues_dev(chicdiff_hip_ctx *ctx, const double *d_stat, i
 /* Device-math self test: out[i] = f(x[i]) with op 0 log (polynomial), 1 log (table), 2 reciprocal,
  * 3 lgamma, 4 digamma, 5 2*pnorm(-|x|), 8 exp (table) — the special functions the fit kernels are built on. */
 int chicdiff_hip_selftest_math_dev(chicdiff_hip_ctx *ctx, int32_t op, const double *d_x, int64_t n, double *d_out);
+/* The same for the functions of two arguments / two results that carry the dispersion objective, the constant part of the NB
+ * log-likelihood and the reported deviance, each called as the kernels call it; y[i] is an integer count held in a double:
+ * op 10 lgr_eval_t(lgr_make_t(x), y) and 11 lgr_eval(lgr_make(x), y) = lgamma(y + x) - lgamma(x), 12 lgr_eval(lgr_one(), y) = log(y!),
+ * 13 tlog1p_from(x, 1 + x, rcp(1 + x)) and 14 flog1p_from(...) = log1p(x), 15 rcp_or_div(x) = 1 / x, 16 stirling(x, log x, 1 / x):
+ * out = lgamma(x), out2 = digamma(x) for x >= 10, 17 rlog_t(x) = R's log(x), 18 the host's table of log(y!), y < 1024.
+ * out2 is NaN for the ops with one result. */
+int chicdiff_hip_selftest_math3_dev(chicdiff_hip_ctx *ctx, int32_t op, const double *d_x, const double *d_y, int64_t n, double *d_out,
+                                    double *d_out2);
+/* The dispersion objective on its own: log posterior of log(alpha) (DESeq2 fitDisp's log_posterior), its derivative and alpha =
+ * exp(log alpha) at K points per row, d_log_alpha[i * K + k], computed by the functions the line searches and the grid fallback
+ * stop on, from the row records the fit's first kernel writes.  counts / nf / group / opts as for chicdiff_hip_nbglm_fit_dev.
+ * d_prior_mean: per row, or NULL for the gene-wise objective (no prior); prior_var: the prior's variance.  live_rows = 0: one row per
+ * lane; 1 .. 64: that many rows per wave, their samples spread across lanes as the line search does for so many live rows at the end
+ * of a launch (CHICDIFF_E_INVALID where it would not) — *lanes_per_row (may be NULL) gets the lanes a row was given (1: row per lane).
+ * Results: d_lp, d_dlp, d_alpha (n x K) and d_mu (n x S, column-major): the means max(nf * group mean, minmu) the evaluations used.
+ * An all-zero row has no objective: NaN everywhere. */
+int chicdiff_hip_selftest_objective_dev(chicdiff_hip_ctx *ctx, const int32_t *d_counts, const double *d_nf, int64_t n, int32_t S,
+                                        const int32_t *group, const chicdiff_nbglm_opts *opts, const double *d_log_alpha, int32_t K,
+                                        const double *d_prior_mean, double prior_var, int32_t live_rows, double *d_lp, double *d_dlp,
+                                        double *d_alpha, double *d_mu, int32_t *lanes_per_row);
 
 /* Host-side self tests of the pieces behind CHICDIFF_ST_PRIORVAR_MC (no device, no context).
  * _r_random: set.seed(seed) followed by n draws of kind 0 runif(n), 1 rnorm(n), 2 rexp(n), 3 rgamma(n, shape = a,
