@@ -124,6 +124,8 @@ struct chicdiff_hip_ctx {
     double *d_logfact = nullptr;  // kLogFactN doubles: log(k!) (wald_prep)
     PmcTable *d_pmc[4] = {nullptr, nullptr, nullptr, nullptr};  // simulated residual densities + loess operator per d.f. (prior_mc.h)
     double *d_nf_tmp = nullptr;
+    unsigned int *d_sfhist = nullptr;  // kSfWorkWords: value-bin histograms (+ list lengths) of the direct size-factor select; zero between calls (sf_pick_kernel)
+    bool sfhist_dirty = false;         // ... unless a call's launches did not all go out
     FitScalars *h_sc = nullptr;  // pinned
     double *h_sf = nullptr;      // pinned, kMaxS
     // timing
@@ -511,7 +513,7 @@ static int ensure_workspace(chicdiff_hip_ctx *c, int64_t n, int S) {
     const size_t selcnt = align256(sizeof(double) * (size_t)kSelMaxWorld * kMaxS * 2);
     const size_t rowpack = align256((size_t)row_stride(S) * (size_t)n);
     const size_t start4 = align256(sizeof(double) * 4 * (size_t)n);
-    const size_t total = nd * n_double_arrays + ni * n_int_arrays + partials + 2 * hist + selcnt + align256(sizeof(FitScalars)) + kQueueBytes + 1024 + kPlaceWords * 8 + nfbytes + rowpack + start4;
+    const size_t total = nd * n_double_arrays + ni * n_int_arrays + partials + 2 * hist + selcnt + align256(sizeof(FitScalars)) + kQueueBytes + 1024 + kPlaceWords * 8 + nfbytes + rowpack + start4 + align256(sizeof(unsigned int) * kSfWorkWords);
     hipError_t e = hipMalloc(&c->ws, total);
     if (e != hipSuccess) return fail(c, CHICDIFF_E_NOMEM, "workspace of %zu bytes: %s", total, hipGetErrorString(e));
     c->ws_bytes = total;
@@ -537,7 +539,9 @@ static int ensure_workspace(chicdiff_hip_ctx *c, int64_t n, int S) {
     w.place = (unsigned long long *)p; p += kPlaceWords * 8;
     c->d_nf_tmp = (double *)p; p += nfbytes;
     w.rowpack = p; p += rowpack;
-    w.start = (double *)p;
+    w.start = (double *)p; p += start4;
+    c->d_sfhist = (unsigned int *)p;
+    c->sfhist_dirty = true;  // (cleared by the first select that uses it)
     c->cap_n = n;
     c->cap_S = S;
     // scalars, queue heads and barrier counters start from zero: size_factors_impl runs before any fit has cleared them, and a
@@ -1436,9 +1440,6 @@ int chicdiff_hip_nbglm_fit(chicdiff_hip_ctx *c, const int32_t *counts, const dou
 // the fit does not clear), from where the fit's last all-reduce — or sf_overflow_consensus — makes it every rank's verdict.
 static int size_factors_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, int64_t n, int32_t S, bool all_rounds) {
     Scope t(c, "size_factors");
-    // (the offsets buffer is free until the size factors exist; the same kernel clears the select's overflow flag, c->d_carry — a
-    // device word the fit does not clear: the fit's last kernel carries it into the all-reduced verdicts)
-    launch_row_ratio(d_counts, n, S, c->d_nf_tmp, c->d_carry, c->stream);
     SelArgs sa{};
     sa.mode = SEL_SIZEFACTOR;
     sa.ncol = S;
@@ -1447,8 +1448,22 @@ static int size_factors_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, int64
     sa.S = S;
     sa.sf_out = c->d_sf;  // the finishing step of the select writes the size factors there
     sa.overflow_out = c->d_carry;
-    const int rc = run_select(c, sa, all_rounds);
-    if (rc) return rc;
+    // (the offsets buffer is free until the size factors exist; on either route the first kernel clears the select's overflow flag,
+    // c->d_carry — a device word the fit does not clear: the fit's last kernel carries it into the all-reduced verdicts)
+    if (S <= kSfMaxS && !c->allreduce && !all_rounds) {
+        // single rank: two passes over the counts, keys recomputed, no key matrix (global_kernels.hip).  Option "select_all_rounds"
+        // = 1 — and the repeat after an overflow verdict, which only the test hook below can raise here — take the radix select.
+        if (c->sfhist_dirty) HIPCHK(c, hipMemsetAsync(c->d_sfhist, 0, sizeof(unsigned int) * kSfWorkWords, c->stream));
+        c->sfhist_dirty = true;
+        launch_sf_direct(d_counts, n, S, sa, c->w, c->d_sfhist, reinterpret_cast<uint64_t *>(c->d_nf_tmp), c->d_carry,
+                         c->cu_count, c->stream);
+        HIPCHK(c, hipGetLastError());
+        c->sfhist_dirty = false;  // every launch went out: the pick leaves the histograms zero
+    } else {
+        launch_row_ratio(d_counts, n, S, c->d_nf_tmp, c->d_carry, c->stream);
+        const int rc = run_select(c, sa, all_rounds);
+        if (rc) return rc;
+    }
     if (c->host.fault_inject & 4) {  // test hook: this rank's size-factor select "could not fit its candidate list"
         c->host.fault_inject &= ~4;
         launch_poke(c->d_carry, 1, c->stream);
@@ -1760,6 +1775,19 @@ extern "C" int chicdiff_hip_selftest_sched_class(int32_t mode, double min_disp, 
     if (n < 0 || (n > 0 && (!alpha_init || !group_mean || !cls_out)) || mode < 1 || mode > 4) return CHICDIFF_E_INVALID;
     for (int64_t i = 0; i < n; i++) cls_out[i] = cd::sched_class(alpha_init[i], group_mean[i], min_disp, mode);
     if (bounds) for (int a = 0; a <= 6; a++) bounds[a] = cd::sched_classes_a(a, mode);
+    return CHICDIFF_OK;
+}
+// the value bins of the direct size-factor select (common.h: sf_bin, sf_sub_bin), evaluated on the host: bins per column for S samples
+// (*nbins_out), the bin of each x, and — sub_out given — its sub-bin inside bin `sub_of`
+extern "C" int chicdiff_hip_selftest_sf_bin(int32_t S, const double *x, int64_t n, int32_t *nbins_out, int32_t *bin_out, int32_t sub_of,
+                                            int32_t *sub_out) {
+    if (S < 1 || S > cd::kSfMaxS || n < 0 || (n > 0 && (!x || !bin_out))) return CHICDIFF_E_INVALID;
+    const int nb = cd::sf_bins(S);
+    if (nbins_out) *nbins_out = nb;
+    for (int64_t i = 0; i < n; i++) {
+        bin_out[i] = cd::sf_bin(x[i], nb);
+        if (sub_out) sub_out[i] = cd::sf_sub_bin(x[i], nb, sub_of);
+    }
     return CHICDIFF_OK;
 }
 // the claim rule of the gene-wise line search's two-ended queue (common.h: queue_claim, filler_claims, filler_stop_f), evaluated on the host

@@ -251,6 +251,34 @@ void launch_sel_gather_place(SelArgs a, FitWork w, int world, int rank, hipStrea
 void launch_sel_gather_finish(SelArgs a, FitWork w, int world, int rank, hipStream_t st);
 
 void launch_row_ratio(const int32_t *counts, int64_t n, int S, double *ratio, int32_t *clear_flag, hipStream_t st);  // keys of the size-factor medians (+ *clear_flag = 0)
+
+// ---- direct select of the size-factor medians (global_kernels.hip, "size factors in two passes over the counts") ----
+// The keys log(count) - row log geometric mean are never stored: a first pass over the counts bins them BY VALUE, a pick finds
+// the bin(s) that hold the two middle ranks of every column, a second pass recomputes the keys and lists those of the picked bins,
+// and a finish reads the exact order statistics off the lists.  Exactness asks two things of the bin function: that it never
+// decreases as the key grows, and that both passes evaluate it alike — not that the bins be equally full or the ends open.
+// Bins of equal width over [kSfBinLo, kSfBinLo + kSfBinSpan), the end bins taking whatever lies outside; as many bins per column
+// as kSfHistWords LDS words allow for 4, 8 or 16 columns (3840, 1920, 960: bin width 1/480, 1/240, 1/120).
+constexpr double kSfBinLo = -4.0, kSfBinSpan = 8.0;
+constexpr int kSfHistWords = 15360;  // pass 1 keeps every column's histogram in LDS: 60 KB beside the 1 KB logarithm table
+constexpr int kSfSubBins = 4096;     // the finish splits a picked bin's width once more
+constexpr int kSfMaxS = 16;
+constexpr int kSfWorkWords = kSfHistWords + 2 * kSfMaxS * 32;  // the global histograms, then the lists' lengths (one per 128 bytes)
+__host__ __device__ inline int sf_bins(int S) { return kSfHistWords / (S <= 4 ? 4 : S <= 8 ? 8 : 16); }
+__host__ __device__ inline double sf_bin_pos(double x, int nb) { return (x - kSfBinLo) * ((double)nb / kSfBinSpan); }
+__host__ __device__ inline int sf_bin(double x, int nb) {
+    const double u = floor(sf_bin_pos(x, nb));
+    return u < 0.0 ? 0 : (u > (double)(nb - 1) ? nb - 1 : (int)u);
+}
+// ... and the sub-bin of a key inside bin b (keys of an end bin that lie outside the range all fall into the first / last one)
+__host__ __device__ inline int sf_sub_bin(double x, int nb, int b) {
+    const double u = floor((sf_bin_pos(x, nb) - (double)b) * (double)kSfSubBins);
+    return u < 0.0 ? 0 : (u > (double)(kSfSubBins - 1) ? kSfSubBins - 1 : (int)u);
+}
+// hist: kSfWorkWords words, the histograms all zero (the pick leaves them so); lists: n x S words, column j's keys from j * n (free: the offsets buffer)
+// cus: compute units of the device (both passes run one workgroup on each)
+void launch_sf_direct(const int32_t *counts, int64_t n, int S, SelArgs a, FitWork w, unsigned int *hist, uint64_t *lists,
+                      int32_t *clear_flag, int cus, hipStream_t st);
 void launch_offsets(const double *fullMean, const double *sf_dev, int64_t n, int S, double theta, int mix,
                     double *out, hipStream_t st);
 void launch_window_sums(const int32_t *fragN, const double *fragFM, int64_t nfrag, int S, const int64_t *rptr,

@@ -1274,6 +1274,395 @@ void launch_row_ratio(const int32_t *counts, int64_t n, int S, double *ratio, in
     else row_ratio_kernel<<<kRedBlocks, 256, 0, st>>>(counts, n, S, ratio, clear_flag);
 }
 
+// ---- size factors in two passes over the counts (single rank, S <= 16; common.h: sf_bin) -------------------------------------
+// row_ratio16 + the radix select write the n x S keys once and read them three times (576 MB at 2 M x 8 for S medians).  A key is S
+// table logarithms and a subtraction on a row that has to be read anyway, so here the counts are read twice and the keys recomputed:
+//   sf_hist   every column's histogram of the keys' VALUE bins, in LDS, added to the global one
+//   sf_pick   per column: population, the two middle ranks, the bin(s) that hold them and the ranks inside (and the global
+//             histogram back to zero for the next call)
+//   sf_list   the keys of the picked bins appended to the column's list (slot 0 from the front of its n words, slot 1 — the upper
+//             middle's bin when it is another — from the back: together at most n keys, so a list cannot overflow whatever the ties)
+//   sf_finish per column: the exact order statistics of the list(s), then sel_finish_col as the radix select ends
+// Plain stream-ordered launches: no grid barrier, nothing that needs workgroups to be resident together.
+
+// The keys of one row, by row_ratio16_kernel's expressions (-ffp-contract=off: the same bits wherever this is inlined — the two
+// passes must agree on every key).  false = the row is not used (a zero or negative count).
+template <int SM>
+__device__ __forceinline__ bool sf_row_keys(const int32_t (&kc)[SM], int S, const LogEntry *lt, double (&x)[SM]) {
+    double l[SM];
+#pragma unroll
+    for (int j = 0; j < SM; j++) {
+        const int32_t k = kc[j];
+        l[j] = k > 0 ? tlog((double)k, lt) : (k == 0 ? -INFINITY : NAN);  // log(0) = -Inf drops the row, as in R
+    }
+    double s = 0;
+#pragma unroll
+    for (int j = 0; j < SM; j++)
+        if (j < S) s += l[j];  // sample order
+    const double lg = s / S;
+#pragma unroll
+    for (int j = 0; j < SM; j++) x[j] = l[j] - lg;
+    return isfinite(lg);
+}
+
+// hist_add with an early way out: real data ties in a few values (a wave's lanes on one LDS word serialise), the benchmark's
+// hardly at all — one look for a group of equal bins, more only while the groups found are worth it
+__device__ __forceinline__ void sf_hist_add(unsigned int *h, bool valid, unsigned int bin) {
+    unsigned long long todo = __ballot(valid);
+    const int lane = threadIdx.x & 63;
+    for (int it = 0; it < 4 && todo; it++) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const unsigned int bl = (unsigned int)__builtin_amdgcn_readlane((int)bin, leader);  // (no LDS round trip: `leader` is wave-uniform)
+        const unsigned long long same = __ballot(valid && bin == bl) & todo;
+        const int cnt = __popcll(same);
+        if (lane == leader) atomicAdd(&h[bl], (unsigned int)cnt);
+        todo &= ~same;
+        if (cnt < 4) break;
+    }
+    if ((todo >> lane) & 1ull) atomicAdd(&h[bin], 1u);
+}
+
+constexpr int kSfThreads = 1024;  // every launch of the route: workgroups of 16 waves
+constexpr int kSfStage = 4096;    // keys a workgroup of sf_list stages in LDS before it reserves room in the lists
+constexpr int kSfCntStride = 32;  // the lists' lengths (words behind the global histograms) lie 128 bytes apart
+
+// The bin that holds 0-based rank r of a histogram of nb <= 4 x kSfThreads counters (LDS or global), for nr ranks at once: the first
+// bin b with h[0] + ... + h[b] > r, else the last one (fit_state.h sel_pick; parallel as in mad_select: thread t owns `per`
+// consecutive bins, a scan over the workgroup, the owning thread refines).  from_total: the ranks are the two middles of the
+// histogram's own total.  Every thread of the workgroup calls it and gets the same answers; ends with a barrier.
+__device__ __forceinline__ void sf_wg_pick(const unsigned int *h, int nb, int nr, bool from_total, double (&rank)[2], int (&bin)[2],
+                                           double (&rin)[2], unsigned int (&cnt)[2], double &total_out) {
+    __shared__ double sh_scan[kSfThreads / 64], sh_rin[2];
+    __shared__ int sh_bin[2];
+    __shared__ unsigned int sh_cnt[2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int per = (nb + kSfThreads - 1) / kSfThreads;
+    double mine[4] = {0, 0, 0, 0}, acc = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int b = tid * per + q;
+        if (q < per && b < nb) mine[q] = (double)h[b];
+        acc += mine[q];
+    }
+    double incl = acc;  // inclusive scan over the workgroup (counts: exact in fp64)
+    for (int off = 1; off < 64; off <<= 1) {
+        const double o = __shfl_up(incl, off);
+        if (lane >= off) incl += o;
+    }
+    if (lane == 63) sh_scan[wave] = incl;
+    __syncthreads();
+    double before_wave = 0, total = 0;
+    for (int q = 0; q < kSfThreads / 64; q++) {
+        if (q < wave) before_wave += sh_scan[q];
+        total += sh_scan[q];
+    }
+    incl += before_wave;
+    const double before = incl - acc;
+    const bool last_thread = tid == (nb - 1) / per;
+    if (from_total) {  // R median(): the two middles
+        const int64_t mi = (int64_t)total;
+        rank[0] = (double)((mi - 1) / 2);
+        rank[1] = (double)(mi / 2);
+    }
+    for (int s = 0; s < nr; s++) {
+        const double r = rank[s];
+        if ((before <= r && r < incl) || (last_thread && r >= incl && incl == total)) {
+            double cum = before;
+            int q = 0;
+            for (; q < per - 1 && tid * per + q < nb - 1; q++) {
+                if (cum + mine[q] > r) break;
+                cum += mine[q];
+            }
+            sh_bin[s] = tid * per + q;
+            sh_rin[s] = r - cum;
+            sh_cnt[s] = (unsigned int)mine[q];
+        }
+    }
+    __syncthreads();
+    for (int s = 0; s < nr; s++) {
+        bin[s] = sh_bin[s];
+        rin[s] = sh_rin[s];
+        cnt[s] = sh_cnt[s];
+    }
+    total_out = total;
+    __syncthreads();  // (the shared words belong to the next call from here on)
+}
+
+template <int SM>
+__global__ __launch_bounds__(kSfThreads) void sf_hist_kernel(const int32_t *__restrict__ counts, int64_t n, int S, int nb,
+                                                            unsigned int *__restrict__ ghist, int32_t *clear_flag) {
+    if (clear_flag && blockIdx.x == 0 && threadIdx.x == 0) *clear_flag = 0;  // (nothing on this route sets it: as row_ratio16_kernel)
+    __shared__ LogEntry s_lt[64];
+    __shared__ unsigned int s_h[kSfHistWords];
+    const int words = S * nb;
+    for (int k = threadIdx.x; k < words; k += kSfThreads) s_h[k] = 0;
+    log_table_to_lds(s_lt);
+    const int64_t step = (int64_t)gridDim.x * kSfThreads;
+    int32_t kn[SM];  // the next row's counts are loaded before the current row is worked on
+    int64_t i = (int64_t)blockIdx.x * kSfThreads + threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < SM; j++) kn[j] = (j < S && i < n) ? counts[(int64_t)j * n + i] : 1;
+    for (; i < n; i += step) {
+        int32_t kc[SM];
+        double x[SM];
+#pragma unroll
+        for (int j = 0; j < SM; j++) kc[j] = kn[j];
+        if (i + step < n) {
+#pragma unroll
+            for (int j = 0; j < SM; j++) kn[j] = j < S ? counts[(int64_t)j * n + i + step] : 1;
+        }
+        const bool use = sf_row_keys<SM>(kc, S, s_lt, x);
+#pragma unroll
+        for (int j = 0; j < SM; j++)
+            if (j < S) sf_hist_add(s_h + j * nb, use, (unsigned int)sf_bin(x[j], nb));
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < words; k += kSfThreads) {
+        const unsigned int c = s_h[k];
+        if (c) atomicAdd(&ghist[k], c);
+    }
+}
+
+// what sf_pick leaves in the select's scalars for the two launches behind it: sel_count = population, sel_prefix[2 c + slot] = the
+// bin of the slot's rank (nb, which no key has, for an empty population), sel_rank = the rank inside that bin; and the lengths of the
+// column's two lists (gcnt) at zero
+__global__ __launch_bounds__(kSfThreads) void sf_pick_kernel(FitWork w, unsigned int *ghist, unsigned int *gcnt, int nb) {
+    const int col = blockIdx.x;
+    FitScalars *sc = w.sc;
+    unsigned int *g = ghist + (size_t)col * nb;
+    double rank[2], rin[2], total;
+    int bin[2];
+    unsigned int cnt[2];
+    sf_wg_pick(g, nb, 2, true, rank, bin, rin, cnt, total);
+    for (int k = threadIdx.x; k < nb; k += kSfThreads) g[k] = 0;  // (every thread has read its bins: sf_wg_pick ends with a barrier)
+    if (threadIdx.x < 2) {
+        const int slot = threadIdx.x;
+        sc->sel_prefix[2 * col + slot] = (uint64_t)(total > 0 ? bin[slot] : nb);
+        sc->sel_rank[2 * col + slot] = rin[slot];
+        gcnt[(2 * col + slot) * kSfCntStride] = 0;
+        if (slot == 0) sc->sel_count[col] = total;
+        if (slot == 0 && col == 0) sc->sel_fast_done = 0;
+    }
+}
+
+// One atomic per wave and list straight into the lists' lengths made this launch 312 us at 2 M x 8: about every wave trip holds a
+// wanted key, the returning atomics of 256 CUs queue on the one cache line the sixteen lengths shared.  So a workgroup keeps what it
+// finds in LDS and reserves room once per list at its end; only keys beyond kSfStage (massive ties) go out at once, wave by wave.
+template <int SM>
+__global__ __launch_bounds__(kSfThreads) void sf_list_kernel(const int32_t *__restrict__ counts, int64_t n, int S, int nb, FitWork w,
+                                                            unsigned int *__restrict__ gcnt, uint64_t *__restrict__ lists) {
+    __shared__ LogEntry s_lt[64];
+    __shared__ int s_b[2][kSfMaxS];
+    __shared__ uint64_t s_key[kSfStage];
+    __shared__ unsigned char s_tag[kSfStage];  // 2 x column + slot
+    __shared__ unsigned int s_n, s_lc[2 * kSfMaxS], s_base[2 * kSfMaxS];
+    const FitScalars *sc = w.sc;
+    if ((int)threadIdx.x < 2 * S) s_b[threadIdx.x & 1][threadIdx.x >> 1] = (int)sc->sel_prefix[threadIdx.x];
+    if (threadIdx.x < 2 * kSfMaxS) s_lc[threadIdx.x] = 0;
+    if (threadIdx.x == 0) s_n = 0;
+    log_table_to_lds(s_lt);
+    const int lane = threadIdx.x & 63;
+    const int64_t step = (int64_t)gridDim.x * kSfThreads;
+    int32_t kn[SM];
+    int64_t i = (int64_t)blockIdx.x * kSfThreads + threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < SM; j++) kn[j] = (j < S && i < n) ? counts[(int64_t)j * n + i] : 1;
+    for (; i < n; i += step) {
+        int32_t kc[SM];
+        double x[SM];
+#pragma unroll
+        for (int j = 0; j < SM; j++) kc[j] = kn[j];
+        if (i + step < n) {
+#pragma unroll
+            for (int j = 0; j < SM; j++) kn[j] = j < S ? counts[(int64_t)j * n + i + step] : 1;
+        }
+        const bool use = sf_row_keys<SM>(kc, S, s_lt, x);
+        unsigned int hit = 0;  // bit j: column j's key lies in the bin of slot 0; bit 16 + j: in that of slot 1, another bin
+#pragma unroll
+        for (int j = 0; j < SM; j++)
+            if (j < S) {
+                const int b = sf_bin(x[j], nb);
+                const int b0 = s_b[0][j], b1 = s_b[1][j];
+                hit |= (b == b0 ? 1u : 0u) << j;
+                hit |= (b != b0 && b == b1 ? 1u : 0u) << (16 + j);
+            }
+        if (!use) hit = 0;
+        unsigned int over = 0;  // the hits that found the stage full
+        if (hit != 0) {
+#pragma unroll
+            for (int j = 0; j < SM; j++)
+#pragma unroll
+                for (int slot = 0; slot < 2; slot++)
+                    if (j < S && ((hit >> (16 * slot + j)) & 1u)) {
+                        const unsigned int pos = atomicAdd(&s_n, 1u);
+                        if (pos < (unsigned int)kSfStage) {
+                            s_key[pos] = key_of(x[j]);
+                            s_tag[pos] = (unsigned char)(2 * j + slot);
+                        } else over |= 1u << (16 * slot + j);
+                    }
+        }
+        if (__ballot(over != 0) == 0ull) continue;
+#pragma unroll
+        for (int j = 0; j < SM; j++)
+            if (j < S) {
+#pragma unroll
+                for (int slot = 0; slot < 2; slot++) {  // one atomic per wave and list: the leader reserves, every lane writes its own
+                    const bool m = (over >> (16 * slot + j)) & 1u;
+                    const unsigned long long mask = __ballot(m);
+                    if (mask == 0ull) continue;
+                    const int leader = __ffsll((long long)mask) - 1;
+                    unsigned int base = 0;
+                    if (lane == leader) base = atomicAdd(&gcnt[(2 * j + slot) * kSfCntStride], (unsigned int)__popcll(mask));
+                    base = (unsigned int)__shfl((int)base, leader);
+                    if (m) {
+                        const int64_t pos = (int64_t)base + __popcll(mask & ((1ull << lane) - 1ull));
+                        lists[(int64_t)j * n + (slot ? n - 1 - pos : pos)] = key_of(x[j]);
+                    }
+                }
+            }
+    }
+    __syncthreads();
+    const int staged = (int)(s_n < (unsigned int)kSfStage ? s_n : (unsigned int)kSfStage);
+    for (int e = threadIdx.x; e < staged; e += kSfThreads) atomicAdd(&s_lc[s_tag[e]], 1u);
+    __syncthreads();
+    if ((int)threadIdx.x < 2 * S) {
+        const unsigned int c = s_lc[threadIdx.x];
+        s_base[threadIdx.x] = c ? atomicAdd(&gcnt[threadIdx.x * kSfCntStride], c) : 0u;
+        s_lc[threadIdx.x] = 0;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < staged; e += kSfThreads) {
+        const int t = s_tag[e], j = t >> 1;
+        const int64_t pos = (int64_t)s_base[t] + atomicAdd(&s_lc[t], 1u);
+        lists[(int64_t)j * n + ((t & 1) ? n - 1 - pos : pos)] = s_key[e];
+    }
+}
+
+constexpr int kSfCand = 1024;  // keys of one sub-bin that are ranked by counting; more (massive ties, keys beyond the binned range): radix rounds
+__device__ __forceinline__ uint64_t sf_list_at(const uint64_t *list, int64_t n, bool back, int64_t e) { return list[back ? n - 1 - e : e]; }
+
+// The keys of ranks rk[0 .. nr) (0-based, inside the list) of a list of m keys that all lie in value bin b.  One histogram of the
+// keys' sub-bins (about one key each on the benchmark's data), the sub-bin of each rank picked, its few keys ranked by counting
+// those in front of each (smaller, or equal with a lower index).  A sub-bin with more than kSfCand keys is massive ties or an end
+// bin whose keys lie beyond the binned range: the rank is then found by the radix select's own six rounds over the key bits, the
+// whole list scanned by this workgroup each round — slow and exact, as sel_tail_rounds is.  Results in s_res (LDS), behind a barrier.
+__device__ __forceinline__ void sf_list_select(const uint64_t *list, int64_t n, bool back, int64_t m, int nb, int b, int nr,
+                                               double (&rk)[2], unsigned int *s_h, uint64_t *s_c, unsigned int *s_nc, uint64_t *s_res) {
+    const int tid = threadIdx.x;
+    for (int k = tid; k < kSfSubBins; k += kSfThreads) s_h[k] = 0;
+    __syncthreads();
+    for (int64_t e = tid; e < m; e += kSfThreads)
+        sf_hist_add(s_h, true, (unsigned int)sf_sub_bin(value_of(sf_list_at(list, n, back, e)), nb, b));
+    __syncthreads();
+    int sb[2];
+    double rin[2], total;
+    unsigned int cnt[2];
+    sf_wg_pick(s_h, kSfSubBins, nr, false, rk, sb, rin, cnt, total);
+    for (int q = 0; q < nr; q++) {
+        const bool shared = nr == 2 && sb[0] == sb[1] && cnt[0] <= (unsigned int)kSfCand;  // both ranks off one set of candidates
+        if (q == 1 && shared) break;
+        if (cnt[q] <= (unsigned int)kSfCand) {
+            if (tid == 0) *s_nc = 0;
+            __syncthreads();
+            for (int64_t e = tid; e < m; e += kSfThreads) {
+                const uint64_t key = sf_list_at(list, n, back, e);
+                if (sf_sub_bin(value_of(key), nb, b) == sb[q]) s_c[atomicAdd(s_nc, 1u)] = key;
+            }
+            __syncthreads();
+            const int nc = (int)cnt[q];
+            if (tid < nc) {
+                const uint64_t mine = s_c[tid];
+                int less = 0;
+                for (int k = 0; k < nc; k++) {
+                    const uint64_t o = s_c[k];
+                    less += (o < mine || (o == mine && k < tid)) ? 1 : 0;
+                }
+                if ((double)less == rin[q]) s_res[q] = mine;
+                if (shared && (double)less == rin[1]) s_res[1] = mine;
+            }
+            __syncthreads();
+        } else {
+            uint64_t p = 0;
+            double r[2] = {rk[q], 0};
+            for (int round = 0; round < 6; round++) {
+                const int shift = kSelShifts[round], bits = sel_bits(shift), hi = shift + bits;
+                const uint64_t dmask = (1ull << bits) - 1ull;
+                for (int k = tid; k < kSelBins; k += kSfThreads) s_h[k] = 0;
+                __syncthreads();
+                for (int64_t e = tid; e < m; e += kSfThreads) {
+                    const uint64_t key = sf_list_at(list, n, back, e);
+                    sf_hist_add(s_h, sel_match(key, p, hi), (unsigned int)((key >> shift) & dmask));
+                }
+                __syncthreads();
+                int rb[2];
+                double rr[2], rt;
+                unsigned int rc[2];
+                sf_wg_pick(s_h, 1 << bits, 1, false, r, rb, rr, rc, rt);
+                p |= (uint64_t)rb[0] << shift;
+                r[0] = rr[0];
+            }
+            if (tid == 0) s_res[q] = p;
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(kSfThreads) void sf_finish_kernel(SelArgs a, FitWork w, int nb, const unsigned int *__restrict__ gcnt,
+                                                              const uint64_t *__restrict__ lists) {
+    __shared__ unsigned int s_h[kSelBins > kSfSubBins ? kSelBins : kSfSubBins];
+    __shared__ uint64_t s_c[kSfCand], s_res[2];
+    __shared__ unsigned int s_nc;
+    const int col = blockIdx.x;
+    FitScalars *sc = w.sc;
+    const int b0 = (int)sc->sel_prefix[2 * col], b1 = (int)sc->sel_prefix[2 * col + 1];
+    const double rank0 = sc->sel_rank[2 * col], rank1 = sc->sel_rank[2 * col + 1];
+    const int64_t m0 = gcnt[2 * col * kSfCntStride], m1 = gcnt[(2 * col + 1) * kSfCntStride];
+    const bool empty = !(sc->sel_count[col] > 0);
+    const uint64_t *list = lists + (int64_t)col * a.n;
+    // (an empty population ends on the prefixes the radix select's rounds leave for one: a NaN pattern; the median is NaN by sel_count)
+    if (threadIdx.x < 2) s_res[threadIdx.x] = 0xFFFFFF0000000000ull;
+    __syncthreads();
+    if (!empty) {
+        if (b0 == b1) {
+            double rk[2] = {rank0, rank1};
+            const int nr = rank0 == rank1 ? 1 : 2;
+            sf_list_select(list, a.n, false, m0, nb, b0, nr, rk, s_h, s_c, &s_nc, s_res);
+            if (nr == 1 && threadIdx.x == 0) s_res[1] = s_res[0];
+        } else {  // the two middles of an even population in different bins: a list each
+            double rk[2] = {rank0, 0};
+            sf_list_select(list, a.n, false, m0, nb, b0, 1, rk, s_h, s_c, &s_nc, s_res);
+            rk[0] = rank1;
+            sf_list_select(list, a.n, true, m1, nb, b1, 1, rk, s_h, s_c, &s_nc, s_res + 1);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        sc->sel_prefix[2 * col] = s_res[0];
+        sc->sel_prefix[2 * col + 1] = s_res[1];
+        if (col == 0) sc->sel_fast_done = 1;
+        sel_finish_col(a, sc, col);  // size factor of the column, as the radix select ends
+    }
+}
+
+void launch_sf_direct(const int32_t *counts, int64_t n, int S, SelArgs a, FitWork w, unsigned int *hist, uint64_t *lists,
+                      int32_t *clear_flag, int cus, hipStream_t st) {
+    const int nb = sf_bins(S);
+    // both passes: one 16-wave workgroup per CU and a grid-stride loop.  LDS (62 KB) would let a second one in, registers do not (65 at
+    // S = 8: a SIMD holds seven such waves, two workgroups need eight); and every workgroup of pass 1 ends by adding its S x nb
+    // counters to the global histogram, so more of them is more of that
+    int64_t hb = (n + kSfThreads - 1) / kSfThreads;
+    if (hb > (cus > 0 ? cus : 256)) hb = cus > 0 ? cus : 256;
+    unsigned int *gcnt = hist + kSfHistWords;
+    if (S <= 4) sf_hist_kernel<4><<<(unsigned)hb, kSfThreads, 0, st>>>(counts, n, S, nb, hist, clear_flag);
+    else if (S <= 8) sf_hist_kernel<8><<<(unsigned)hb, kSfThreads, 0, st>>>(counts, n, S, nb, hist, clear_flag);
+    else sf_hist_kernel<16><<<(unsigned)hb, kSfThreads, 0, st>>>(counts, n, S, nb, hist, clear_flag);
+    sf_pick_kernel<<<S, kSfThreads, 0, st>>>(w, hist, gcnt, nb);
+    if (S <= 4) sf_list_kernel<4><<<(unsigned)hb, kSfThreads, 0, st>>>(counts, n, S, nb, w, gcnt, lists);
+    else if (S <= 8) sf_list_kernel<8><<<(unsigned)hb, kSfThreads, 0, st>>>(counts, n, S, nb, w, gcnt, lists);
+    else sf_list_kernel<16><<<(unsigned)hb, kSfThreads, 0, st>>>(counts, n, S, nb, w, gcnt, lists);
+    sf_finish_kernel<<<S, kSfThreads, 0, st>>>(a, w, nb, gcnt, lists);
+}
+
 // a4: offsets.  One thread per row.  For S <= 16 the row lives in registers (one HBM read, one write);
 // larger S re-reads the row from L1/L2.  log() keeps R's semantics for NA/0/negative inputs, the
 // common positive-finite case takes the cheaper flog().

@@ -103,7 +103,8 @@ int32_t chicdiff_hip_last_refits(const chicdiff_hip_ctx *ctx);
  *                               their own part of the queue (100 = never, 0 = fillers claim nothing)
  *   "theta_grid_concurrency"    5 (default), 1 .. 16: fits of the theta grid in flight at once (single rank only)
  *   "host_copy_threads"         12 (default), 1 .. 64: host threads staging caller buffers in chicdiff_hip_nbglm_fit
- *   "select_all_rounds"         0 (default) | 1: exact medians by histogram rounds only (no candidate-sort shortcut)
+ *   "select_all_rounds"         0 (default) | 1: exact medians by histogram rounds only (no candidate-sort shortcut; the size factors of a
+ *                               single-rank call with S <= 16: by the radix select over stored keys instead of two passes over the counts)
  *   "trend_one_launch_per_pass" 0 (default) | 1: trend fit as one launch per IRLS pass instead of one persistent kernel
  *   "sharded_trend_gather"      1 (default) | 0: sharded fits exchange the trend's rows once and fit them on every rank,
  *                               instead of one all-reduce per IRLS pass (same coefficients up to summation order)
@@ -454,6 +455,10 @@ int chicdiff_hip_selftest_sched_class(int32_t mode, double min_disp, const doubl
  * in the rows fillers may take (first_back; >= chunks: none) and the stop share in percent ("line_search_filler_stop"). */
 int chicdiff_hip_selftest_queue_claim(uint64_t old, int32_t back, uint32_t chunks, uint32_t first_back, int32_t stop_percent, int32_t claimed,
                                       uint32_t *chunk_out, int32_t *again_out);
+/* _sf_bin (host only): the value bins of the single-rank size-factor select, as its kernels apply them.  *nbins_out (may be NULL): the
+ * number of bins per column for S samples (<= 16); bin_out[n]: the bin of each key x (log count - row log geometric mean); sub_out[n] (may be NULL):
+ * its sub-bin inside bin `sub_of`.  Both never decrease as x grows: all the select's exactness asks of them. */
+int chicdiff_hip_selftest_sf_bin(int32_t S, const double *x, int64_t n, int32_t *nbins_out, int32_t *bin_out, int32_t sub_of, int32_t *sub_out);
 
 /* Timing of the last *_dev call's kernels, measured with HIP events on the context's stream:
  * fills up to `cap` (name, milliseconds, launches) records; returns the number available. */
