@@ -1964,6 +1964,65 @@ extern "C" int chicdiff_hip_region_universe_dev(chicdiff_hip_ctx *c, const int32
     return CHICDIFF_OK;
 }
 
+// getCandidateInteractions (chicdiff.R:2068-2163): everything is enqueued behind one another; the one host stop is the read of the
+// counts (and of the refusals' row numbers, which ride in the same 40 bytes)
+extern "C" int chicdiff_hip_candidate_interactions_dev(chicdiff_hip_ctx *c, const int32_t *d_baitID, const int32_t *d_minOE,
+                                                       const int32_t *d_maxOE, const double *d_p, int64_t n, const int32_t *d_peak_baitID,
+                                                       const int32_t *d_peak_oeID, const double *d_scores, int64_t npeaks, int32_t ncols,
+                                                       int32_t ncond1, int32_t ncond2, int32_t merged, double score, double pvcut,
+                                                       double minDeltaAsinhScore, int64_t pair_capacity, int32_t *d_group_peak,
+                                                       int64_t *d_group_ptr, double *d_group_min_p, double *d_group_delta, int32_t *d_pair_row,
+                                                       int64_t *ngroups_host, int64_t *npairs_host) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (ngroups_host) *ngroups_host = 0;
+    if (npairs_host) *npairs_host = 0;
+    if (!d_baitID || !d_minOE || !d_maxOE || !d_p || !d_group_peak || !d_group_ptr || !d_group_min_p || !d_group_delta || !ngroups_host ||
+        !npairs_host || (pair_capacity > 0 && !d_pair_row) || pair_capacity < 0 || (npeaks > 0 && (!d_peak_baitID || !d_peak_oeID || !d_scores)))
+        return fail(c, CHICDIFF_E_INVALID, "candidate_interactions: bad arguments");
+    if (n < 1 || n >= (1ll << 31))
+        return fail(c, CHICDIFF_E_INVALID, "candidate_interactions: n = %lld regions (1 <= n < 2^31: pair rows are int32)", (long long)n);
+    if (ncols < 2) return fail(c, CHICDIFF_E_INVALID, "candidate_interactions: ncols = %d score columns (at least one per condition)", (int)ncols);
+    if (npeaks < 0 || npeaks >= (1ll << 31))
+        return fail(c, CHICDIFF_E_INVALID, "candidate_interactions: npeaks = %lld (0 <= npeaks < 2^31)", (long long)npeaks);
+    if ((merged != 0 && merged != 1) || ncond1 < 1 || ncond2 < 1 || ncond1 + ncond2 != ncols || (merged && ncols != 2))
+        return fail(c, CHICDIFF_E_INVALID, "candidate_interactions: ncond1 = %d, ncond2 = %d, merged = %d do not describe %d score columns",
+                    (int)ncond1, (int)ncond2, (int)merged, (int)ncols);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_aux(c, cand_workspace_bytes(n, npeaks))) return rc;
+    CandArgs a;
+    a.bait = d_baitID; a.minOE = d_minOE; a.maxOE = d_maxOE; a.p = d_p; a.n = n;
+    a.peak_bait = d_peak_baitID; a.peak_oe = d_peak_oeID; a.scores = d_scores; a.npeaks = npeaks;
+    a.ncols = ncols; a.ncond1 = ncond1; a.merged = merged;
+    a.score = score; a.pvcut = pvcut; a.min_delta = minDeltaAsinhScore; a.pair_capacity = pair_capacity;
+    a.group_peak = d_group_peak; a.group_ptr = d_group_ptr; a.group_min_p = d_group_min_p; a.group_delta = d_group_delta;
+    a.pair_row = d_pair_row;
+    const CandResult *d_res = nullptr;
+    timing_reset(c);
+    {
+        Scope t(c, "candidates");
+        if (launch_candidates(a, c->aux, c->stream, &d_res)) return fail(c, CHICDIFF_E_HIP, "candidate_interactions: sort/scan failed");
+    }
+    CandResult h;
+    HIPCHK(c, hipMemcpyAsync(&h, d_res, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    timing_collect(c);
+    if (h.bad_region != ~0ull)
+        return fail(c, CHICDIFF_E_INVALID, "candidate_interactions: region row %llu has minOE > maxOE or an NA (INT32_MIN) key: foverlaps stops on it",
+                    h.bad_region);
+    if (h.bad_peak_key != ~0ull)
+        return fail(c, CHICDIFF_E_INVALID, "candidate_interactions: peak row %llu has baitID = oeID = INT32_MAX, which is not a fragment ID", h.bad_peak_key);
+    if (h.dup_peak != ~0ull)
+        return fail(c, CHICDIFF_E_INVALID, "candidate_interactions: peak row %llu repeats the (baitID, oeID) of an earlier selected row: the peak matrix "
+                    "has one row per pair", h.dup_peak);
+    *ngroups_host = h.ngroups;
+    *npairs_host = h.npairs;
+    if (h.npairs > pair_capacity)
+        return fail(c, CHICDIFF_E_INVALID, "candidate_interactions: room for %lld pairs needed, %lld given (no pair was written)", h.npairs,
+                    (long long)pair_capacity);
+    return CHICDIFF_OK;
+}
+
 extern "C" int chicdiff_hip_count_table_dev(chicdiff_hip_ctx *c, const int32_t *d_bait, const int32_t *d_oe, const int32_t *d_N,
                                             int64_t nrows, const uint8_t *d_bait_in_RU, int32_t max_id, int64_t *d_keys,
                                             int32_t *d_vals, int64_t *nkeys_host) {

@@ -323,6 +323,29 @@ hipError_t launch_region_assemble(const int32_t *bait, const int32_t *oe, int64_
                                   void *scratch, int force_generic, hipStream_t st);
 void launch_count_join_inner(const int32_t *bait, const int32_t *oe, int64_t nru, int S, const int64_t *const *keys,
                              const int32_t *const *vals, const int64_t *nkeys, int32_t *out, hipStream_t st);
+// candidate_kernels.hip — getCandidateInteractions (chicdiff.R:2068-2163)
+struct CandArgs {
+    const int32_t *bait, *minOE, *maxOE;  // region table, caller's row order
+    const double *p;
+    int64_t n;
+    const int32_t *peak_bait, *peak_oe;
+    const double *scores;                 // npeaks x ncols, column-major
+    int64_t npeaks;
+    int32_t ncols, ncond1, merged;
+    double score, pvcut, min_delta;
+    int64_t pair_capacity;
+    int32_t *group_peak;
+    int64_t *group_ptr;
+    double *group_min_p, *group_delta;
+    int32_t *pair_row;
+};
+// what the host reads back: the two counts, and the smallest offending row of each refusal (all ones = none)
+struct CandResult {
+    unsigned long long bad_region, bad_peak_key, dup_peak;
+    long long ngroups, npairs;
+};
+size_t cand_workspace_bytes(int64_t n, int64_t npeaks);
+int launch_candidates(const CandArgs &a, char *ws, hipStream_t st, const CandResult **res_out);
 void launch_math_selftest(int op, const double *x, int64_t n, double *out, hipStream_t st);
 void launch_math3_selftest(int op, const double *x, const double *y, int64_t n, const double *logfact, double *out, double *out2, hipStream_t st);
 // the dispersion objective on its own (disp_kernels.hip, objective_probe_kernel): K points a[i * K + k] per row of a prepared fit

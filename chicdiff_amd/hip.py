@@ -27,6 +27,7 @@ EXPORTS = [
     "chicdiff_hip_offsets_dev", "chicdiff_hip_window_sums_dev", "chicdiff_hip_count_join_dev",
     "chicdiff_hip_fragment_background_dev", "chicdiff_hip_bh_adjust_dev", "chicdiff_hip_ihw_apply_dev",
     "chicdiff_hip_region_universe_count_dev", "chicdiff_hip_region_universe_fill_dev", "chicdiff_hip_region_universe_dev", "chicdiff_hip_count_table_dev",
+    "chicdiff_hip_candidate_interactions_dev",
     "chicdiff_hip_chinput_read", "chicdiff_hip_chinput_table_dev", "chicdiff_hip_region_avdist_dev",
     "chicdiff_hip_count_join_inner_dev", "chicdiff_hip_count_join_multi_dev", "chicdiff_hip_region_assemble_dev",
     "chicdiff_hip_malloc", "chicdiff_hip_free", "chicdiff_hip_outstanding_allocations", "chicdiff_hip_memcpy_h2d", "chicdiff_hip_memcpy_d2h",
@@ -135,6 +136,8 @@ def load_library() -> C.CDLL:
     L.chicdiff_hip_region_universe_count_dev.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp, vp, vp, C.POINTER(i64)]
     L.chicdiff_hip_region_universe_fill_dev.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp, vp, vp, vp]
     L.chicdiff_hip_region_universe_dev.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
+    L.chicdiff_hip_candidate_interactions_dev.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, dbl, dbl, dbl, i64,
+                                                          vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
     L.chicdiff_hip_nbglm_fit_dev.argtypes = [vp, vp, vp, i64, i32, C.POINTER(i32), C.POINTER(Opts), C.POINTER(Out),
                                              C.POINTER(Scalars)]
     L.chicdiff_hip_nbglm_fit.argtypes = L.chicdiff_hip_nbglm_fit_dev.argtypes
@@ -548,6 +551,57 @@ class HipContext:
         if 2 * total.value < cap:  # (a view would pin the whole upper-bound allocation for as long as the universe lives)
             rb, rr, ro = rb.clone(), rr.clone(), ro.clone()
         return dict(region_ptr=ptr, minOE=mn, maxOE=mx, baitID=rb, regionID=rr, otherEndID=ro)
+
+    # -- getCandidateInteractions ----------------------------------------------------------------
+    def candidate_interactions(self, d_baitID, d_minOE, d_maxOE, d_p, d_peak_baitID, d_peak_oeID, d_scores, ncond1, ncond2, merged,
+                               score, pvcut, minDeltaAsinhScore, pair_row=None):
+        """getCandidateInteractions' join and filter (chicdiff.R:2068-2163; the rules are above
+        chicdiff_hip_candidate_interactions_dev in include/chicdiff_hip.h).  Region table: int32 (n,) tensors and the chosen
+        p column, float64 (n,), in the rows' own order; peak matrix rows as read: int32 (npeaks,) IDs and ``d_scores`` of shape
+        (ncols, npeaks), contiguous (= the C ABI's column-major npeaks x ncols), condition 1's columns first.
+
+        Returns dict(group_peak, group_ptr, group_min_p, group_delta, pair_row, ngroups, npairs), the tensors trimmed to the
+        surviving groups and their pairs.  The first call gives room for 16 npeaks pairs; if that is too little (duplicate
+        regions have no bound) it is repeated once with exactly the reported need.  ``pair_row``: a caller's int32 buffer
+        instead — its length is the capacity, and there is no second call: too small raises, with ``.need = (ngroups, npairs)``."""
+        torch = self.torch
+        n, (ncols, npeaks) = d_baitID.numel(), d_scores.shape
+        for t in (d_baitID, d_minOE, d_maxOE, d_peak_baitID, d_peak_oeID):
+            assert t.dtype == torch.int32 and t.is_contiguous()
+        assert d_p.dtype == torch.float64 and d_scores.dtype == torch.float64 and d_p.is_contiguous() and d_scores.is_contiguous()
+        assert d_minOE.numel() == n and d_maxOE.numel() == n and d_p.numel() == n
+        assert d_peak_baitID.numel() == npeaks and d_peak_oeID.numel() == npeaks
+        gpeak = torch.empty(max(npeaks, 1), dtype=torch.int32, device=self.device)
+        gptr = torch.empty(npeaks + 1, dtype=torch.int64, device=self.device)
+        gmin, gdelta = (torch.empty(max(npeaks, 1), dtype=torch.float64, device=self.device) for _ in range(2))
+        ng, npairs = C.c_int64(0), C.c_int64(0)
+
+        def call(pairs):
+            return self.lib.chicdiff_hip_candidate_interactions_dev(
+                self.h, d_baitID.data_ptr(), d_minOE.data_ptr(), d_maxOE.data_ptr(), d_p.data_ptr(), n, d_peak_baitID.data_ptr(),
+                d_peak_oeID.data_ptr(), d_scores.data_ptr(), npeaks, ncols, int(ncond1), int(ncond2), int(bool(merged)), float(score),
+                float(pvcut), float(minDeltaAsinhScore), pairs.numel(), gpeak.data_ptr(), gptr.data_ptr(), gmin.data_ptr(),
+                gdelta.data_ptr(), pairs.data_ptr(), C.byref(ng), C.byref(npairs))
+
+        own = pair_row is None
+        pairs = torch.empty(max(16 * npeaks, 1), dtype=torch.int32, device=self.device) if own else pair_row
+        assert pairs.dtype == torch.int32 and pairs.is_contiguous()
+        rc = call(pairs)
+        if rc and npairs.value > pairs.numel():          # the capacity status: both counts are written, no pair is
+            if not own:
+                e = ChicdiffHipError(f"[{rc}] " + self.lib.chicdiff_hip_last_error(self.h).decode())
+                e.need = (ng.value, npairs.value)
+                raise e
+            pairs = torch.empty(npairs.value, dtype=torch.int32, device=self.device)
+            rc = call(pairs)
+        self._check(rc)
+        self.last_candidates_ms = self.kernel_times().get("candidates", (0.0, 0))[0]
+        g, m = ng.value, npairs.value
+        pairs = pairs[:m]
+        if own and 2 * m < pairs.numel():   # (a view would pin the whole 16 npeaks allocation)
+            pairs = pairs.clone()
+        return dict(group_peak=gpeak[:g].clone(), group_ptr=gptr[: g + 1].clone(), group_min_p=gmin[:g].clone(), group_delta=gdelta[:g].clone(),
+                    pair_row=pairs, ngroups=g, npairs=m)
 
     # -- a6 + a7 ----------------------------------------------------------------------------
     def nbglm_fit(self, d_counts, d_nf, group, want=None, opts: Opts | None = None, outputs: dict | None = None):

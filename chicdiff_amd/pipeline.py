@@ -10,6 +10,8 @@ here; the reference's own chicdiffPipeline() needs no change).
       DESeq2Wrap(chicdiff.settings, RUcontrol, FullRegionData[[2]], suffix = "Control", theta = attributes(DESeqOut)$theta)
       IHWcorrection(chicdiff.settings, DESeqOut, FullRegionData[[1]], DESeqOutControl, FullRegionData[[2]],
                     countput = FullRegionData[[3]])                              :1956-2065 -> avDist from the device, ihw() stays R
+    getCandidateInteractions(output, peakFiles, chicdiff.settings, ...)          :2068-2163 -> device overlap join + filter; the
+                                                                                              survivors' strings on the host
 
 ``chicdiff_settings`` is the reference's 17-key list as a dict, passed through UNCHANGED (chicdiff_amd/settings.py);
 in particular ``device`` keeps meaning the plot device.  What stays outside this module, as in SURVEY.md §2: reading
@@ -399,3 +401,76 @@ def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, r
     finally:
         if own:
             ctx.close()
+
+
+# ---- getCandidateInteractions, chicdiff.R:2068-2163 --------------------------------------------------------------------------
+def _fmt_double(x):
+    # as.character(<double>): 15 significant digits (unpinned: no R here); NA prints as "NA" inside paste()
+    return "NA" if x != x else "%.15g" % x
+
+
+def getCandidateInteractions(output, peakFiles, chicdiff_settings, pcol="weighted_padj", method="min", minDeltaAsinhScore=1, pvcut=0.05,
+                             ctx=None):
+    """chicdiff.R:2068-2163: region-level results -> fragment-level candidate interactions.  The sort of the regions, the overlap
+    join of every peak against the regions of its bait, min(pcol) per (baitID, oeID) and the final filter run on the device
+    (chicdiff_hip_candidate_interactions_dev); only the surviving groups come back, and their four paste()d columns are built
+    here.  ``output``: the results table (a DataFrame, or the path of the _results.csv IHWcorrection wrote); ``peakFiles``: ONE
+    peak matrix, read as it is — only the score filter applies (:2082-2087), not readAndFilterPeakMatrix's other filters.
+    ``method = "hmp"`` is not offered: harmonicmeanp::p.hmp stays R."""
+    import pandas as pd
+    if method not in ("min", "hmp"):                                               # :2095-2097
+        raise ValueError("getCandidateInteractions error: Unknown method to combine p-values (should be 'min' or 'hmp')")
+    if method == "hmp":
+        raise ValueError("getCandidateInteractions: method = 'hmp' needs harmonicmeanp::p.hmp (the tail of a Landau distribution), "
+                         "which stays R; the device path offers method = 'min'")
+    raw = chicdiff_settings["chicagoData"]
+    raw = raw[0] if isinstance(raw, (list, tuple)) and len(raw) == 1 and isinstance(raw[0], dict) else raw
+    conds = list(raw)
+    if len(conds) != 2:
+        raise ValueError("getCandidateInteractions: chicagoData must hold two conditions")
+    # :2102-2114 — names(chicagoData[[k]]) when the condition maps named replicates to files, else the condition's own name
+    cnames = [list(raw[c]) if isinstance(raw[c], dict) and len(raw[c]) else [c] for c in conds]
+    merged = not isinstance(raw[conds[0]], dict)                                   # :2118 is.null(names(chicagoData[[1]]))
+    s = asChicdiffSettings(chicdiff_settings)
+    score, target = s["score"], list(s["targetColumns"])
+    x = pd.read_csv(peakFiles, sep=None, engine="python")                          # fread(peakFiles)
+    x = x[list(x.columns[:11]) + [c for c in x.columns[11:] if c in target]]      # :2080-2081
+    names = cnames[0] + cnames[1]
+    if sorted(names) != sorted(c for c in x.columns[11:]) or (merged and len(names) != 2):
+        raise ValueError(f"getCandidateInteractions: the score columns {names} named by chicagoData must be the targetColumns of the peak file")
+    if isinstance(output, str):
+        output = pd.read_csv(output)
+    from . import hip
+    own = ctx is None
+    if own:
+        from .settings import hipDevice
+        ctx = hip.HipContext(hipDevice(chicdiff_settings))
+    try:
+        torch = ctx.torch
+        dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(ctx.device)
+        scores = np.ascontiguousarray(x[names].to_numpy(np.float64).T)
+        r = ctx.candidate_interactions(dev(output["baitID"], np.int32), dev(output["minOE"], np.int32), dev(output["maxOE"], np.int32),
+                                       dev(output[pcol], np.float64), dev(x["baitID"], np.int32), dev(x["oeID"], np.int32),
+                                       dev(scores, np.float64), len(cnames[0]), len(cnames[1]), merged, score, pvcut, minDeltaAsinhScore)
+        gp, ptr, rows = r["group_peak"].cpu().numpy(), r["group_ptr"].cpu().numpy(), r["pair_row"].cpu().numpy()
+        min_p, delta = r["group_min_p"].cpu().numpy(), r["group_delta"].cpu().numpy()
+    finally:
+        if own:
+            ctx.close()
+    first = rows[ptr[:-1]] if len(gp) else np.zeros(0, dtype=np.int64)           # baitstart[1], baitend[1]: the group's first region
+    px = x.iloc[gp]
+    final = {"baitID": px["baitID"].to_numpy(), "oeID": px["oeID"].to_numpy(), "baitChr": px["baitChr"].to_numpy(),
+             "baitstart": output["baitstart"].to_numpy()[first], "baitend": output["baitend"].to_numpy()[first],
+             "baitName": px["baitName"].to_numpy()}
+    for c in names:
+        final[c] = px[c].to_numpy()
+    final["min_" + pcol] = min_p
+    final["deltaAsinhScore"] = delta
+    rid, lfc, pv = output["regionID"].to_numpy(), output["log2FoldChange"].to_numpy(np.float64), output[pcol].to_numpy(np.float64)
+    oes, oee = output["OEstart"].to_numpy(), output["OEend"].to_numpy()
+    groups = [rows[ptr[g]:ptr[g + 1]] for g in range(len(gp))]
+    final["regionIDs"] = [",".join(str(rid[k]) for k in g) for g in groups]
+    final["log2FoldChanges"] = [",".join(_fmt_double(lfc[k]) for k in g) for g in groups]
+    final[pcol] = [",".join(_fmt_double(pv[k]) for k in g) for g in groups]
+    final["OEranges"] = [",".join(f"{oes[k]}-{oee[k]}" for k in g) for g in groups]
+    return pd.DataFrame(final)

@@ -378,6 +378,50 @@ int chicdiff_hip_region_universe_dev(chicdiff_hip_ctx *ctx, const int32_t *d_bai
                                      int32_t *d_maxOE, int32_t *d_ru_baitID, int32_t *d_ru_regionID, int32_t *d_ru_otherEndID,
                                      int64_t capacity, int64_t *total_host);
 
+/* getCandidateInteractions (chicdiff.R:2068-2163): the region-level results turned into fragment-level candidate interactions —
+ * setkey(output, baitID, minOE, maxOE), the overlap join of every peak row against the regions of its bait (foverlaps, :2129),
+ * min(pcol) per (baitID, oeID) group and the final filter (:2161).  No work is done on host buffers; everything is enqueued on
+ * the context's stream, and the only host stop is the read of the two counts.
+ *
+ * Inputs (device): the region table in the caller's row order (= rows of `output`, any order) as d_baitID, d_minOE, d_maxOE
+ * (int32[n]) and d_p (double[n], the chosen pcol, NaN = NA); the peak matrix's rows as read, BEFORE the score filter, as
+ * d_peak_baitID, d_peak_oeID (int32[npeaks]) and d_scores (double[npeaks x ncols], column-major, NaN = NA): the first ncond1
+ * columns are condition 1, the next ncond2 condition 2; merged = 1 (a merged peak matrix) asks for ncond1 = ncond2 = 1.
+ *
+ * Rules, by statement of the reference:
+ *   selection (:2082-2087)   a peak row is selected when some score column is > score and not NA.
+ *   delta (:2118-2124)       |asinh(mean of the cond-1 columns) - asinh(mean of the cond-2 columns)|.  rowMeans has no na.rm: one NA
+ *                            makes delta NA.  Each row sum is formed as a double-double and rounded once, then divided once; R's
+ *                            rowMeans accumulates in long double, and agreement with that 80-bit sum in the last bit is unpinned.
+ *   delta, merged (:2126)    |col2 - col1| with NO asinh — what the reference computes for a merged peak matrix, kept as it is.
+ *   overlap (:2129)          type = "any" on the closed point interval [oe, oe]: peak and region match when baitID is equal and
+ *                            minOE <= oeID <= maxOE.  nomatch = 0: a peak without a region forms no group.
+ *   min_p (:2145)            min(pcol) over the group's regions WITHOUT na.rm: any NaN gives NaN.
+ *   filter (:2161)           min_p <= pvcut & delta >= minDeltaAsinhScore; a NaN on either side drops the group.  The filter runs on
+ *                            the device: only surviving groups get a slot, a CSR entry and pairs.
+ *
+ * Outputs (device): d_group_peak (int32[npeaks]) the peak row of each surviving group, groups in ascending (baitID, oeID) order;
+ * d_group_ptr (int64[npeaks + 1]) CSR offsets into the pairs; d_group_min_p, d_group_delta (double[npeaks]); d_pair_row
+ * (int32[pair_capacity]) rows of the region table, within a group ordered by (minOE, maxOE), ties in order of appearance in the
+ * table (setkey is a stable sort, and foverlaps(mult = "all") returns matches in key order).  *ngroups_host, *npairs_host: how many
+ * entries are written.
+ *
+ * The number of pairs has no a-priori bound (duplicate regions are legal).  When it exceeds pair_capacity the call writes both counts
+ * and everything per group, writes NO pair, and returns CHICDIFF_E_INVALID with a message that names the need: call again with
+ * that much room.
+ *
+ * CHICDIFF_E_INVALID, the message naming the offending row: a region row with minOE > maxOE or an INT32_MIN (NA) key (foverlaps stops
+ * on both); two SELECTED peak rows with the same (baitID, oeID) (the reference would merge them into one group; Chicago's peak
+ * matrix has one row per pair); a selected peak row with baitID = oeID = INT32_MAX.  Also n < 1, n >= 2^31, ncols < 2,
+ * npeaks >= 2^31.  npeaks = 0 or no survivor: CHICDIFF_OK with zero groups (d_group_ptr[0] = 0).
+ * method = "hmp" (harmonicmeanp::p.hmp) is not offered: it stays R. */
+int chicdiff_hip_candidate_interactions_dev(chicdiff_hip_ctx *ctx, const int32_t *d_baitID, const int32_t *d_minOE, const int32_t *d_maxOE,
+                                            const double *d_p, int64_t n, const int32_t *d_peak_baitID, const int32_t *d_peak_oeID,
+                                            const double *d_scores, int64_t npeaks, int32_t ncols, int32_t ncond1, int32_t ncond2,
+                                            int32_t merged, double score, double pvcut, double minDeltaAsinhScore, int64_t pair_capacity,
+                                            int32_t *d_group_peak, int64_t *d_group_ptr, double *d_group_min_p, double *d_group_delta,
+                                            int32_t *d_pair_row, int64_t *ngroups_host, int64_t *npairs_host);
+
 /* a6 + a7 — estimateDispersions + nbinomWaldTest (chicdiff.R:1573-1574, 1602-1603, 1643-1644,
  * 1673-1674) for design ~condition (group[j] in {0,1}, both present) or ~1 (all group[j]==0).
  * d_nf = normalizationFactors (n x S).  `group` is a HOST array of S ints. */
