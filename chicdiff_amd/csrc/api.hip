@@ -59,6 +59,7 @@ struct HostOpts {
     // overflow.  Each verdict is all-reduced, so every rank of a sharded fit must re-enter together.
     int fault_inject = 0;
     int region_assemble_generic = 0;  // test option: every tile of region_assemble takes the generic path
+    int chicago_tables_run_merge = 1;  // chicago_tables: runs of rows with one slot are merged inside the wave before the global atomic
 };
 
 struct chicdiff_hip_ctx {
@@ -216,6 +217,7 @@ static const OptionDef kOptions[] = {
     {"trend_mad_in_kernel", nullptr, &HostOpts::trend_mad_in_kernel, 0, 1, 1, 0},
     {"fuse_offsets", nullptr, &HostOpts::fuse_offsets, 0, 2, 1, 0},
     {"region_assemble_generic", nullptr, &HostOpts::region_assemble_generic, 0, 1, 1, 0},
+    {"chicago_tables_run_merge", nullptr, &HostOpts::chicago_tables_run_merge, 0, 1, 1, 0},
     {"fault_inject", nullptr, &HostOpts::fault_inject, 0, 7, 1, 0},
     {"bench_fake_world", nullptr, &HostOpts::bench_fake_world, 0, kGatherMaxWorld, 1, 0},
     {"local_trend_substitute", nullptr, &HostOpts::local_trend_substitute, 0, 1, 1, 0},
@@ -2020,6 +2022,61 @@ extern "C" int chicdiff_hip_candidate_interactions_dev(chicdiff_hip_ctx *c, cons
     if (h.npairs > pair_capacity)
         return fail(c, CHICDIFF_E_INVALID, "candidate_interactions: room for %lld pairs needed, %lld given (no pair was written)", h.npairs,
                     (long long)pair_capacity);
+    return CHICDIFF_OK;
+}
+
+// The Chicago background tables of one replicate (chicdiff.R:656-692, 538-548): init, two streaming passes and an epilogue behind one
+// another; the one host stop is the read of the status word
+extern "C" int chicdiff_hip_chicago_tables_dev(chicdiff_hip_ctx *c, const int32_t *d_bait, const int32_t *d_oe, const double *d_s_j,
+                                               const double *d_s_i, const double *d_Tmean, const double *d_refBinMean, const int32_t *d_tblb,
+                                               const int32_t *d_tlb, const int32_t *d_distbin, int64_t nrows, int32_t id_min, int32_t nid,
+                                               int32_t ntblb, int32_t ntlb, int32_t ndistbin, double *d_sj, double *d_si, int32_t *d_tblb_of,
+                                               int32_t *d_tlb_of, double *d_T, double *d_ref, int32_t *status_host) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (status_host) *status_host = 0;
+    if (!d_bait || !d_oe || !d_s_j || !d_s_i || !d_Tmean || !d_refBinMean || !d_tblb || !d_tlb || !d_distbin || !d_sj || !d_si || !d_tblb_of ||
+        !d_tlb_of || !d_T || !d_ref || !status_host)
+        return fail(c, CHICDIFF_E_INVALID, "chicago_tables: bad arguments (a NULL pointer)");
+    if (nrows < 1 || nrows >= (1ll << 32))
+        return fail(c, CHICDIFF_E_INVALID, "chicago_tables: nrows = %lld (1 <= nrows < 2^32: the row index is half of a 64-bit atomic word)",
+                    (long long)nrows);
+    if (nid < 1) return fail(c, CHICDIFF_E_INVALID, "chicago_tables: nid = %d (an empty restriction map)", (int)nid);
+    if (ntblb < 1 || ntlb < 1 || (int64_t)ntblb * ntlb > CHICDIFF_CHICAGO_MAX_PAIRS)
+        return fail(c, CHICDIFF_E_INVALID, "chicago_tables: ntblb = %d, ntlb = %d (both >= 1, ntblb * ntlb <= %d: the capacity of the LDS table)",
+                    (int)ntblb, (int)ntlb, CHICDIFF_CHICAGO_MAX_PAIRS);
+    if (ndistbin < 0 || ndistbin > CHICDIFF_CHICAGO_MAX_DISTBIN)
+        return fail(c, CHICDIFF_E_INVALID, "chicago_tables: ndistbin = %d (0 <= ndistbin <= %d: the capacity of the LDS table)", (int)ndistbin,
+                    CHICDIFF_CHICAGO_MAX_DISTBIN);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_aux(c, chicago_workspace_bytes(nid))) return rc;
+    ChicagoArgs a;
+    a.bait = d_bait; a.oe = d_oe; a.s_j = d_s_j; a.s_i = d_s_i; a.Tmean = d_Tmean; a.refBinMean = d_refBinMean;
+    a.tblb = d_tblb; a.tlb = d_tlb; a.distbin = d_distbin; a.nrows = nrows;
+    a.id_min = id_min; a.nid = nid; a.ntblb = ntblb; a.ntlb = ntlb; a.ndistbin = ndistbin;
+    a.sj = d_sj; a.si = d_si; a.tblb_of = d_tblb_of; a.tlb_of = d_tlb_of; a.T = d_T; a.ref = d_ref;
+    const uint32_t *d_status = nullptr;
+    static const char *const stage_name[3] = {"chicago_tables_init", "chicago_tables_pass1", "chicago_tables_pass2"};
+    timing_reset(c);
+    for (int stage = 0; stage < 3; stage++) {
+        Scope t(c, stage_name[stage]);
+        launch_chicago_tables(a, stage, c->host.chicago_tables_run_merge, c->aux, c->stream, &d_status);
+    }
+    HIPCHK(c, hipGetLastError());
+    uint32_t h = 0;
+    HIPCHK(c, hipMemcpyAsync(&h, d_status, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    timing_collect(c);
+    if (h & CHICDIFF_CHICAGO_BAD_CODE)
+        return fail(c, CHICDIFF_E_INVALID, "chicago_tables: a tblb, tlb or distbin code lies outside [-1, %d) / [-1, %d) / [-1, %d)", (int)ntblb,
+                    (int)ntlb, (int)ndistbin);
+    *status_host = (int32_t)(h & CHICDIFF_CHICAGO_NOT_A_FUNCTION);
+    return CHICDIFF_OK;
+}
+
+extern "C" int chicdiff_hip_chicago_tables_caps(int32_t *max_pairs, int32_t *max_distbin, int32_t *rows_per_workgroup) {
+    if (max_pairs) *max_pairs = CHICDIFF_CHICAGO_MAX_PAIRS;
+    if (max_distbin) *max_distbin = CHICDIFF_CHICAGO_MAX_DISTBIN;
+    if (rows_per_workgroup) *rows_per_workgroup = CHICDIFF_CHICAGO_ROWS_PER_WORKGROUP;
     return CHICDIFF_OK;
 }
 

@@ -346,6 +346,19 @@ struct CandResult {
 };
 size_t cand_workspace_bytes(int64_t n, int64_t npeaks);
 int launch_candidates(const CandArgs &a, char *ws, hipStream_t st, const CandResult **res_out);
+// chicago_kernels.hip — the Chicago background tables of one replicate (chicdiff.R:656-692, 538-548)
+struct ChicagoArgs {
+    const int32_t *bait, *oe;                          // one row per observed pair, any order
+    const double *s_j, *s_i, *Tmean, *refBinMean;      // NaN = NA
+    const int32_t *tblb, *tlb, *distbin;               // level codes, -1 = NA
+    int64_t nrows;
+    int32_t id_min, nid, ntblb, ntlb, ndistbin;
+    double *sj, *si;                                   // nid
+    int32_t *tblb_of, *tlb_of;                         // nid
+    double *T, *ref;                                   // ntblb x ntlb; ndistbin + 1
+};
+size_t chicago_workspace_bytes(int32_t nid);
+void launch_chicago_tables(const ChicagoArgs &a, int stage, int merge, char *ws, hipStream_t st, const uint32_t **status_out);
 void launch_math_selftest(int op, const double *x, int64_t n, double *out, hipStream_t st);
 void launch_math3_selftest(int op, const double *x, const double *y, int64_t n, const double *logfact, double *out, double *out2, hipStream_t st);
 // the dispersion objective on its own (disp_kernels.hip, objective_probe_kernel): K points a[i * K + k] per row of a prepared fit

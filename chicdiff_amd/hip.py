@@ -27,7 +27,7 @@ EXPORTS = [
     "chicdiff_hip_offsets_dev", "chicdiff_hip_window_sums_dev", "chicdiff_hip_count_join_dev",
     "chicdiff_hip_fragment_background_dev", "chicdiff_hip_bh_adjust_dev", "chicdiff_hip_ihw_apply_dev",
     "chicdiff_hip_region_universe_count_dev", "chicdiff_hip_region_universe_fill_dev", "chicdiff_hip_region_universe_dev", "chicdiff_hip_count_table_dev",
-    "chicdiff_hip_candidate_interactions_dev",
+    "chicdiff_hip_candidate_interactions_dev", "chicdiff_hip_chicago_tables_dev", "chicdiff_hip_chicago_tables_caps",
     "chicdiff_hip_chinput_read", "chicdiff_hip_chinput_table_dev", "chicdiff_hip_region_avdist_dev",
     "chicdiff_hip_count_join_inner_dev", "chicdiff_hip_count_join_multi_dev", "chicdiff_hip_region_assemble_dev",
     "chicdiff_hip_malloc", "chicdiff_hip_free", "chicdiff_hip_outstanding_allocations", "chicdiff_hip_memcpy_h2d", "chicdiff_hip_memcpy_d2h",
@@ -138,6 +138,9 @@ def load_library() -> C.CDLL:
     L.chicdiff_hip_region_universe_dev.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
     L.chicdiff_hip_candidate_interactions_dev.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, dbl, dbl, dbl, i64,
                                                           vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
+    L.chicdiff_hip_chicago_tables_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp,
+                                                  C.POINTER(i32)]
+    L.chicdiff_hip_chicago_tables_caps.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.chicdiff_hip_nbglm_fit_dev.argtypes = [vp, vp, vp, i64, i32, C.POINTER(i32), C.POINTER(Opts), C.POINTER(Out),
                                              C.POINTER(Scalars)]
     L.chicdiff_hip_nbglm_fit.argtypes = L.chicdiff_hip_nbglm_fit_dev.argtypes
@@ -166,6 +169,14 @@ def default_opts(**kw) -> Opts:
         else:
             setattr(o, k, v)
     return o
+
+
+def chicago_tables_caps() -> dict:
+    """The limits of ``HipContext.chicago_tables`` as the library was built (include/chicdiff_hip.h, CHICDIFF_CHICAGO_*): the most
+    (tblb, tlb) pairs and distbin codes its LDS tables hold, and the consecutive rows a workgroup takes in each pass."""
+    a, b, r = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    load_library().chicdiff_hip_chicago_tables_caps(C.byref(a), C.byref(b), C.byref(r))
+    return dict(max_pairs=a.value, max_distbin=b.value, rows_per_workgroup=r.value)
 
 
 def _scalars_dict(s: Scalars) -> dict:
@@ -602,6 +613,52 @@ class HipContext:
             pairs = pairs.clone()
         return dict(group_peak=gpeak[:g].clone(), group_ptr=gptr[: g + 1].clone(), group_min_p=gmin[:g].clone(), group_delta=gdelta[:g].clone(),
                     pair_row=pairs, ngroups=g, npairs=m)
+
+    # -- the Chicago background tables ----------------------------------------------------------
+    def chicago_tables(self, d_bait, d_oe, d_s_j, d_s_i, d_Tmean, d_refBinMean, d_tblb, d_tlb, d_distbin, id_min, ndistbin,
+                       sj, si, tblb_of, tlb_of, T, ref=None):
+        """The background tables of ONE replicate from the columns of its Chicago table, rows in any order (chicdiff.R:656-692,
+        538-548; the winner rule is above chicdiff_hip_chicago_tables_dev in include/chicdiff_hip.h).  Columns: int32 IDs, float64
+        values (NaN = NA), int32 level codes (-1 = NA), all (nrows,).  Outputs, written in place: ``sj, si`` float64 and
+        ``tblb_of, tlb_of`` int32 (nid,) — row s of the (S, nid) tables ``fragment_background`` takes; ``T`` float64 (ntblb, ntlb).
+        Returns (ref, flag): ``ref`` float64 (ndistbin + 1,), the refBinMean of every distbin code (last entry: the NA code; NaN =
+        none), and whether some code carries two different values — ``ref`` is then not the distance function's input, and the
+        caller builds that replicate's on the host."""
+        torch = self.torch
+        self._check_tensor("d_bait", d_bait, torch.int32, (-1,))
+        n = d_bait.numel()
+        if not 1 <= n < 1 << 32:
+            raise ValueError(f"chicago_tables: 1 <= nrows < 2^32 rows are supported, got {n}")
+        self._check_tensor("d_oe", d_oe, torch.int32, (n,))
+        for name, t in (("d_s_j", d_s_j), ("d_s_i", d_s_i), ("d_Tmean", d_Tmean), ("d_refBinMean", d_refBinMean)):
+            self._check_tensor(name, t, torch.float64, (n,))
+        for name, t in (("d_tblb", d_tblb), ("d_tlb", d_tlb), ("d_distbin", d_distbin)):
+            self._check_tensor(name, t, torch.int32, (n,))
+        self._check_tensor("sj", sj, torch.float64, (-1,))
+        nid = sj.numel()
+        if nid < 1:
+            raise ValueError("sj: empty restriction map")
+        self._check_tensor("si", si, torch.float64, (nid,))
+        self._check_tensor("tblb_of", tblb_of, torch.int32, (nid,))
+        self._check_tensor("tlb_of", tlb_of, torch.int32, (nid,))
+        self._check_tensor("T", T, torch.float64, (-1, -1))
+        caps = chicago_tables_caps()
+        if T.shape[0] < 1 or T.shape[1] < 1 or T.numel() > caps["max_pairs"]:
+            raise ValueError(f"T: shape (ntblb >= 1, ntlb >= 1) with at most {caps['max_pairs']} cells is required, got {tuple(T.shape)}")
+        ndistbin = int(ndistbin)
+        if not 0 <= ndistbin <= caps["max_distbin"]:
+            raise ValueError(f"chicago_tables: 0 <= ndistbin <= {caps['max_distbin']} is required, got {ndistbin}")
+        if ref is None:
+            ref = torch.empty(ndistbin + 1, dtype=torch.float64, device=self.device)
+        self._check_tensor("ref", ref, torch.float64, (ndistbin + 1,))
+        flag = C.c_int32(0)
+        self._check(self.lib.chicdiff_hip_chicago_tables_dev(
+            self.h, d_bait.data_ptr(), d_oe.data_ptr(), d_s_j.data_ptr(), d_s_i.data_ptr(), d_Tmean.data_ptr(), d_refBinMean.data_ptr(),
+            d_tblb.data_ptr(), d_tlb.data_ptr(), d_distbin.data_ptr(), n, int(id_min), nid, T.shape[0], T.shape[1], ndistbin,
+            sj.data_ptr(), si.data_ptr(), tblb_of.data_ptr(), tlb_of.data_ptr(), T.data_ptr(), ref.data_ptr(), C.byref(flag)))
+        kt = self.kernel_times()
+        self.last_chicago_tables_ms = {k[len("chicago_tables_"):]: v[0] for k, v in kt.items() if k.startswith("chicago_tables_")}
+        return ref, bool(flag.value)
 
     # -- a6 + a7 ----------------------------------------------------------------------------
     def nbglm_fit(self, d_counts, d_nf, group, want=None, opts: Opts | None = None, outputs: dict | None = None):

@@ -161,8 +161,15 @@ def chicEstimateDistFun(x, binsize=20000):
     tail by continuity of f and f'.  Returns the ten numbers chicdiff_hip_fragment_background_dev takes."""
     fd = x[["distbin", "refBinMean"]].drop_duplicates().dropna(subset=["refBinMean"])
     fd = fd.sort_values("refBinMean", ascending=False, kind="stable")
-    mid = round(binsize / 2) + binsize * np.arange(len(fd), dtype=np.float64)
-    lm, y = np.log(mid), np.log(fd["refBinMean"].to_numpy(np.float64))
+    return chicEstimateDistFunValues(fd["refBinMean"].to_numpy(np.float64), binsize)
+
+
+def chicEstimateDistFunValues(values, binsize=20000):
+    """The second half of .chicEstimateDistFun (chicdiff.R:549-573) from its first half's result: ``values`` = refBinMean of the
+    distinct (distbin, refBinMean) pairs with a non-NA refBinMean, sorted descending (:543-548)."""
+    values = np.asarray(values, dtype=np.float64)
+    mid = round(binsize / 2) + binsize * np.arange(len(values), dtype=np.float64)
+    lm, y = np.log(mid), np.log(values)
     fit = np.linalg.lstsq(np.stack([np.ones_like(lm), lm, lm ** 2, lm ** 3], axis=1), y, rcond=None)[0]
     ends = np.array([lm.min(), lm.max()])
     beta = fit[1] + 2 * fit[2] * ends + 3 * fit[3] * ends ** 2
@@ -199,6 +206,80 @@ def background_tables(xs, id_min, nid):
     return dict(sj=sj, si=si, tblb=tblb, tlb=tlb, T=T, distfun=distfun, levB=levB, levL=levL)
 
 
+def _column_codes(col):
+    """One label column -> (int32 codes, -1 = NA; the labels the codes index).  A pandas categorical hands over its own codes and
+    categories; any other column is factorised (None / NaN -> -1).  No string is made per row."""
+    import pandas as pd
+    if isinstance(col.dtype, pd.CategoricalDtype):
+        return col.cat.codes.to_numpy(np.int32), list(col.cat.categories)
+    codes, labels = pd.factorize(col, use_na_sentinel=True)
+    return codes.astype(np.int32), list(labels)
+
+
+def chicago_codes(xs):
+    """The three label columns of the S Chicago tables as level codes for chicdiff_hip_chicago_tables_dev.  ``levB`` / ``levL``
+    are background_tables' level lists — the sorted strings of the values some replicate shows — and ``tblb[s]`` / ``tlb[s]``
+    index them; ``distbin[s]`` indexes replicate s's own ``ndistbin[s]`` labels (only equality matters there).  -1 = NA."""
+    out = dict(tblb=[], tlb=[], distbin=[], ndistbin=[])
+    for col, lev_name in (("tblb", "levB"), ("tlb", "levL")):
+        local = [_column_codes(x[col]) for x in xs]
+        seen = [np.unique(c[c >= 0]) for c, _ in local]                          # a categorical may list labels no row shows
+        lev = sorted({str(labels[k]) for (_, labels), ks in zip(local, seen) for k in ks})
+        code = {v: i for i, v in enumerate(lev)}
+        for (c, labels), ks in zip(local, seen):
+            lut = np.full(len(labels) + 1, -1, dtype=np.int32)                   # (the last entry serves the code -1)
+            lut[ks] = [code[str(labels[k])] for k in ks]
+            out[col].append(lut[c])
+        out[lev_name] = lev
+    for x in xs:
+        c, labels = _column_codes(x["distbin"])
+        out["distbin"].append(c)
+        out["ndistbin"].append(len(labels))
+    return out
+
+
+def background_tables_dev(xs, id_min, nid, ctx, id_columns=None):
+    """``background_tables`` on the device (HipContext.chicago_tables, one call per replicate): the same dictionary, bit for bit,
+    with sj, si, tblb, tlb (S, nid) and T (S, ntblb, ntlb) as device tensors and ``distfun`` (S, 10) on the host — the cubic fit
+    (tens of points) runs here on the refBinMean per distbin that the device returns.  ``id_columns``: [(baitID, otherEndID)] per
+    replicate as int32 device tensors, when the caller has uploaded them already.
+    The host twin serves in two cases: a replicate whose refBinMean is not a function of its distbin gets its ``distfun`` row from
+    chicEstimateDistFun (the other tables are unaffected); level counts beyond the library's LDS tables
+    (hip.chicago_tables_caps()) send the whole call to ``background_tables``, uploaded."""
+    from . import hip
+    torch = ctx.torch
+    S = len(xs)
+    dev = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, dtype=t)).to(ctx.device)
+    cd = chicago_codes(xs)
+    levB, levL = cd["levB"], cd["levL"]
+    ntblb, ntlb = max(len(levB), 1), max(len(levL), 1)
+    caps = hip.chicago_tables_caps()
+    if ntblb * ntlb > caps["max_pairs"] or max(cd["ndistbin"]) > caps["max_distbin"]:
+        message("background_tables_dev: ", ntblb, " x ", ntlb, " (tblb, tlb) pairs / ", max(cd["ndistbin"]), " distance bins exceed the "
+                "device tables (", caps["max_pairs"], " / ", caps["max_distbin"], "): building the background tables on the host")
+        bg = background_tables(xs, id_min, nid)
+        for k, t in (("sj", np.float64), ("si", np.float64), ("tblb", np.int32), ("tlb", np.int32), ("T", np.float64)):
+            bg[k] = dev(bg[k], t)
+        return bg
+    sj, si = (torch.empty((S, nid), dtype=torch.float64, device=ctx.device) for _ in range(2))
+    tblb, tlb = (torch.empty((S, nid), dtype=torch.int32, device=ctx.device) for _ in range(2))
+    T = torch.empty((S, ntblb, ntlb), dtype=torch.float64, device=ctx.device)
+    distfun = np.zeros((S, 10))
+    for s, x in enumerate(xs):
+        d_bait, d_oe = id_columns[s] if id_columns is not None else (dev(x["baitID"].to_numpy(), np.int32), dev(x["otherEndID"].to_numpy(), np.int32))
+        val = lambda col: dev(x[col].to_numpy(np.float64), np.float64)
+        ref, flag = ctx.chicago_tables(d_bait, d_oe, val("s_j"), val("s_i"), val("Tmean"), val("refBinMean"), dev(cd["tblb"][s], np.int32),
+                                       dev(cd["tlb"][s], np.int32), dev(cd["distbin"][s], np.int32), id_min, cd["ndistbin"][s],
+                                       sj[s], si[s], tblb[s], tlb[s], T[s])
+        if flag:
+            message("background_tables_dev: refBinMean of data set ", s + 1, " is not a function of distbin: its distance function is estimated on the host")
+            distfun[s] = chicEstimateDistFun(x)
+        else:
+            v = ref.cpu().numpy()
+            distfun[s] = chicEstimateDistFunValues(np.sort(v[~np.isnan(v)])[::-1])
+    return dict(sj=sj, si=si, tblb=tblb, tlb=tlb, T=T, distfun=distfun, levB=levB, levL=levL)
+
+
 def _countput(xs, conditions, rmap):
     """countput, chicdiff.R:708-735 + :754-768: per condition the replicates' observed pairs (non-NA distSign) stacked,
     then Nav = mean(N), Bav = mean(Bmean), score = max(score), the other end's midpoint — what plotDiffBaits() draws."""
@@ -220,14 +301,16 @@ def _countput(xs, conditions, rmap):
     return pd.concat(out, ignore_index=True)
 
 
-def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, read_chicago=None, assemble=False):
+def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, read_chicago=None, assemble=False, device_tables=False):
     """chicdiff.R:1460-1478 with the device path behind it: list(test block, control block, countput).  Every Chicago
     data set and every chinput file is read ONCE for both universes (what ``parallel = TRUE`` -> getFullRegionData2,
     :948-1456, does in the reference; the result does not depend on it).  The long "recast" table (one row per region,
     fragment and sample) is never built: a block holds the per-sample fragment columns N and FullMean on the device in
     (regionID, otherEndID) order, the region offsets, and IHWcorrection()'s per-region avDist.
     ``assemble=True`` (chinput branch only): a block holds the region-level ``regionN`` / ``regionFullMean`` (S, n) that DESeq2Wrap
-    would sum from the fragment columns — from one kernel (HipContext.region_assemble), same bits — and no fragment columns."""
+    would sum from the fragment columns — from one kernel (HipContext.region_assemble), same bits — and no fragment columns.
+    ``device_tables=True``: the Chicago background tables are built on the device (``background_tables_dev``) instead of by pandas
+    and uploaded — same bits; without countData the uploaded ID columns also feed ``ctx.count_table``."""
     s = asChicdiffSettings(chicdiff_settings)
     if assemble and s["countData"] is None:
         raise ValueError("getFullRegionData(assemble=True) covers the chinput branch only: without countData the counts are "
@@ -249,7 +332,13 @@ def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, rea
         message("\nReading Chicago dataset ", i + 1, " of ", S, " : ", names[i])
         x, dispersions[i] = read_chicago(p)
         xs.append(x)
-    bg = background_tables(xs, id_min, nid)
+    d_ids = None
+    if device_tables:
+        if s["countData"] is None:                                                 # the ID columns go up once: here and for count_table below
+            d_ids = [(dev(x["baitID"].to_numpy(), np.int32), dev(x["otherEndID"].to_numpy(), np.int32)) for x in xs]
+        bg = background_tables_dev(xs, id_min, nid, ctx, id_columns=d_ids)
+    else:
+        bg = background_tables(xs, id_min, nid)
     bg.update(id_min=id_min, midsum=midsum)
     message("Saving counts\n")
     countput = _countput(xs, conditions, rmap)
@@ -270,12 +359,13 @@ def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, rea
             tables.append((keys, vals))
     else:                                                                          # chicdiff.R:742-747, 774-807
         message("Reconstructing countData")
-        for x in xs:
-            tables.append(ctx.count_table(dev(x["baitID"].to_numpy(), np.int32), dev(x["otherEndID"].to_numpy(), np.int32),
-                                          dev(x["N"].to_numpy(), np.int32), d_flags))
+        for i, x in enumerate(xs):
+            d_xb, d_xo = d_ids[i] if d_ids is not None else (dev(x["baitID"].to_numpy(), np.int32), dev(x["otherEndID"].to_numpy(), np.int32))
+            tables.append(ctx.count_table(d_xb, d_xo, dev(x["N"].to_numpy(), np.int32), d_flags))
+        d_ids = None
 
     d_midsum, d_chr = dev(midsum, np.int64), dev(chr_codes, np.int32)
-    d_bg = {k: dev(bg[k], t) for k, t in (("sj", np.float64), ("si", np.float64), ("tblb", np.int32), ("tlb", np.int32), ("T", np.float64))}
+    d_bg = {k: bg[k] if device_tables else dev(bg[k], t) for k, t in (("sj", np.float64), ("si", np.float64), ("tblb", np.int32), ("tlb", np.int32), ("T", np.float64))}
     blocks = []
     for u, is_control in zip(universes, (False, True)):
         message("Reading data for significant interactions" if not is_control else "\nReading data for control interactions")

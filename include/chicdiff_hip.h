@@ -117,6 +117,8 @@ int32_t chicdiff_hip_last_refits(const chicdiff_hip_ctx *ctx);
  *                               first kernel for fits of up to 2^18 rows at S <= 16; 0 = always by a launch of their own, 2 = always
  *                               inside (at S <= 16): same bits
  *   "region_assemble_generic"   0 (default) | 1: test option of chicdiff_hip_region_assemble_dev (see there): same bits
+ *   "chicago_tables_run_merge"  1 (default) | 0: chicdiff_hip_chicago_tables_dev merges runs of rows that aim at one fragment's slot inside the
+ *                               wave before the global atomic (tables keyed by bait); 0 = one atomic per row: same bits
  *   "fault_inject"              0 (default) .. 7; test hook, one-shot bits consumed by the next call: 1 = this rank reports a select
  *                               overflow in its next fit, 2 = a grid-barrier timeout of its trend kernel, 4 = an overflow of its
  *                               next size-factor select — to prove that all ranks of a sharded fit refit together
@@ -421,6 +423,44 @@ int chicdiff_hip_candidate_interactions_dev(chicdiff_hip_ctx *ctx, const int32_t
                                             int32_t merged, double score, double pvcut, double minDeltaAsinhScore, int64_t pair_capacity,
                                             int32_t *d_group_peak, int64_t *d_group_ptr, double *d_group_min_p, double *d_group_delta,
                                             int32_t *d_pair_row, int64_t *ngroups_host, int64_t *npairs_host);
+
+/* limits and status bits of chicdiff_hip_chicago_tables_dev (below) */
+#define CHICDIFF_CHICAGO_MAX_PAIRS 1024          /* ntblb * ntlb */
+#define CHICDIFF_CHICAGO_MAX_DISTBIN 1023        /* ndistbin (the NA code makes 1024 entries) */
+#define CHICDIFF_CHICAGO_ROWS_PER_WORKGROUP 4096 /* consecutive rows a workgroup takes in each pass */
+#define CHICDIFF_CHICAGO_NOT_A_FUNCTION 1        /* bits of *status_host */
+#define CHICDIFF_CHICAGO_BAD_CODE 2
+/* The Chicago background tables of ONE replicate (chicdiff.R:656-692 the per-fragment and per-pair tables, 538-548 the input of
+ * .chicEstimateDistFun) from the columns of chicagoData@x, rows r = 0 .. nrows - 1 in ANY order.  No sort.
+ * WINNER RULE: every "first" of the reference follows setkey(x, baitID, otherEndID), a stable sort, and drop_duplicates / unique
+ * keeping the first row, so it is the row that minimises (baitID, otherEndID, r) within its group:
+ *   per bait b       d_sj[b - id_min] = s_j, d_tblb_of[b - id_min] = tblb of the winner among the rows with baitID = b    (:659)
+ *   per other end o  d_si, d_tlb_of likewise among the rows with otherEndID = o                                            (:668)
+ *                    the winner's values are kept even when they are NA; IDs outside [id_min, id_min + nid) are ignored; an
+ *                    ID that no row shows stays NaN / -1
+ *   per (tblb, tlb)  d_T[tblb * ntlb + tlb] = Tmean of the winner among the rows whose two codes are both non-NA (IDs are not
+ *                    filtered here); a pair that no row shows stays NaN                                                    (:678-681)
+ *   per distbin d    d_ref[d] = the refBinMean of the rows with that code and a non-NA refBinMean (an NA distbin is a value of its
+ *                    own: the last entry, d_ref[ndistbin]); NaN = no such row.  The non-NaN entries are the multiset .chicEstimateDistFun
+ *                    sorts and fits (:543-548) exactly when refBinMean is a function of distbin, as Chicago's is.  A code with
+ *                    two different values gets NaN and sets CHICDIFF_CHICAGO_NOT_A_FUNCTION in *status_host (the call still
+ *                    returns CHICDIFF_OK: the caller builds that replicate's distance function on the host)
+ * All of these are minima of integers: the result does not depend on the order of the rows, and equals the host twin
+ * (chicdiff_amd.pipeline.background_tables) bit for bit.
+ * Inputs, device, nrows entries each: d_bait, d_oe (int32); d_s_j, d_s_i, d_Tmean, d_refBinMean (double, NaN = NA); d_tblb, d_tlb,
+ * d_distbin (int32 level codes in [0, ntblb) / [0, ntlb) / [0, ndistbin), -1 = NA).  Outputs, device, filled with NaN / -1 by
+ * the call itself: d_sj, d_si (double), d_tblb_of, d_tlb_of (int32) [nid] — row s of the (S, nid) tables
+ * chicdiff_hip_fragment_background_dev takes; d_T [ntblb * ntlb]; d_ref [ndistbin + 1].
+ * CHICDIFF_E_INVALID, with a message: nrows < 1 or nrows >= 2^32 (the row index is half of a 64-bit atomic word); nid < 1;
+ * ntblb < 1, ntlb < 1 or ntblb * ntlb > CHICDIFF_CHICAGO_MAX_PAIRS, ndistbin < 0 or ndistbin > CHICDIFF_CHICAGO_MAX_DISTBIN (both
+ * tables are kept per workgroup in LDS); a code outside its range (nothing of the outputs is to be used then).
+ * chicdiff_hip_chicago_tables_caps: the three constants below, as the library was built (any pointer may be NULL). */
+int chicdiff_hip_chicago_tables_dev(chicdiff_hip_ctx *ctx, const int32_t *d_bait, const int32_t *d_oe, const double *d_s_j,
+                                    const double *d_s_i, const double *d_Tmean, const double *d_refBinMean, const int32_t *d_tblb,
+                                    const int32_t *d_tlb, const int32_t *d_distbin, int64_t nrows, int32_t id_min, int32_t nid,
+                                    int32_t ntblb, int32_t ntlb, int32_t ndistbin, double *d_sj, double *d_si, int32_t *d_tblb_of,
+                                    int32_t *d_tlb_of, double *d_T, double *d_ref, int32_t *status_host);
+int chicdiff_hip_chicago_tables_caps(int32_t *max_pairs, int32_t *max_distbin, int32_t *rows_per_workgroup);
 
 /* a6 + a7 — estimateDispersions + nbinomWaldTest (chicdiff.R:1573-1574, 1602-1603, 1643-1644,
  * 1673-1674) for design ~condition (group[j] in {0,1}, both present) or ~1 (all group[j]==0).
