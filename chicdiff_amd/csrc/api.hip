@@ -20,6 +20,7 @@
 #include <dlfcn.h>
 
 #include "common.h"
+#include "philox.h"
 #include "prior_mc.h"
 
 using namespace cd;
@@ -1715,10 +1716,10 @@ extern "C" int chicdiff_hip_wald_pvalues_dev(chicdiff_hip_ctx *c, const double *
     return CHICDIFF_OK;
 }
 
-// device-math self test: op 0 flog, 1 tlog (table), 2 rcp, 3 lgamma, 4 digamma, 5 2*pnorm(-|x|), 6 / 7 raw v_rcp_f64 (+ one Newton step), 8 texp (table)
+// device-math self test: op 0 flog, 1 tlog (table), 2 rcp, 3 lgamma, 4 digamma, 5 2*pnorm(-|x|), 6 / 7 raw v_rcp_f64 (+ one Newton step), 8 texp (table), 9 qnorm (AS 241)
 extern "C" int chicdiff_hip_selftest_math_dev(chicdiff_hip_ctx *c, int32_t op, const double *d_x, int64_t n, double *d_out) {
     if (!c) return CHICDIFF_E_INVALID;
-    if (!d_x || !d_out || n < 0 || op < 0 || op > 8) return fail(c, CHICDIFF_E_INVALID, "selftest_math: bad arguments");
+    if (!d_x || !d_out || n < 0 || op < 0 || op > 9) return fail(c, CHICDIFF_E_INVALID, "selftest_math: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     if (n > 0) launch_math_selftest(op, d_x, n, d_out, c->stream);
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2022,6 +2023,77 @@ extern "C" int chicdiff_hip_candidate_interactions_dev(chicdiff_hip_ctx *c, cons
     if (h.npairs > pair_capacity)
         return fail(c, CHICDIFF_E_INVALID, "candidate_interactions: room for %lld pairs needed, %lld given (no pair was written)", h.npairs,
                     (long long)pair_capacity);
+    return CHICDIFF_OK;
+}
+
+// The seeded control draws (chicdiff.R:430-481): contact pass, draws, sort and unpack enqueued behind one another; the one host stop is
+// the read of the counts (and of the refusals, which ride in the same 40 bytes)
+extern "C" int chicdiff_hip_control_draws_dev(chicdiff_hip_ctx *c, const int32_t *d_ru_baitID, int64_t nru, const int64_t *d_region_ptr,
+                                              const int32_t *d_minOE, const int32_t *d_maxOE, int64_t n, const int32_t *d_bmap_id,
+                                              const int32_t *d_bmap_chr, int64_t nb, const int32_t *chr_min, const int32_t *chr_max,
+                                              int32_t nchr, uint64_t seed, int32_t *d_ctrl_baitID, int32_t *d_ctrl_oeID,
+                                              int32_t *d_max_contact, int64_t *n_regions_host, int64_t *m_host) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (n_regions_host) *n_regions_host = 0;
+    if (m_host) *m_host = 0;
+    if (!d_ru_baitID || !d_region_ptr || !d_minOE || !d_maxOE || !d_bmap_id || !d_bmap_chr || !chr_min || !chr_max || !d_ctrl_baitID ||
+        !d_ctrl_oeID || !d_max_contact || !n_regions_host || !m_host || nru < 0)
+        return fail(c, CHICDIFF_E_INVALID, "control_draws: bad arguments (a NULL pointer)");
+    if (n < 1 || n >= (1ll << 31)) return fail(c, CHICDIFF_E_INVALID, "control_draws: n = %lld regions (1 <= n < 2^31)", (long long)n);
+    if (nb < 1 || nb >= (1ll << 31)) return fail(c, CHICDIFF_E_INVALID, "control_draws: nb = %lld baits on the baitmap (1 <= nb < 2^31)", (long long)nb);
+    if (nchr < 1 || nchr > CHICDIFF_CONTROL_MAX_CHR)
+        return fail(c, CHICDIFF_E_INVALID, "control_draws: nchr = %d chromosomes (1 <= nchr <= %d: the capacity of the LDS tables)", (int)nchr,
+                    CHICDIFF_CONTROL_MAX_CHR);
+    // the chromosomes as disjoint ID ranges sorted by their first ID: how the contact pass finds a bait's chromosome
+    std::vector<int32_t> order, lo, hi, code;
+    for (int32_t k = 0; k < nchr; k++)
+        if (chr_min[k] <= chr_max[k]) order.push_back(k);
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return chr_min[a] < chr_min[b]; });
+    for (size_t j = 0; j < order.size(); j++) {
+        const int32_t k = order[j];
+        if (j > 0 && chr_min[k] <= hi.back())
+            return fail(c, CHICDIFF_E_INVALID, "control_draws: the ID ranges of chromosome codes %d [%d, %d] and %d [%d, %d] overlap: a chromosome "
+                        "must be one run of restriction-map IDs", (int)code.back(), (int)lo.back(), (int)hi.back(), (int)k, (int)chr_min[k], (int)chr_max[k]);
+        lo.push_back(chr_min[k]);
+        hi.push_back(chr_max[k]);
+        code.push_back(k);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_aux(c, ctrl_workspace_bytes(n, nchr))) return rc;
+    CtrlArgs a;
+    a.ru_bait = d_ru_baitID; a.nru = nru; a.region_ptr = d_region_ptr; a.minOE = d_minOE; a.maxOE = d_maxOE; a.n = n;
+    a.bmap_id = d_bmap_id; a.bmap_chr = d_bmap_chr; a.nb = nb; a.chr_min = chr_min; a.chr_max = chr_max; a.nchr = nchr; a.seed = seed;
+    a.ctrl_bait = d_ctrl_baitID; a.ctrl_oe = d_ctrl_oeID; a.max_contact = d_max_contact;
+    const CtrlResult *d_res = nullptr;
+    timing_reset(c);
+    {
+        Scope t(c, "control_draws");
+        if (launch_control_draws(a, lo.data(), hi.data(), code.data(), (int)code.size(), c->aux, c->stream, &d_res))
+            return fail(c, CHICDIFF_E_HIP, "control_draws: copy/sort failed");
+    }
+    CtrlResult h;
+    HIPCHK(c, hipMemcpyAsync(&h, d_res, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    timing_collect(c);
+    if (h.bad_region != ~0ull)
+        return fail(c, CHICDIFF_E_INVALID, "control_draws: region_ptr[%llu .. %llu + 1] is not an ascending pair of offsets inside [0, %lld]", h.bad_region,
+                    h.bad_region, (long long)nru);
+    if (h.bad_bait != ~0ull)
+        return fail(c, CHICDIFF_E_INVALID, "control_draws: row %llu of the baitmap has chromosome code >= nchr = %d", h.bad_bait, (int)nchr);
+    if (h.n_regions == 0) return fail(c, CHICDIFF_E_INVALID, "control_draws: RU holds no non-empty region");
+    if (h.cap_k != ~0ull) {  // name the draw: its bait is a function of (seed, k) that the host can restate
+        const Philox4 r = control_draw_words(seed, h.cap_k, 0, 0);
+        const uint64_t idx = (uint64_t)(((unsigned __int128)((uint64_t)r.w[0] | ((uint64_t)r.w[1] << 32)) * (unsigned __int128)(uint64_t)nb) >> 64);
+        int32_t bait = 0, chr = -1;
+        HIPCHK(c, hipMemcpy(&bait, d_bmap_id + idx, sizeof bait, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(&chr, d_bmap_chr + idx, sizeof chr, hipMemcpyDeviceToHost));
+        return fail(c, CHICDIFF_E_INVALID, "control_draws: draw k = %llu (bait %d on chromosome code %d, IDs %d .. %d) found no valid distance in %d "
+                    "attempts: the chromosome leaves this bait no fragment to go to", h.cap_k, (int)bait, (int)chr,
+                    chr >= 0 && chr < nchr ? (int)chr_min[chr] : 0, chr >= 0 && chr < nchr ? (int)chr_max[chr] : 0, CHICDIFF_CONTROL_MAX_ATTEMPTS);
+    }
+    *n_regions_host = (int64_t)h.n_regions;
+    *m_host = (int64_t)h.m;
     return CHICDIFF_OK;
 }
 

@@ -346,6 +346,28 @@ struct CandResult {
 };
 size_t cand_workspace_bytes(int64_t n, int64_t npeaks);
 int launch_candidates(const CandArgs &a, char *ws, hipStream_t st, const CandResult **res_out);
+// control_kernels.hip — the seeded draws of getControlRegionUniverse (chicdiff.R:430-481)
+struct CtrlArgs {
+    const int32_t *ru_bait;               // RU rows in (regionID, otherEndID) order: baitID
+    int64_t nru;
+    const int64_t *region_ptr;            // n + 1 CSR offsets into them
+    const int32_t *minOE, *maxOE;         // per region
+    int64_t n;
+    const int32_t *bmap_id, *bmap_chr;    // the baitmap in file order: ID, chromosome code of the map (-1 = not on it)
+    int64_t nb;
+    const int32_t *chr_min, *chr_max;     // HOST, nchr entries: smallest / largest map ID per chromosome code
+    int32_t nchr;
+    uint64_t seed;
+    int32_t *ctrl_bait, *ctrl_oe;         // n entries each, the first m written
+    int32_t *max_contact;                 // nchr entries, 0 = no contact
+};
+// what the host reads back: the two counts, and the smallest offender of each refusal (all ones = none)
+struct CtrlResult {
+    unsigned long long n_regions, m, bad_bait, bad_region, cap_k;
+};
+size_t ctrl_workspace_bytes(int64_t n, int32_t nchr);
+int launch_control_draws(const CtrlArgs &a, const int32_t *range_lo, const int32_t *range_hi, const int32_t *range_code, int nranges, char *ws,
+                         hipStream_t st, const CtrlResult **res_out);
 // chicago_kernels.hip — the Chicago background tables of one replicate (chicdiff.R:656-692, 538-548)
 struct ChicagoArgs {
     const int32_t *bait, *oe;                          // one row per observed pair, any order

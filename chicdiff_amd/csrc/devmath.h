@@ -60,6 +60,11 @@ __device__ __forceinline__ double flog(double x) {
     return fma(dk, 6.93147180369123816490e-01, -((hfsq - fma(s, hfsq + R, dk * 1.90821492927058770002e-10)) - f));
 }
 
+// flog as a function object: the logarithm that AS 241 (r_rng.h: as241) takes on the device
+struct FlogFn {
+    __device__ __forceinline__ double operator()(double x) const { return flog(x); }
+};
+
 // ---- table-driven log for the hot loops ------------------------------------------------------
 // x = 2^k z, z in [0.6875, 1.375); the top 6 mantissa bits of (bits(x) - OFF) pick c_i ~ z with
 // (1/c_i, log c_i) tabulated (log_table.h); r = z/c_i - 1, |r| <= 1/64, and

@@ -2505,6 +2505,7 @@ __global__ __launch_bounds__(256) void math_selftest_kernel(int op, const double
             case 6: r = __builtin_amdgcn_rcp(v); break;  // raw v_rcp_f64 (~25 bits)
             case 7: { double q = __builtin_amdgcn_rcp(v); r = fma(q, fma(-v, q, 1.0), q); } break;  // + 1 Newton step
             case 8: r = texp(v, s_exptab); break;
+            case 9: r = as241(v, FlogFn()); break;  // qnorm as the control draws call it (control_kernels.hip)
         }
         out[i] = r;
     }

@@ -1,4 +1,4 @@
-// r_rng.h — R's default random number stream (host side, plain C++), as far as DESeq2's estimateDispersionsPriorVar
+// r_rng.h — R's default random number stream (host side), as far as DESeq2's estimateDispersionsPriorVar
 // draws from it after its set.seed(2) (prior_mc.h): Mersenne-Twister with set.seed()'s scrambling, unif_rand(),
 // norm_rand() by inversion, exp_rand() and rgamma().  R is an un-vendored dependency of the reference (SURVEY.md
 // §8c): the algorithms are the published ones R implements, in R's draw order —
@@ -9,10 +9,59 @@
 // Checked against R outputs everybody can reproduce (set.seed(1); runif/rnorm/rexp ...) through
 // chicdiff_hip_r_random() in tests/test_r_rng.py.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 namespace cd {
+
+// Wichura's AS 241 (PPND16), 0 < p < 1, for the host stream below and for device code (control_kernels.hip): ONE statement of the
+// coefficients and of the order of operations.  `lg` supplies the logarithm of the tails (the host's log; flog on the device); the
+// middle, |p - 0.5| <= 0.425, takes only + x / and gives the same bits on both sides under -ffp-contract=off.
+__host__ __device__ inline double as241_horner(const double *c, int n, double r) {  // c[0] r^(n-1) + ... + c[n-1]
+    double v = c[0];
+    for (int k = 1; k < n; k++) v = v * r + c[k];
+    return v;
+}
+struct As241HostLog {
+    double operator()(double x) const { return log(x); }
+};
+template <class Log>
+__host__ __device__ inline double as241(double p, Log lg) {
+    const double A[] = {2509.0809287301226727, 33430.575583588128105, 67265.770927008700853,
+                        45921.953931549871457, 13731.693765509461125, 1971.5909503065514427,
+                        133.14166789178437745, 3.387132872796366608};
+    const double B[] = {5226.495278852545925, 28729.085735721942674, 39307.89580009271061,
+                        21213.794301586595867, 5394.1960214247511077, 687.1870074920579083,
+                        42.313330701600911252, 1.0};
+    const double C[] = {7.7454501427834140764e-4, 0.0227238449892691845833, 0.24178072517745061177,
+                        1.27045825245236838258, 3.64784832476320460504, 5.7694972214606914055,
+                        4.6303378461565452959, 1.42343711074968357734};
+    const double D[] = {1.05075007164441684324e-9, 5.475938084995344946e-4, 0.0151986665636164571966,
+                        0.14810397642748007459, 0.68976733498510000455, 1.6763848301838038494,
+                        2.05319162663775882187, 1.0};
+    const double E[] = {2.01033439929228813265e-7, 2.71155556874348757815e-5, 0.0012426609473880784386,
+                        0.026532189526576123093, 0.29656057182850489123, 1.7848265399172913358,
+                        5.4637849111641143699, 6.6579046435011037772};
+    const double F[] = {2.04426310338993978564e-15, 1.4215117583164458887e-7, 1.8463183175100546818e-5,
+                        7.868691311456132591e-4, 0.0148753612908506148525, 0.13692988092273580531,
+                        0.59983220655588793769, 1.0};
+    const double q = p - 0.5;
+    if (fabs(q) <= 0.425) {
+        const double r = 0.180625 - q * q;
+        return q * as241_horner(A, 8, r) / as241_horner(B, 8, r);
+    }
+    double r = sqrt(-lg(q < 0 ? p : 1.0 - p));
+    double v;
+    if (r <= 5.0) {
+        r -= 1.6;
+        v = as241_horner(C, 8, r) / as241_horner(D, 8, r);
+    } else {
+        r -= 5.0;
+        v = as241_horner(E, 8, r) / as241_horner(F, 8, r);
+    }
+    return q < 0 ? -v : v;
+}
 
 class RStream {
     static constexpr int kN = 624, kM = 397;
@@ -53,46 +102,8 @@ class RStream {
         if (1.0 - x <= 0.0) return 1.0 - half_ulp;
         return x;
     }
-    static double horner(const double *c, int n, double r) {  // c[0] r^(n-1) + ... + c[n-1]
-        double v = c[0];
-        for (int k = 1; k < n; k++) v = v * r + c[k];
-        return v;
-    }
-    static double qnorm(double p) {  // AS 241, 0 < p < 1
-        static const double A[] = {2509.0809287301226727, 33430.575583588128105, 67265.770927008700853,
-                                   45921.953931549871457, 13731.693765509461125, 1971.5909503065514427,
-                                   133.14166789178437745, 3.387132872796366608};
-        static const double B[] = {5226.495278852545925, 28729.085735721942674, 39307.89580009271061,
-                                   21213.794301586595867, 5394.1960214247511077, 687.1870074920579083,
-                                   42.313330701600911252, 1.0};
-        static const double C[] = {7.7454501427834140764e-4, 0.0227238449892691845833, 0.24178072517745061177,
-                                   1.27045825245236838258, 3.64784832476320460504, 5.7694972214606914055,
-                                   4.6303378461565452959, 1.42343711074968357734};
-        static const double D[] = {1.05075007164441684324e-9, 5.475938084995344946e-4, 0.0151986665636164571966,
-                                   0.14810397642748007459, 0.68976733498510000455, 1.6763848301838038494,
-                                   2.05319162663775882187, 1.0};
-        static const double E[] = {2.01033439929228813265e-7, 2.71155556874348757815e-5, 0.0012426609473880784386,
-                                   0.026532189526576123093, 0.29656057182850489123, 1.7848265399172913358,
-                                   5.4637849111641143699, 6.6579046435011037772};
-        static const double F[] = {2.04426310338993978564e-15, 1.4215117583164458887e-7, 1.8463183175100546818e-5,
-                                   7.868691311456132591e-4, 0.0148753612908506148525, 0.13692988092273580531,
-                                   0.59983220655588793769, 1.0};
-        const double q = p - 0.5;
-        if (fabs(q) <= 0.425) {
-            const double r = 0.180625 - q * q;
-            return q * horner(A, 8, r) / horner(B, 8, r);
-        }
-        double r = sqrt(-log(q < 0 ? p : 1.0 - p));
-        double v;
-        if (r <= 5.0) {
-            r -= 1.6;
-            v = horner(C, 8, r) / horner(D, 8, r);
-        } else {
-            r -= 5.0;
-            v = horner(E, 8, r) / horner(F, 8, r);
-        }
-        return q < 0 ? -v : v;
-    }
+    static double horner(const double *c, int n, double r) { return as241_horner(c, n, r); }
+    static double qnorm(double p) { return as241(p, As241HostLog()); }  // AS 241, 0 < p < 1
     double norm() {
         const double big = 134217728.0;  // 2^27
         double u = unif();

@@ -28,6 +28,7 @@ EXPORTS = [
     "chicdiff_hip_fragment_background_dev", "chicdiff_hip_bh_adjust_dev", "chicdiff_hip_ihw_apply_dev",
     "chicdiff_hip_region_universe_count_dev", "chicdiff_hip_region_universe_fill_dev", "chicdiff_hip_region_universe_dev", "chicdiff_hip_count_table_dev",
     "chicdiff_hip_candidate_interactions_dev", "chicdiff_hip_chicago_tables_dev", "chicdiff_hip_chicago_tables_caps",
+    "chicdiff_hip_control_draws_dev",
     "chicdiff_hip_chinput_read", "chicdiff_hip_chinput_table_dev", "chicdiff_hip_region_avdist_dev",
     "chicdiff_hip_count_join_inner_dev", "chicdiff_hip_count_join_multi_dev", "chicdiff_hip_region_assemble_dev",
     "chicdiff_hip_malloc", "chicdiff_hip_free", "chicdiff_hip_outstanding_allocations", "chicdiff_hip_memcpy_h2d", "chicdiff_hip_memcpy_d2h",
@@ -141,6 +142,8 @@ def load_library() -> C.CDLL:
     L.chicdiff_hip_chicago_tables_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp,
                                                   C.POINTER(i32)]
     L.chicdiff_hip_chicago_tables_caps.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.chicdiff_hip_control_draws_dev.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, vp, i64, C.POINTER(i32), C.POINTER(i32), i32, C.c_uint64,
+                                                 vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
     L.chicdiff_hip_nbglm_fit_dev.argtypes = [vp, vp, vp, i64, i32, C.POINTER(i32), C.POINTER(Opts), C.POINTER(Out),
                                              C.POINTER(Scalars)]
     L.chicdiff_hip_nbglm_fit.argtypes = L.chicdiff_hip_nbglm_fit_dev.argtypes
@@ -613,6 +616,48 @@ class HipContext:
             pairs = pairs.clone()
         return dict(group_peak=gpeak[:g].clone(), group_ptr=gptr[: g + 1].clone(), group_min_p=gmin[:g].clone(), group_delta=gdelta[:g].clone(),
                     pair_row=pairs, ngroups=g, npairs=m)
+
+    # -- getControlRegionUniverse: the seeded draws ------------------------------------------------
+    def control_draws(self, d_ru_baitID, d_region_ptr, d_minOE, d_maxOE, d_bmap_id, d_bmap_chr, chr_min, chr_max, seed):
+        """The draws of getControlRegionUniverse from a seed (chicdiff.R:430-481; the rules and the Philox counter layout are above
+        chicdiff_hip_control_draws_dev in include/chicdiff_hip.h).  RU as ``region_universe`` returns it: ``d_ru_baitID`` int32 (nru,)
+        in (regionID, otherEndID) order, ``d_region_ptr`` int64 (n + 1,), ``d_minOE, d_maxOE`` int32 (n,).  The baitmap in file
+        order: ``d_bmap_id, d_bmap_chr`` int32 (nb,) device tensors, the chromosome as a code of the restriction map (-1 = a name
+        not on it); ``chr_min, chr_max``: host arrays, smallest and largest map ID per code; ``seed``: 0 <= seed < 2^64.
+
+        Returns dict(baitID, oeID, max_contact, n_regions, m): the m kept pairs sorted by (baitID, oeID) as int32 device tensors,
+        the largest contact per chromosome code (int32 device tensor, 0 = none) and the number of non-empty regions of RU."""
+        torch = self.torch
+        self._check_tensor("d_ru_baitID", d_ru_baitID, torch.int32, (-1,))
+        self._check_tensor("d_region_ptr", d_region_ptr, torch.int64, (-1,))
+        n = d_region_ptr.numel() - 1
+        if n < 1:
+            raise ValueError("control_draws: region_ptr must hold at least one region (two entries)")
+        self._check_tensor("d_minOE", d_minOE, torch.int32, (n,))
+        self._check_tensor("d_maxOE", d_maxOE, torch.int32, (n,))
+        self._check_tensor("d_bmap_id", d_bmap_id, torch.int32, (-1,))
+        nb = d_bmap_id.numel()
+        if nb < 1:
+            raise ValueError("control_draws: the baitmap is empty (nb = 0)")
+        self._check_tensor("d_bmap_chr", d_bmap_chr, torch.int32, (nb,))
+        lo, hi = (np.ascontiguousarray(a, dtype=np.int32) for a in (chr_min, chr_max))
+        if lo.ndim != 1 or lo.shape != hi.shape or len(lo) < 1:
+            raise ValueError(f"chr_min, chr_max: two vectors of one length >= 1 are required, got shapes {lo.shape} and {hi.shape}")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+            raise ValueError(f"control_draws: seed must be an integer in [0, 2^64), got {seed!r}")
+        bait, oe = (torch.empty(n, dtype=torch.int32, device=self.device) for _ in range(2))
+        contact = torch.empty(len(lo), dtype=torch.int32, device=self.device)
+        n_regions, m = C.c_int64(0), C.c_int64(0)
+        P = C.POINTER(C.c_int32)
+        self._check(self.lib.chicdiff_hip_control_draws_dev(
+            self.h, d_ru_baitID.data_ptr(), d_ru_baitID.numel(), d_region_ptr.data_ptr(), d_minOE.data_ptr(), d_maxOE.data_ptr(), n,
+            d_bmap_id.data_ptr(), d_bmap_chr.data_ptr(), nb, lo.ctypes.data_as(P), hi.ctypes.data_as(P), len(lo), int(seed),
+            bait.data_ptr(), oe.data_ptr(), contact.data_ptr(), C.byref(n_regions), C.byref(m)))
+        self.last_control_draws_ms = self.kernel_times().get("control_draws", (0.0, 0))[0]
+        k = m.value
+        if 2 * k < n:   # (a view would pin the whole n-entry allocation)
+            bait, oe = bait[:k].clone(), oe[:k].clone()
+        return dict(baitID=bait[:k], oeID=oe[:k], max_contact=contact, n_regions=n_regions.value, m=k)
 
     # -- the Chicago background tables ----------------------------------------------------------
     def chicago_tables(self, d_bait, d_oe, d_s_j, d_s_i, d_Tmean, d_refBinMean, d_tblb, d_tlb, d_distbin, id_min, ndistbin,

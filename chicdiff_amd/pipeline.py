@@ -4,7 +4,8 @@ here; the reference's own chicdiffPipeline() needs no change).
 
     chicdiffPipeline(chicdiff.settings)                                         chicdiff.R:301-347
       getRegionUniverse(chicdiff.settings)                                       :369-426   -> device expansion (f4)
-      getControlRegionUniverse(chicdiff.settings, RU)                            :456-511   -> host draws, device expansion
+      getControlRegionUniverse(chicdiff.settings, RU)                            :456-511   -> device expansion; the draws on the host
+                                                                                              from ``rng``, or on the device from ``seed``
       getFullRegionData(chicdiff.settings, RU, RUcontrol, suffix = "")           :1460-1478 -> device blocks, never the long table
       DESeq2Wrap(chicdiff.settings, RU, FullRegionData[[1]])                     :1494      -> chicdiff_amd.deseq2wrap
       DESeq2Wrap(chicdiff.settings, RUcontrol, FullRegionData[[2]], suffix = "Control", theta = attributes(DESeqOut)$theta)
@@ -108,12 +109,48 @@ def getRegionUniverse(chicdiff_settings, ctx, suffix=""):
     return ru
 
 
-def getControlRegionUniverse(chicdiff_settings, RU, ctx, rng=None):
-    """chicdiff.R:456-511: as many control regions as test regions, around random baits at N(0, maxContact / 3) fragment
-    offsets (giveDists / giveOneSeed, :430-449; the reference draws unseeded, so only the distribution is reproduced —
-    pass ``rng`` for a repeatable run), expanded like the test regions."""
+def _control_draws_dev(s, RU, ctx, seed):
+    """The seeded draws on the device (HipContext.control_draws): only the two design files are read here, and their chromosome
+    tables (a few dozen entries) built; no RU row leaves the device.  Returns (baitID, oeID) as int32 device tensors, sorted."""
     import pandas as pd
+    torch = ctx.torch
+    rmap = _read_rmap(s["rmapfile"])
+    bmap = pd.read_csv(s["baitmapfile"], sep=r"\s+", header=None, quotechar='"', engine="python").iloc[:, :4]
+    bmap.columns = ["chr", "start", "end", "ID"]
+    ids = rmap["otherEndID"].to_numpy(np.int64)
+    names, codes = np.unique(rmap["OEchr"].astype(str).to_numpy(), return_inverse=True)
+    chr_min, chr_max = np.full(len(names), np.iinfo(np.int32).max, dtype=np.int64), np.full(len(names), np.iinfo(np.int32).min, dtype=np.int64)
+    np.minimum.at(chr_min, codes, ids)
+    np.maximum.at(chr_max, codes, ids)
+    # the baitmap's own chr column in the map's code space (:468 merges on it); a name the map does not hold gets -1
+    bchr = bmap["chr"].astype(str).to_numpy()
+    pos = np.clip(np.searchsorted(names, bchr), 0, len(names) - 1)
+    bcode = np.where(names[pos] == bchr, pos, -1)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(ctx.device)
+    r = ctx.control_draws(RU["csr_baitID"], RU["region_ptr"], RU["minOE"], RU["maxOE"], dev(bmap["ID"].to_numpy()), dev(bcode),
+                          chr_min, chr_max, seed)
+    if r["m"] == 0:
+        raise ValueError("getControlRegionUniverse: every control draw was dropped (no bait of the baitmap lies on a chromosome with a contact in RU)")
+    return r["baitID"], r["oeID"], rmap
+
+
+def getControlRegionUniverse(chicdiff_settings, RU, ctx, rng=None, seed=None):
+    """chicdiff.R:456-511: as many control regions as test regions, around random baits at N(0, maxContact / 3) fragment
+    offsets (giveDists / giveOneSeed, :430-449; the reference draws unseeded, so only the distribution is reproduced),
+    expanded like the test regions.  ``seed is None``: the draws run on the host from ``rng`` (pass one for a repeatable run).
+    An integer ``seed``: the draws run on the device (chicdiff_hip_control_draws_dev) and the control set is a pure function of
+    (inputs, seed) — a counter-based stream of this project's own, not R's; no RU row is copied to the host.  Give one of the two."""
+    import pandas as pd
+    if rng is not None and seed is not None:
+        raise ValueError("getControlRegionUniverse: give rng (host draws) or seed (device draws), not both")
     s = asChicdiffSettings(chicdiff_settings)
+    if seed is not None:
+        d_bait, d_oe, rmap = _control_draws_dev(s, RU, ctx, seed)
+        ru = RegionUniverse(post.getRegionUniverse(ctx, d_bait, d_oe, s["RUexpand"], rmap["OEchr"].astype(str).to_numpy(), rmap["otherEndID"].to_numpy()))
+        ru["peak_baitID"] = d_bait.cpu().numpy()
+        if s["saveAuxData"]:
+            ru.to_frame().to_csv(f"{s['outprefix']}_ControlRegionUniverse.csv", index=False)
+        return ru
     rng = np.random.default_rng() if rng is None else rng
     rmap = _read_rmap(s["rmapfile"])
     bmap = pd.read_csv(s["baitmapfile"], sep=r"\s+", header=None, quotechar='"', engine="python").iloc[:, :4]
@@ -459,8 +496,10 @@ def IHWcorrection(chicdiff_settings, DESeqOut, FullRegionData, DESeqOutControl, 
     return out
 
 
-def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, rng=None, assemble=False):
-    """chicdiff.R:301-347, same stage order and messages.  ``assemble``: passed to getFullRegionData."""
+def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, rng=None, assemble=False, control_seed=None):
+    """chicdiff.R:301-347, same stage order and messages.  ``assemble``: passed to getFullRegionData.  ``control_seed``: the control
+    regions are drawn on the device from this seed (getControlRegionUniverse(seed=...)) instead of on the host from ``rng``, which
+    then serves IHWcorrection's columns alone."""
     from . import hip
     from .settings import hipDevice
     own = ctx is None
@@ -471,7 +510,7 @@ def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, r
         message("\n*** Running getRegionUniverse\n")
         RU = getRegionUniverse(chicdiff_settings, ctx)
         message("\n*** Running getControlRegionUniverse\n")
-        RUcontrol = getControlRegionUniverse(chicdiff_settings, RU, ctx, rng=rng)
+        RUcontrol = getControlRegionUniverse(chicdiff_settings, RU, ctx, rng=rng if control_seed is None else None, seed=control_seed)
         message("\n*** Running getFullRegionData\n")
         FullRegionData = getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=ctx, read_chicago=read_chicago,
                                            assemble=assemble)

@@ -32,11 +32,23 @@ def rmap_chr_codes(rmap_chr, rmap_id):
 def getRegionUniverse(ctx, baitID, oeID, RUexpand, rmap_chr, rmap_id):
     """Window-mode region universe.  Returns a dict of device tensors: ``baitID, regionID, otherEndID`` in RU.DT's
     order (keyed by baitID after otherEndID, chicdiff.R:389/:393), plus the region-major CSR view
-    (``region_ptr, minOE, maxOE`` and ``csr_*`` rows) that the window sums consume."""
+    (``region_ptr, minOE, maxOE`` and ``csr_*`` rows) that the window sums consume.  ``baitID`` / ``oeID``: arrays, or int32
+    tensors already on the context's device (the seeded control draws), which are used as they are."""
     torch = ctx.torch
     chr_of, _ = rmap_chr_codes(rmap_chr, rmap_id)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(ctx.device)
-    r = ctx.region_universe(dev(baitID), dev(oeID), int(RUexpand), dev(chr_of))
+
+    def peaks(name, a):
+        if not torch.is_tensor(a):
+            return dev(a)
+        if a.dtype != torch.int32 or a.device != ctx.device or a.dim() != 1:
+            raise ValueError(f"{name}: a tensor must be a one-dimensional int32 tensor on {ctx.device}, got {a.dtype} {tuple(a.shape)} on {a.device}")
+        return a.contiguous()
+
+    d_bait, d_oe = peaks("baitID", baitID), peaks("oeID", oeID)
+    if d_bait.numel() != d_oe.numel():
+        raise ValueError(f"baitID and oeID: one entry per peak each, got {d_bait.numel()} and {d_oe.numel()}")
+    r = ctx.region_universe(d_bait, d_oe, int(RUexpand), dev(chr_of))
     # setkey(otherEndID) then setkey(baitID): two stable sorts of the (regionID, otherEndID)-ordered rows
     o1 = torch.sort(r["otherEndID"], stable=True).indices
     o2 = o1[torch.sort(r["baitID"][o1], stable=True).indices]

@@ -424,6 +424,53 @@ int chicdiff_hip_candidate_interactions_dev(chicdiff_hip_ctx *ctx, const int32_t
                                             int32_t *d_group_peak, int64_t *d_group_ptr, double *d_group_min_p, double *d_group_delta,
                                             int32_t *d_pair_row, int64_t *ngroups_host, int64_t *npairs_host);
 
+/* limits of chicdiff_hip_control_draws_dev (below) */
+#define CHICDIFF_CONTROL_MAX_CHR 1024     /* chromosome codes: the per-chromosome tables are kept per workgroup in LDS */
+#define CHICDIFF_CONTROL_MAX_ATTEMPTS 256 /* redraws of one distance before the call gives up */
+/* The draws of getControlRegionUniverse (chicdiff.R:430-481) from a 64-bit seed: as many control (baitID, oeID) pairs as RU has
+ * non-empty regions, sorted, ready for chicdiff_hip_region_universe_dev (the expansion of :483-504 is that call, unchanged).  The
+ * reference draws from R's unseeded stream; here the pairs are a pure function of (inputs, seed) — the same on every run, launch
+ * shape and number of ranks.  The stream is this library's own, not R's: set.seed() is not reproduced.  Everything is enqueued on
+ * the context's stream; the one host stop is the read of the counts.
+ *
+ * Random words: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85), key = (seed & 0xffffffff,
+ * seed >> 32), counter = (k & 0xffffffff, k >> 32, attempt, stream) for draw k = 0 .. n_regions - 1; (r0, r1, ..) = its output.
+ *
+ * Rules, by statement of the reference:
+ *   n_regions (:466)          length(unique(RU$regionID)): the regions i with d_region_ptr[i + 1] > d_region_ptr[i].
+ *   max_contact (:463-464)    max |baitID - otherEndID| over the RU rows whose bait lies on chromosome c.  A region's rows lie in
+ *                             [minOE, maxOE] on one side of its bait (.expandAvoidBait, :353-367), so this is computed as
+ *                             max(|bait - minOE|, |bait - maxOE|) over the non-empty regions, bait = d_ru_baitID[d_region_ptr[i]].  The
+ *                             bait's chromosome is the one whose [chr_min, chr_max] holds it; an ID in no range is not on the map and
+ *                             its rows drop out (the inner merge of :463).  d_max_contact[c] = 0: no contact.
+ *   bait (:466-468)           stream 0, attempt 0: idx = high 64 bits of ((r0 | r1 << 32) * nb), bait = d_bmap_id[idx] (file order).  The
+ *                             draw is DROPPED when d_bmap_chr[idx] is -1 (a name not on the map) or a chromosome without a contact:
+ *                             merge(bmap[chr %in% max_contacts$chr], ..).  The control set may be smaller than the test set.
+ *   std, min, max (:472-474)  max_contact[c] / 3.0 in double; chr_min[c], chr_max[c].
+ *   distance (:434-444)       stream 1, attempts 0, 1, 2, ..: u = ((r0 >> 6) * 2^26 + (r1 >> 6) + 0.5) * 2^-52, exact, inside
+ *                             [2^-53, 1 - 2^-53]; z = qnorm(u) by Wichura's AS 241 (PPND16); d = rint(z * std), ties to even (R's
+ *                             round()); accepted when d != 0 and (bait + |d| < max or bait - |d| > min) — strict, as giveDists.
+ *   seed of the region        fwd = bait + d; oeID = bait - d when fwd < min or fwd > max, else fwd — not strict, as giveOneSeed
+ *   (:430-432)
+ *   order (:480-481)          the kept pairs ascending by (baitID, oeID); regionID = 1 .. m by position.  Equal pairs are legal.
+ *
+ * Inputs: RU as chicdiff_hip_region_universe_dev left it — d_ru_baitID (int32[nru], rows in (regionID, otherEndID) order),
+ * d_region_ptr (int64[n + 1]), d_minOE, d_maxOE (int32[n]); the baitmap d_bmap_id, d_bmap_chr (int32[nb], device; the chromosome as a
+ * code of the restriction map, coded on the host); chr_min, chr_max (HOST, int32[nchr]): smallest and largest map ID per code
+ * (min > max: a code without fragments).  The ranges must not overlap.
+ * Outputs (device): d_ctrl_baitID, d_ctrl_oeID (int32, room for n, the first *m_host written); d_max_contact (int32[nchr]);
+ * *n_regions_host, *m_host.
+ * CHICDIFF_E_INVALID, with a message: n < 1 or nb < 1; nchr < 1 or nchr > CHICDIFF_CONTROL_MAX_CHR; overlapping ranges; a
+ * d_region_ptr entry outside [0, nru] or descending; a bait of the baitmap with code >= nchr; no non-empty region; a distance still
+ * rejected after CHICDIFF_CONTROL_MAX_ATTEMPTS attempts (the message names k, the bait and its chromosome code; the reference
+ * would loop forever — only a chromosome that leaves a bait no valid distance gets there).  No chromosome with a contact, or every
+ * draw dropped: CHICDIFF_OK with *m_host = 0. */
+int chicdiff_hip_control_draws_dev(chicdiff_hip_ctx *ctx, const int32_t *d_ru_baitID, int64_t nru, const int64_t *d_region_ptr,
+                                   const int32_t *d_minOE, const int32_t *d_maxOE, int64_t n, const int32_t *d_bmap_id,
+                                   const int32_t *d_bmap_chr, int64_t nb, const int32_t *chr_min, const int32_t *chr_max, int32_t nchr,
+                                   uint64_t seed, int32_t *d_ctrl_baitID, int32_t *d_ctrl_oeID, int32_t *d_max_contact,
+                                   int64_t *n_regions_host, int64_t *m_host);
+
 /* limits and status bits of chicdiff_hip_chicago_tables_dev (below) */
 #define CHICDIFF_CHICAGO_MAX_PAIRS 1024          /* ntblb * ntlb */
 #define CHICDIFF_CHICAGO_MAX_DISTBIN 1023        /* ndistbin (the NA code makes 1024 entries) */
@@ -492,7 +539,8 @@ int chicdiff_hip_theta_grid_dev(chicdiff_hip_ctx *ctx, const int32_t *d_counts, 
 int chicdiff_hip_wald_pvalues_dev(chicdiff_hip_ctx *ctx, const double *d_stat, int64_t n, double *d_p);
 
 /* Device-math self test: out[i] = f(x[i]) with op 0 log (polynomial), 1 log (table), 2 reciprocal,
- * 3 lgamma, 4 digamma, 5 2*pnorm(-|x|), 8 exp (table) — the special functions the fit kernels are built on. */
+ * 3 lgamma, 4 digamma, 5 2*pnorm(-|x|), 8 exp (table) — the special functions the fit kernels are built on —, 9 qnorm (AS 241
+ * with the polynomial log in its tails, 0 < x < 1), as chicdiff_hip_control_draws_dev calls it. */
 int chicdiff_hip_selftest_math_dev(chicdiff_hip_ctx *ctx, int32_t op, const double *d_x, int64_t n, double *d_out);
 /* The same for the functions of two arguments / two results that carry the dispersion objective, the constant part of the NB
  * log-likelihood and the reported deviance, each called as the kernels call it; y[i] is an integer count held in a double:
