@@ -49,6 +49,7 @@ struct HostOpts {
     int trend_mad_in_kernel = 1;   // the persistent trend kernel also takes the median / MAD of the residuals (0: separate launches)
     int local_trend_substitute = 1;  // 0: a failed parametric trend is reported (CHICDIFF_ST_TREND_FAILED), not replaced by the local fit
     int fuse_offsets = 1;  // 0 = offsets always as a launch of their own, 2 = always inside prep: the bit-identity test
+    int prep_blocks = 0;   // test handle: at most this many workgroups for prep16_kernel (0 = one resident round), so that small fits run several tiles per workgroup
     int theta_grid_concurrency = 5;  // theta grid: fits in flight at once (1 = one after the other)
     int host_copy_threads = 12;      // host threads that move caller buffers to / from the pinned staging area
     // bench hook (a 1-rank communicator only): the trend's rows are gathered as if N ranks had each sent this rank's block — the
@@ -143,7 +144,6 @@ struct chicdiff_hip_ctx {
 };
 
 static char g_create_err[512];
-constexpr int64_t kFuseOffsetsMaxRows = 1 << 18;  // fits up to this many rows form their offsets inside prep (see form_offsets)
 
 // simulated residual densities + loess operator of one d.f. (prior_mc.h): constants, built once per process
 static const PmcTable &pmc_table(int df) {
@@ -217,6 +217,7 @@ static const OptionDef kOptions[] = {
     {"trend_persistent_blocks", &Opts::trend_blocks, nullptr, 0, 256, 1, 0},
     {"trend_mad_in_kernel", nullptr, &HostOpts::trend_mad_in_kernel, 0, 1, 1, 0},
     {"fuse_offsets", nullptr, &HostOpts::fuse_offsets, 0, 2, 1, 0},
+    {"prep_blocks", nullptr, &HostOpts::prep_blocks, 0, kRedBlocks, 1, 0},
     {"region_assemble_generic", nullptr, &HostOpts::region_assemble_generic, 0, 1, 1, 0},
     {"chicago_tables_run_merge", nullptr, &HostOpts::chicago_tables_run_merge, 0, 1, 1, 0},
     {"fault_inject", nullptr, &HostOpts::fault_inject, 0, 7, 1, 0},
@@ -1047,8 +1048,8 @@ static int fit_pass(chicdiff_hip_ctx *c, const int32_t *d_counts, const double *
     {
         Scope t(c, "prep");
         const bool fused = c->fuse.fm != nullptr && d.S <= 16 && d_nf == c->d_nf_tmp;
-        launch_prep(d_counts, const_cast<double *>(d_nf), d, w, o, st, fused ? c->fuse : FusedOffsets());
-        launch_prep_finish(d, w, col_slots ? slots + slot_doubles * c->rank : nullptr, st);
+        const int nblk = launch_prep(d_counts, const_cast<double *>(d_nf), d, w, o, st, fused ? c->fuse : FusedOffsets(), c->host.prep_blocks);
+        launch_prep_finish(d, w, nblk, col_slots ? slots + slot_doubles * c->rank : nullptr, st);
     }
     if (col_slots) {
         if ((rc = do_allreduce(c, slots, (int64_t)(slot_doubles * world)))) return rc;
@@ -1263,11 +1264,19 @@ static int begin_call(chicdiff_hip_ctx *c, int rc, int64_t n, int32_t S) {
 }
 
 // The offsets of the fit that c is about to make on c->d_nf_tmp: formed from FullMean inside the fit's first kernel (c->fuse; the
-// caller clears it when the fit returns) where a launch is worth more than the arithmetic, else by a launch of their own.  Measured
-// (round 5), offsets + prep against the fused prep: 18.5 + 28 -> 47 us at 250 k x 8 (and one launch, ~5 us + its gap, less), 30 + 40 ->
-// 76 at 500 k, 67 + 130 -> 291 at 2 M (the fused kernel carries 2 S logarithms per row at the four waves per SIMD its LDS tiles allow)
+// caller clears it when the fit returns), else by a launch of their own.  Inside, the nf matrix is written once and not read straight
+// back (2 M x 8: 658 MB moved instead of 786), and a launch goes.  Rounds 5-17 kept that to fits of <= 2^18 rows, because at 2 M x 8
+// the fused kernel took 283 us against 75 + 133 for the pair; the reasons were in the kernel, not in the idea (disp_kernels.hip,
+// prep16_kernel): register arrays of 16 samples whatever S (157 registers: three workgroups per CU resident, so the 1024 of the grid
+// ran as a round and a quarter), and the size factors read by 2 S vector loads per tile, each waited for on its own.  Measured since
+// (round 18, one MI355X, kernel times of five steps, fused | offsets + prep of the same build): 30 k x 4 13.9 | 6.3 + 12.0 us,
+// 250 k x 8 25.2 | 12.3 + 19.7, 1 M x 8 83.1 | 33.0 + 57.5, 2 M x 4 115.8 | 32.2 + 93.5, 2 M x 8 146.6 | 54.0 + 107.0,
+// 2 M x 16 309.4 | 116.2 + 214.8 — ahead at every shape, outside the runs' spread, before the launch saved is counted
+// (profiles/r18_routes_kernel_times.txt).
+// So the rule is: inside wherever the fused kernel exists (S <= 16).  fuse_offsets = 0 keeps the pair (the bit-identity tests).
+static bool fused_offsets_win(int64_t, int32_t S) { return S <= 16; }
 static void form_offsets(chicdiff_hip_ctx *c, const double *d_fullMean, int64_t n, int32_t S, double theta, int mix) {
-    if (d_fullMean && S <= 16 && c->host.fuse_offsets && (c->host.fuse_offsets == 2 || n <= kFuseOffsetsMaxRows)) {
+    if (d_fullMean && S <= 16 && c->host.fuse_offsets && (c->host.fuse_offsets == 2 || fused_offsets_win(n, S))) {
         c->fuse.fm = d_fullMean;
         c->fuse.sf = c->d_sf;
         c->fuse.theta = theta;

@@ -187,8 +187,9 @@ __device__ __forceinline__ void class_peers(int c, bool valid, int lane, unsigne
 // function offsets16_kernel runs — written to `nf` (the stages behind read them from there) and used at once: one read and one
 // launch less than offsets + prep (round 5)
 struct FusedOffsets { const double *fm = nullptr; const double *sf = nullptr; double theta = 0; int mix = 0; };
-void launch_prep(const int32_t *counts, double *nf, FitDims d, FitWork w, Opts o, hipStream_t st, FusedOffsets fo = FusedOffsets());
-void launch_prep_finish(FitDims d, FitWork w, double *slot, hipStream_t st);  // partials -> colsum, nnz (slot: as (hi, lo) pairs into this rank's slot instead)
+// -> the blocks whose partial column sums exist (launch_prep_finish's nblk); max_blocks > 0 caps the workgroups at S <= 16 (option "prep_blocks")
+int launch_prep(const int32_t *counts, double *nf, FitDims d, FitWork w, Opts o, hipStream_t st, FusedOffsets fo = FusedOffsets(), int max_blocks = 0);
+void launch_prep_finish(FitDims d, FitWork w, int nblk, double *slot, hipStream_t st);  // partials -> colsum, nnz (slot: as (hi, lo) pairs into this rank's slot instead)
 void launch_xim(FitDims d, FitWork w, const double *slots, int world, hipStream_t st);  // (the ranks' slots ->) colsum -> xim
 void launch_disp_gene(const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o, hipStream_t st);
 void launch_order_build(FitDims d, FitWork w, int classesA, bool have_hist, hipStream_t st, bool fine = false);  // w.cls -> w.order (schedule of a row-queue kernel; fine: kSchedClassesFine classes)

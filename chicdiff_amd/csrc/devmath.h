@@ -351,25 +351,28 @@ __device__ __forceinline__ double pnorm_two_sided(double z) {
 __device__ __forceinline__ double rlog_t(double x, const LogEntry *lt) { return (x > 2.3e-308 && x < 1.7e308) ? tlog(x, lt) : log(x); }
 // a4 — one row of the offsets (chicdiff.R:1583-1589 M3, :1635-1638 / :1666-1669 the theta mix): v[0..S) = FullMean in, the
 // normalisation factors out.  Shared by offsets16_kernel and by prep16_kernel's fused form (global_kernels.hip / disp_kernels.hip),
-// so that the two produce the same bits.  S <= 16; sf: the size factors (nullSizeFactors), wave-uniform loads.
-__device__ __forceinline__ void offsets_row16(double (&v)[16], int S, const double *__restrict__ sf, double theta, int mix, const LogEntry *lt) {
+// so that the two produce the same bits.  S <= N <= 16; sf: the size factors (nullSizeFactors), wave-uniform loads.  N (4, 8 or 16) is
+// the length of the register array, the sample class of the launch: the operations on the samples j < S and their order are the
+// same for every N, so a row gets the same bits from every class that holds it — a shorter array only frees registers.
+template <int N>
+__device__ __forceinline__ void offsets_row16(double (&v)[N], int S, const double *__restrict__ sf, double theta, int mix, const LogEntry *lt) {
     const double iS = 1.0 / S;
     double sl = 0;
 #pragma unroll
-    for (int j = 0; j < 16; j++)
+    for (int j = 0; j < N; j++)
         if (j < S) sl += rlog_t(v[j], lt);
     const double gmean = exp(sl * iS);
     const double ig = (gmean > 1e-300 && gmean < 1e300) ? rcp(gmean) : 1.0 / gmean;
     bool anyna = false;
 #pragma unroll
-    for (int j = 0; j < 16; j++)
+    for (int j = 0; j < N; j++)
         if (j < S) {
             v[j] = v[j] * ig;
             anyna |= (v[j] != v[j]);
         }
     double sl2 = 0;
 #pragma unroll
-    for (int j = 0; j < 16; j++)
+    for (int j = 0; j < N; j++)
         if (j < S) {
             if (anyna) v[j] = sf[j];
             if (mix) {
@@ -381,7 +384,7 @@ __device__ __forceinline__ void offsets_row16(double (&v)[16], int S, const doub
         const double g2 = exp(sl2 * iS);
         const double i2 = (g2 > 1e-300 && g2 < 1e300) ? rcp(g2) : 1.0 / g2;
 #pragma unroll
-        for (int j = 0; j < 16; j++)
+        for (int j = 0; j < N; j++)
             if (j < S) v[j] = v[j] * i2;
     }
 }

@@ -75,20 +75,49 @@ __device__ __forceinline__ void prep_store(FitDims d, FitWork w, int64_t i, doub
     w.allZero[i] = (tot == 0);
 }
 
+// Row i of the sample-major matrix src into v[0..S).  No branch per sample and none per lane: N loads in a row, with nothing between
+// them for the compiler to wait at (a load under `j < S && i < n` is a block of its own, and the blocks' joins got vmcnt(0) waits that
+// drained the loads there and then).  Instead the address is clamped into the matrix — a lane past the last row reads row 0, a slot
+// past the last sample reads the last sample again (a line the lane has just asked for) — and what such a load returns is never
+// used: every use of v[j] is under j < S, every use of the row under i < n.  No address outside the matrix is ever formed.
+template <int N, typename V>
+__device__ __forceinline__ void prep16_load(const V *__restrict__ src, int64_t n, int S, int64_t i, V (&v)[N]) {
+    const int64_t ii = i < n ? i : 0;
+#pragma unroll
+    for (int j = 0; j < N; j++) v[j] = src[(int64_t)(j < S ? j : S - 1) * n + ii];
+}
+
 // S <= 16: the row's q_j live in registers — one read of counts and offsets, one division per sample.  The same pass writes
 // FitWork::rowpack, the row-major copy the row-queue kernels read (a row = 12 S contiguous bytes): the block's 256 rows go
 // through an LDS tile (row pitch + 1 dword: conflict-free both ways) and leave as one contiguous run of 16-byte stores.
 // (Measured, 2 M x 8: with every thread storing its own row straight to global memory — 16 partial-line stores per row — the
 // pass took 0.47 ms instead of 0.12; through the tile it is 0.19 ms, and the three row-queue kernels gain 0.46 ms.)
-template <bool FUSED>
-__global__ __launch_bounds__(256) void prep16_kernel(const int32_t *__restrict__ counts,
-                                                     double *__restrict__ nf, FitDims d, FitWork w, FusedOffsets fo) {
+// N: the sample class of the launch (S <= N: 4, 8 or 16, picked as sf_hist_kernel's) — the length of the row's register arrays and of
+// the unrolled sample loops.  The operations on the samples j < S and their order do not depend on it: same bits from every class.
+// S > 8 is the class whose rows are longer than 128 bytes: its tiles are 128 rows, the others' 256 (launch_prep), so T is a constant.
+// The launch bound is the residency the LDS tiles allow — four workgroups per CU, i.e. four waves per SIMD at 256 threads (128
+// registers), two at 128 — and what prep16_blocks sizes the grid by; the build's resource report shows no instance spilling to scratch
+// under it.
+// A workgroup walks its tiles one after the other, and a tile ends in a barrier, the stores of the record, the column sums and a
+// one-wave merge behind two more barriers: the loads of the workgroup's NEXT tile (nf and the counts, 3 N registers; fused: FullMean
+// alone, 2 N) are issued before all that, so they are in flight across it (plain global loads are not drained by the barrier) instead
+// of starting when it is over (prep16_load: addresses clamped into the matrix).
+template <bool FUSED, int N>
+__global__ __launch_bounds__(N == 16 ? 128 : 256, N == 16 ? 2 : 4) void prep16_kernel(const int32_t *__restrict__ counts,
+                                                                                      double *__restrict__ nf, FitDims d, FitWork w, FusedOffsets fo) {
     __shared__ LogEntry s_lt[FUSED ? 64 : 1];
-    if (FUSED) log_table_to_lds(s_lt);
-    extern __shared__ uint32_t s_tile[];  // T rows x (stride / 4 + 1) dwords, T = blockDim.x (256, or 128 when a row is longer than 128 bytes)
+    // the size factors, once per workgroup: read through fo.sf (a pointer inside a by-value struct, so not known to be read-only) they
+    // were 2 S vector loads per tile, inside offsets_row16's per-lane branches and each waited for with vmcnt(0) — 2 S serial round
+    // trips to L2 per tile, behind the previous tile's stores (offsets16_kernel, whose sf is a __restrict__ argument, gets scalar loads)
+    __shared__ double s_sf[FUSED ? 16 : 1];
+    if (FUSED) {
+        if ((int)threadIdx.x < d.S) s_sf[threadIdx.x] = fo.sf[threadIdx.x];
+        log_table_to_lds(s_lt);  // (ends with the barrier)
+    }
+    extern __shared__ uint32_t s_tile[];  // T rows x (stride / 4 + 1) dwords
     __shared__ DD s_part[256];            // column sums of the tile by row group: [group][column]
     __shared__ unsigned char s_live[256]; // row of the tile is not all zero
-    const int T = blockDim.x;
+    constexpr int T = N == 16 ? 128 : 256;
     const int64_t n = d.n;
     const int S = d.S;
     const int64_t stride = row_stride(S);
@@ -96,42 +125,48 @@ __global__ __launch_bounds__(256) void prep16_kernel(const int32_t *__restrict__
     const int tid = threadIdx.x;
     // column sums of nf over the non-all-zero rows + their number (momentsDispEstimate's xim): the tile holds the values anyway.
     // Thread (group g, column c) adds the rows g, g + G, ... of column c; thread c then adds the G group sums in order: fixed order
-    const int ncol = S + 1, G = T / ncol, cg = tid / ncol, cc = tid % ncol;
-    DD colacc{0.0, 0.0};  // threads 0..S: this block's sum of column tid (column S counts the rows)
-    for (int64_t base = (int64_t)blockIdx.x * T; base < n; base += (int64_t)gridDim.x * T) {
+    const int ncol = S + 1, G = T / ncol;
+    __shared__ DD s_col[17];  // this block's sum of column c (column S counts the rows), kept by thread c: in LDS, not in two register pairs of every thread
+    if (tid < ncol) s_col[tid] = DD{0.0, 0.0};
+    const double *__restrict__ src = FUSED ? fo.fm : nf;  // what the offsets come from: FullMean, or the caller's nf
+    int32_t kv[N];  // this tile's row as loaded: counts ...
+    double fv[N];   // ... and FullMean (fused: the normalisation factors once offsets_row16 has run) or nf
+    uint32_t *row = s_tile + tid * ldw;
+    row[7] = 0;                                                        // second half of the header: the count profile (three words, below) + one spare
+    for (int k = 8 + 3 * S; k < (int)(stride / 4); k++) row[k] = 0;  // the pad behind the row.  Both once, not per tile: no tile writes them again
+    int64_t base = (int64_t)blockIdx.x * T;
+    prep16_load<N>(src, n, S, base + tid, fv);
+    if (!FUSED) prep16_load<N>(counts, n, S, base + tid, kv);
+    while (base < n) {
         const int64_t i = base + tid;
+        const int64_t next = base + (int64_t)gridDim.x * T;
         const int nrows = n - base < T ? (int)(n - base) : T;
         if (i < n) {
-            double q[16];
+            double q[N];
             double s = 0, g0 = 0, g1 = 0;
-            int64_t tot = 0;
-            int32_t sign = 0;
+            int32_t sign = 0;  // OR of the counts: negative if one is (NA_integer_ too), zero if and only if the row is all zero — no 64-bit total beside it
             CountProfile cprof;
-            uint32_t *row = s_tile + tid * ldw;
-            row[7] = 0;                                                        // second half of the header: the count profile (three words, below) + one spare
-            for (int k = 8 + 3 * S; k < (int)(stride / 4); k++) row[k] = 0;  // the pad behind the row
-            double fv[16];
             if (FUSED) {  // the row's normalisation factors from FullMean (offsets_row16: the function offsets16_kernel runs)
+                offsets_row16<N>(fv, S, s_sf, fo.theta, fo.mix, s_lt);
+                // (fused: the counts only now, in front of the stores — held across offsets_row16 their N registers push the S <= 8
+                // instance past the 128 of the launch bound, into scratch)
+                prep16_load<N>(counts, n, S, i, kv);
 #pragma unroll
-                for (int j = 0; j < 16; j++) fv[j] = j < S ? fo.fm[(int64_t)j * n + i] : 1.0;
-                offsets_row16(fv, S, fo.sf, fo.theta, fo.mix, s_lt);
-#pragma unroll
-                for (int j = 0; j < 16; j++)
+                for (int j = 0; j < N; j++)
                     if (j < S) nf[(int64_t)j * n + i] = fv[j];
             }
 #pragma unroll
-            for (int j = 0; j < 16; j++) {
+            for (int j = 0; j < N; j++) {
                 q[j] = 0;
                 if (j < S) {
-                    const int32_t k = counts[(int64_t)j * n + i];
-                    const double f = FUSED ? fv[j] : nf[(int64_t)j * n + i];
+                    const int32_t k = kv[j];
+                    const double f = fv[j];
                     row[8 + 2 * j] = (uint32_t)__double2loint(f);
                     row[8 + 2 * j + 1] = (uint32_t)__double2hiint(f);
                     row[8 + 2 * S + j] = (uint32_t)k;
                     profile_add(cprof, k);
                     sign |= k;
                     q[j] = (double)k / f;
-                    tot += k;
                     s += q[j];
                     if ((d.gmask >> j) & 1) g1 += q[j]; else g0 += q[j];
                 }
@@ -140,33 +175,36 @@ __global__ __launch_bounds__(256) void prep16_kernel(const int32_t *__restrict__
             g0 /= d.nA;
             if (d.p == 2) g1 /= d.nB;
             row[0] = (uint32_t)__double2loint(g0);  // first half of the header: the group means
-            row[1] = (uint32_t)__double2hiint(g0) | (tot == 0 ? 0x80000000u : 0u);  // sign bit of the (never negative) mean: the row is all zero — the row-queue kernels read the flag with the record
+            row[1] = (uint32_t)__double2hiint(g0) | (sign == 0 ? 0x80000000u : 0u);  // sign bit of the (never negative) mean: the row is all zero — the row-queue kernels read the flag with the record
             row[2] = (uint32_t)__double2loint(g1);
             row[3] = (uint32_t)__double2hiint(g1);
             row[4] = cprof.w0;
             row[5] = cprof.w1;
             row[6] = cprof.w2;
-            s_live[tid] = tot != 0;
+            s_live[tid] = sign != 0;
             const double m0 = fmax(1.0, g0), m1 = fmax(1.0, g1);
             const double i0 = 1.0 / (m0 * m0), i1 = 1.0 / (m1 * m1);  // two divisions per row instead of one per sample
             double v = 0, est = 0;
 #pragma unroll
-            for (int j = 0; j < 16; j++)
+            for (int j = 0; j < N; j++)
                 if (j < S) {
                     v += (q[j] - bm) * (q[j] - bm);
                     const bool g = (d.gmask >> j) & 1;
                     const double mj = g ? m1 : m0;
                     est += ((q[j] - mj) * (q[j] - mj) - mj) * (g ? i1 : i0);
                 }
-            prep_store(d, w, i, s, g0, g1, v, est, tot);
+            prep_store(d, w, i, s, g0, g1, v, est, sign != 0);
             if (sign < 0) w.sc->neg_counts = 1;  // NA_integer_ / negative count: the fit is refused (include/chicdiff_hip.h)
         }
+        prep16_load<N>(src, n, S, next + tid, fv);  // the next tile's row, in flight across the rest of this one
+        if (!FUSED) prep16_load<N>(counts, n, S, next + tid, kv);
         __syncthreads();
         uint4 *dst = reinterpret_cast<uint4 *>(w.rowpack + base * stride);
         for (int c = tid; c < nrows * qpr; c += T) {
             const uint32_t *src = s_tile + (c / qpr) * ldw + (c % qpr) * 4;
             dst[c] = make_uint4(src[0], src[1], src[2], src[3]);
         }
+        const int cg = tid / ncol, cc = tid % ncol;  // (formed here, per tile: two registers less across the row's arithmetic above)
         if (cg < G) {
             DD a{0.0, 0.0};
             for (int r = cg; r < nrows; r += G)
@@ -177,13 +215,17 @@ __global__ __launch_bounds__(256) void prep16_kernel(const int32_t *__restrict__
             s_part[cg * ncol + cc] = a;
         }
         __syncthreads();
-        if (tid < ncol)
+        if (tid < ncol) {
+            DD colacc = s_col[tid];
             for (int g = 0; g < G; g++) dd_add(colacc, s_part[g * ncol + tid]);
+            s_col[tid] = colacc;
+        }
         __syncthreads();
+        base = next;
     }
     if (tid < ncol) {
-        w.partials[((int64_t)tid * gridDim.x + blockIdx.x) * 2] = colacc.hi;
-        w.partials[((int64_t)tid * gridDim.x + blockIdx.x) * 2 + 1] = colacc.lo;
+        w.partials[((int64_t)tid * gridDim.x + blockIdx.x) * 2] = s_col[tid].hi;
+        w.partials[((int64_t)tid * gridDim.x + blockIdx.x) * 2 + 1] = s_col[tid].lo;
     }
 }
 
@@ -286,19 +328,55 @@ __global__ void xim_kernel(FitDims d, FitWork w, const double *slots, int world)
 }
 
 constexpr int kColsumBlocks = 512;  // per column; (S+1) x 512 partials fit the 1024 x 72 partials buffer for S <= 64
-static int prep16_blocks(int) { return 1024; }  // four workgroups per CU — what their LDS tiles (34-38 KB) allow at once: one full round, no tail (768: 0.148 -> 0.127 ms at 2 M x 8, 1280: 0.163; S = 16: 1536 -> 1024: 0.40 -> 0.32, 2048: 0.33; round 4); (S + 1) x 1024 partials
-void launch_prep(const int32_t *counts, double *nf, FitDims d, FitWork w, Opts, hipStream_t st, FusedOffsets fo) {
-    if (d.S <= 16) {  // one resident round: 3 workgroups of 256 per CU; the LDS tile stays under 34 KB; the column sums ride along
-        const int T = row_stride(d.S) > 128 ? 128 : 256;
-        if (fo.fm) prep16_kernel<true><<<prep16_blocks(d.S), T, (size_t)T * (row_stride(d.S) + 4), st>>>(counts, nf, d, w, fo);
-        else prep16_kernel<false><<<prep16_blocks(d.S), T, (size_t)T * (row_stride(d.S) + 4), st>>>(counts, nf, d, w, fo);
-    } else {
-        prep_kernel<<<kRedBlocks, 256, 0, st>>>(counts, nf, d, w);
-        colsum_kernel<<<dim3(kColsumBlocks, d.S + 1), 256, 0, st>>>(nf, d, w);
-    }
+// Workgroups of prep16_kernel<FUSED, N>: one full resident round, no tail (768 instead of 1024 at four resident per CU: 0.127 -> 0.148 ms
+// at 2 M x 8, 1280: 0.163; S = 16: 1536 -> 1024: 0.40 -> 0.32, 2048: 0.33; round 4 — and an instance of which only three fit per CU ran
+// its 1024 as one round and a quarter: the fused form of rounds 5-17).  How many are resident is ASKED, not assumed: the runtime's
+// occupancy query for the instance with its largest LDS tile, once per process and instance (the devices of one process are one
+// model), times the device's CUs; at most four per CU (what the tiles, 34-38 KB, were laid out for) and at most kRedBlocks in all
+// ((S + 1) x kRedBlocks double-double partials fit FitWork::partials).  A query that fails leaves the four per CU of the launch bound.
+template <bool FUSED, int N>
+static int prep16_resident() {
+    static const int blocks = [] {
+        constexpr int T = N == 16 ? 128 : 256;
+        int per_cu = 0, dev = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, prep16_kernel<FUSED, N>, T, (size_t)T * (row_stride(N) + 4)) != hipSuccess || per_cu < 1 || per_cu > 4) per_cu = 4;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+        (void)hipGetLastError();
+        const int b = per_cu * cus;
+        return b < kRedBlocks ? b : kRedBlocks;
+    }();
+    return blocks;
 }
-void launch_prep_finish(FitDims d, FitWork w, double *slot, hipStream_t st) {
-    colsum_finish_kernel<<<d.S + 1, 64, 0, st>>>(d, w, d.S <= 16 ? prep16_blocks(d.S) : kColsumBlocks, d.S <= 16, slot);
+template <bool FUSED>
+static int prep16_blocks(int S) { return S <= 4 ? prep16_resident<FUSED, 4>() : S <= 8 ? prep16_resident<FUSED, 8>() : prep16_resident<FUSED, 16>(); }
+template <bool FUSED, int N>
+static void prep16_launch(int blocks, const int32_t *counts, double *nf, FitDims d, FitWork w, hipStream_t st, FusedOffsets fo) {
+    constexpr int T = N == 16 ? 128 : 256;  // (S > 8 <=> a row of the tile is longer than 128 bytes)
+    prep16_kernel<FUSED, N><<<blocks, T, (size_t)T * (row_stride(d.S) + 4), st>>>(counts, nf, d, w, fo);
+}
+// max_blocks > 0 (option "prep_blocks"): at most so many workgroups for the S <= 16 kernel, so that a few thousand rows are several
+// tiles per workgroup.  Returns the number of blocks whose partial column sums launch_prep_finish has to add.
+int launch_prep(const int32_t *counts, double *nf, FitDims d, FitWork w, Opts, hipStream_t st, FusedOffsets fo, int max_blocks) {
+    if (d.S <= 16) {  // the column sums ride along
+        int blocks = fo.fm ? prep16_blocks<true>(d.S) : prep16_blocks<false>(d.S);
+        if (max_blocks > 0 && max_blocks < blocks) blocks = max_blocks;
+        if (fo.fm) {
+            if (d.S <= 4) prep16_launch<true, 4>(blocks, counts, nf, d, w, st, fo);
+            else if (d.S <= 8) prep16_launch<true, 8>(blocks, counts, nf, d, w, st, fo);
+            else prep16_launch<true, 16>(blocks, counts, nf, d, w, st, fo);
+        } else {
+            if (d.S <= 4) prep16_launch<false, 4>(blocks, counts, nf, d, w, st, fo);
+            else if (d.S <= 8) prep16_launch<false, 8>(blocks, counts, nf, d, w, st, fo);
+            else prep16_launch<false, 16>(blocks, counts, nf, d, w, st, fo);
+        }
+        return blocks;
+    }
+    prep_kernel<<<kRedBlocks, 256, 0, st>>>(counts, nf, d, w);
+    colsum_kernel<<<dim3(kColsumBlocks, d.S + 1), 256, 0, st>>>(nf, d, w);
+    return kColsumBlocks;
+}
+void launch_prep_finish(FitDims d, FitWork w, int nblk, double *slot, hipStream_t st) {
+    colsum_finish_kernel<<<d.S + 1, 64, 0, st>>>(d, w, nblk, d.S <= 16, slot);
 }
 void launch_xim(FitDims d, FitWork w, const double *slots, int world, hipStream_t st) { xim_kernel<<<1, 64, 0, st>>>(d, w, slots, world); }
 

@@ -1671,18 +1671,21 @@ __device__ __forceinline__ double rlog(double x) { return (x > 0.0 && x < 1.7e30
 // 2 S logarithms, 2 exponentials and 2 S quotients per row sit beside 16 S bytes of traffic: the kernel is only
 // HBM-bound if that arithmetic is lean — table-driven log (devmath.h tlog, 1 KB table in LDS) and one reciprocal per
 // geometric mean instead of S divisions (x * (1/g) against x / g: <= 1.5 ulp, far inside the 1e-13 the parity test asks).
+// N: the sample class (S <= N, 4 / 8 / 16, picked at launch as sf_hist_kernel's) — the row's register array is as long as the class, not
+// always 16 doubles (compile-time resource report of the build: DESIGN.md section 5, round 18)
+template <int N>
 __global__ __launch_bounds__(256) void offsets16_kernel(const double *__restrict__ fm, const double *__restrict__ sf,
                                                         int64_t n, int S, double theta, int mix,
                                                         double *__restrict__ out) {
     __shared__ LogEntry s_lt[64];
     log_table_to_lds(s_lt);
     for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        double v[16];
+        double v[N];
 #pragma unroll
-        for (int j = 0; j < 16; j++) v[j] = j < S ? fm[(int64_t)j * n + i] : 1.0;
-        offsets_row16(v, S, sf, theta, mix, s_lt);
+        for (int j = 0; j < N; j++) v[j] = j < S ? fm[(int64_t)j * n + i] : 1.0;
+        offsets_row16<N>(v, S, sf, theta, mix, s_lt);
 #pragma unroll
-        for (int j = 0; j < 16; j++)
+        for (int j = 0; j < N; j++)
             if (j < S) out[(int64_t)j * n + i] = v[j];
     }
 }
@@ -1728,8 +1731,12 @@ void launch_offsets(const double *fm, const double *sf_dev, int64_t n, int S, do
         offsets_sf_kernel<<<(unsigned)blocks, 256, 0, st>>>(sf_dev, n, S, out);
         return;
     }
-    if (S <= 16)
-        offsets16_kernel<<<(unsigned)blocks, 256, 0, st>>>(fm, sf_dev, n, S, theta, mix, out);
+    if (S <= 4)
+        offsets16_kernel<4><<<(unsigned)blocks, 256, 0, st>>>(fm, sf_dev, n, S, theta, mix, out);
+    else if (S <= 8)
+        offsets16_kernel<8><<<(unsigned)blocks, 256, 0, st>>>(fm, sf_dev, n, S, theta, mix, out);
+    else if (S <= 16)
+        offsets16_kernel<16><<<(unsigned)blocks, 256, 0, st>>>(fm, sf_dev, n, S, theta, mix, out);
     else
         offsets_kernel<<<(unsigned)blocks, 256, 0, st>>>(fm, sf_dev, n, S, theta, mix, out);
 }

@@ -114,8 +114,12 @@ int32_t chicdiff_hip_last_refits(const chicdiff_hip_ctx *ctx);
  *   "trend_mad_in_kernel"       1 (default) | 0: the single-launch trend kernel goes on to the residuals, their exact median and MAD
  *                               and the closed-form prior variance; 0 = separate launches (residuals, two radix selects): same bits
  *   "fuse_offsets"              1 (default) | 0 | 2: chicdiff_hip_wald_test_dev and the theta grid form the offsets inside the fit's
- *                               first kernel for fits of up to 2^18 rows at S <= 16; 0 = always by a launch of their own, 2 = always
- *                               inside (at S <= 16): same bits
+ *                               first kernel wherever that was measured to be the faster route — since the kernels are built by
+ *                               sample class that is every fit at S <= 16; 0 = always by a launch of their own, 2 = always inside
+ *                               (at S <= 16): same bits
+ *   "prep_blocks"               0 (default: one resident round, sized by the runtime's occupancy query) | 1 .. 1024: test handle, at
+ *                               most this many workgroups for the fit's first kernel at S <= 16, so that a fit of a few thousand
+ *                               rows runs several tiles per workgroup: same bits
  *   "region_assemble_generic"   0 (default) | 1: test option of chicdiff_hip_region_assemble_dev (see there): same bits
  *   "chicago_tables_run_merge"  1 (default) | 0: chicdiff_hip_chicago_tables_dev merges runs of rows that aim at one fragment's slot inside the
  *                               wave before the global atomic (tables keyed by bait); 0 = one atomic per row: same bits

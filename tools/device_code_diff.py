@@ -4,7 +4,8 @@
     python tools/device_code_diff.py PARENT_DIR CHANGE_DIR
 
 A file's assembly is cut into its functions (from `.type NAME,@function` to the kernel descriptor or `.Lfunc_endN:`); local labels carry the
-function's position in the file (.LBB12_3, BB12_3, .Lfunc_end12), so the position is taken out before two bodies are compared.
+function's position in the file (.LBB12_3, BB12_3, .Lfunc_end12), so the position is taken out before two bodies are compared
+(and with it the blanks between a label and its comment, whose number depends on the position's digits).
 A kernel that exists in both builds must not differ in a single line; kernels of one build only are listed.  The kernel
 descriptors (.amdhsa_* blocks: registers, LDS, scratch) are compared the same way, under NAME.kd.
 """
@@ -32,6 +33,8 @@ def functions(path):
             kd, body = m.group(1) + ".kd", []
             continue
         line = re.sub(r"(\.?L?BB|\.Lfunc_(?:begin|end)|\.Ltmp)\d+", r"\1#", line)
+        # the assembler pads a label up to the column of its comment: a position of one digit more or less moves the blanks
+        line = re.sub(r"^(\.LBB#_\d+:)\s+;", r"\1 ;", line)
         if kd is not None:
             if re.match(r"\s*\.end_amdhsa_kernel", line):
                 out[kd] = body
