@@ -1735,6 +1735,16 @@ extern "C" int chicdiff_hip_selftest_math_dev(chicdiff_hip_ctx *c, int32_t op, c
     return CHICDIFF_OK;
 }
 
+// landau_tail (devmath.h) as the "hmp" overlap kernel calls it
+extern "C" int chicdiff_hip_selftest_landau_dev(chicdiff_hip_ctx *c, const double *d_z, int64_t n, double *d_out) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (!d_z || !d_out || n < 0) return fail(c, CHICDIFF_E_INVALID, "selftest_landau: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n > 0) launch_landau_selftest(d_z, n, d_out, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CHICDIFF_OK;
+}
+
 // building blocks with a second argument / a second result (header: the op numbers)
 extern "C" int chicdiff_hip_selftest_math3_dev(chicdiff_hip_ctx *c, int32_t op, const double *d_x, const double *d_y, int64_t n, double *d_out,
                                                double *d_out2) {
@@ -1978,16 +1988,19 @@ extern "C" int chicdiff_hip_region_universe_dev(chicdiff_hip_ctx *c, const int32
 
 // getCandidateInteractions (chicdiff.R:2068-2163): everything is enqueued behind one another; the one host stop is the read of the
 // counts (and of the refusals' row numbers, which ride in the same 40 bytes)
-extern "C" int chicdiff_hip_candidate_interactions_dev(chicdiff_hip_ctx *c, const int32_t *d_baitID, const int32_t *d_minOE,
-                                                       const int32_t *d_maxOE, const double *d_p, int64_t n, const int32_t *d_peak_baitID,
-                                                       const int32_t *d_peak_oeID, const double *d_scores, int64_t npeaks, int32_t ncols,
-                                                       int32_t ncond1, int32_t ncond2, int32_t merged, double score, double pvcut,
-                                                       double minDeltaAsinhScore, int64_t pair_capacity, int32_t *d_group_peak,
-                                                       int64_t *d_group_ptr, double *d_group_min_p, double *d_group_delta, int32_t *d_pair_row,
-                                                       int64_t *ngroups_host, int64_t *npairs_host) {
+extern "C" int chicdiff_hip_candidate_interactions_method_dev(chicdiff_hip_ctx *c, const int32_t *d_baitID, const int32_t *d_minOE,
+                                                              const int32_t *d_maxOE, const double *d_p, int64_t n,
+                                                              const int32_t *d_peak_baitID, const int32_t *d_peak_oeID, const double *d_scores,
+                                                              int64_t npeaks, int32_t ncols, int32_t ncond1, int32_t ncond2, int32_t merged,
+                                                              double score, double pvcut, double minDeltaAsinhScore, int32_t method,
+                                                              int64_t pair_capacity, int32_t *d_group_peak, int64_t *d_group_ptr,
+                                                              double *d_group_min_p, double *d_group_delta, int32_t *d_pair_row,
+                                                              int64_t *ngroups_host, int64_t *npairs_host) {
     if (!c) return CHICDIFF_E_INVALID;
     if (ngroups_host) *ngroups_host = 0;
     if (npairs_host) *npairs_host = 0;
+    if (method != CHICDIFF_CAND_MIN && method != CHICDIFF_CAND_HMP)
+        return fail(c, CHICDIFF_E_INVALID, "candidate_interactions: method = %d (CHICDIFF_CAND_MIN = 0 or CHICDIFF_CAND_HMP = 1)", (int)method);
     if (!d_baitID || !d_minOE || !d_maxOE || !d_p || !d_group_peak || !d_group_ptr || !d_group_min_p || !d_group_delta || !ngroups_host ||
         !npairs_host || (pair_capacity > 0 && !d_pair_row) || pair_capacity < 0 || (npeaks > 0 && (!d_peak_baitID || !d_peak_oeID || !d_scores)))
         return fail(c, CHICDIFF_E_INVALID, "candidate_interactions: bad arguments");
@@ -2005,7 +2018,7 @@ extern "C" int chicdiff_hip_candidate_interactions_dev(chicdiff_hip_ctx *c, cons
     a.bait = d_baitID; a.minOE = d_minOE; a.maxOE = d_maxOE; a.p = d_p; a.n = n;
     a.peak_bait = d_peak_baitID; a.peak_oe = d_peak_oeID; a.scores = d_scores; a.npeaks = npeaks;
     a.ncols = ncols; a.ncond1 = ncond1; a.merged = merged;
-    a.score = score; a.pvcut = pvcut; a.min_delta = minDeltaAsinhScore; a.pair_capacity = pair_capacity;
+    a.score = score; a.pvcut = pvcut; a.min_delta = minDeltaAsinhScore; a.method = method; a.pair_capacity = pair_capacity;
     a.group_peak = d_group_peak; a.group_ptr = d_group_ptr; a.group_min_p = d_group_min_p; a.group_delta = d_group_delta;
     a.pair_row = d_pair_row;
     const CandResult *d_res = nullptr;
@@ -2033,6 +2046,19 @@ extern "C" int chicdiff_hip_candidate_interactions_dev(chicdiff_hip_ctx *c, cons
         return fail(c, CHICDIFF_E_INVALID, "candidate_interactions: room for %lld pairs needed, %lld given (no pair was written)", h.npairs,
                     (long long)pair_capacity);
     return CHICDIFF_OK;
+}
+
+extern "C" int chicdiff_hip_candidate_interactions_dev(chicdiff_hip_ctx *c, const int32_t *d_baitID, const int32_t *d_minOE,
+                                                       const int32_t *d_maxOE, const double *d_p, int64_t n, const int32_t *d_peak_baitID,
+                                                       const int32_t *d_peak_oeID, const double *d_scores, int64_t npeaks, int32_t ncols,
+                                                       int32_t ncond1, int32_t ncond2, int32_t merged, double score, double pvcut,
+                                                       double minDeltaAsinhScore, int64_t pair_capacity, int32_t *d_group_peak,
+                                                       int64_t *d_group_ptr, double *d_group_min_p, double *d_group_delta, int32_t *d_pair_row,
+                                                       int64_t *ngroups_host, int64_t *npairs_host) {
+    return chicdiff_hip_candidate_interactions_method_dev(c, d_baitID, d_minOE, d_maxOE, d_p, n, d_peak_baitID, d_peak_oeID, d_scores, npeaks, ncols,
+                                                          ncond1, ncond2, merged, score, pvcut, minDeltaAsinhScore, CHICDIFF_CAND_MIN, pair_capacity,
+                                                          d_group_peak, d_group_ptr, d_group_min_p, d_group_delta, d_pair_row, ngroups_host,
+                                                          npairs_host);
 }
 
 // The seeded control draws (chicdiff.R:430-481): contact pass, draws, sort and unpack enqueued behind one another; the one host stop is

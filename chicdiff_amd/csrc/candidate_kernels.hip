@@ -17,6 +17,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "devmath.h"
 
 namespace cd {
 
@@ -25,6 +26,9 @@ namespace {
 constexpr uint64_t kCandNoKey = ~0ull;  // sort key of a peak row that the score filter drops: behind every selected row
 constexpr int kCandWin = 256;           // regions a wave stages in its LDS slice (20 bytes each: 20 KB per workgroup of four waves)
 constexpr int kCandRegionBlocks = 1024;
+// method = "hmp" (:2135-2137, 2146): 1 + digamma(1) - log(2 / pi), the location of p.hmp's Landau law without its log L; its scale
+constexpr double kHmpLoc = 0.874367040387922004, kHmpScale = 1.57079632679489661923;
+static __device__ const LandauTable kLandauTable = CD_LANDAU_TABLE_INIT;
 
 __device__ __forceinline__ uint64_t cand_key(int32_t bait, int32_t oe) {
     return ((uint64_t)((uint32_t)bait ^ 0x80000000u) << 32) | (uint64_t)((uint32_t)oe ^ 0x80000000u);
@@ -151,8 +155,12 @@ __device__ __forceinline__ int64_t cand_bound(const Keys &keys, int64_t lo, int6
 // fits — one bait with thousands of regions is legal, then the lanes search global memory instead.  Each lane then scans
 // [lower_bound(bait, oe - span), upper_bound(bait, oe)) and tests maxOE >= oe.  The look-back by span is what finds a wide region
 // that sits many rows in front of the peak's neighbours in key order.
-// Per sorted peak: keep flag, kept degree (the two scan inputs), min p, and for the fill the scan's first index and which of its
-// first 64 candidates matched.
+// Per sorted peak: keep flag, kept degree (the two scan inputs), the combined p, and for the fill the scan's first index and which
+// of its first 64 candidates matched.
+// METHOD: CHICDIFF_CAND_MIN — the minimum of p over the matches, NA if one is NA; CHICDIFF_CAND_HMP — p.hmp of the matches: NA and
+// p > 1 count as 1 (:2136), the reciprocals are summed in match (= pair) order, each a division, and the sum goes through
+// landau_tail once per peak.  Only the reduction differs: the scan, its order and everything written for the fill are shared.
+template <int METHOD>
 __global__ __launch_bounds__(256) void cand_overlap_kernel(const uint64_t *__restrict__ pkey, const int32_t *__restrict__ prow, int64_t P,
                                                            const double *__restrict__ delta, const uint64_t *__restrict__ rkey,
                                                            const int32_t *__restrict__ rrow, int64_t n, const int32_t *__restrict__ maxOE,
@@ -204,7 +212,7 @@ __global__ __launch_bounds__(256) void cand_overlap_kernel(const uint64_t *__res
         b = cand_bound<true>(rkey, wlo + a, whi, key) - wlo;
     }
     int32_t deg = 0;
-    double m = INFINITY;
+    double m = METHOD == CHICDIFF_CAND_HMP ? 0.0 : INFINITY;  // hmp: the sum of 1 / p'
     bool na = false;
     uint64_t msk = 0;
     for (int64_t j = a; j < b; j++) {
@@ -220,12 +228,22 @@ __global__ __launch_bounds__(256) void cand_overlap_kernel(const uint64_t *__res
         }
         if (mx >= oe) {
             deg++;
-            na |= pv != pv;       // min() without na.rm: one NA makes the minimum NA (fmin would drop it)
-            m = pv < m ? pv : m;
+            if constexpr (METHOD == CHICDIFF_CAND_HMP) {
+                m += 1.0 / (pv <= 1.0 ? pv : 1.0);  // NA fails the comparison too
+            } else {
+                na |= pv != pv;       // min() without na.rm: one NA makes the minimum NA (fmin would drop it)
+                m = pv < m ? pv : m;
+            }
             if (j - a < 64) msk |= 1ull << (j - a);
         }
     }
-    const double mp = na ? NAN : m;
+    double mp;
+    if constexpr (METHOD == CHICDIFF_CAND_HMP) {
+        const double L = (double)deg;  // x = mean of 1 / p' >= 1, so z > -14 for every L < 2^31; p = 0 gives x = z = inf and 0
+        mp = deg > 0 ? landau_tail((m / L - (flog(L) + kHmpLoc)) / kHmpScale, kLandauTable) : NAN;
+    } else {
+        mp = na ? NAN : m;
+    }
     const int32_t r = prow[s];
     const bool kp = deg > 0 && mp <= pvcut && delta[r] >= min_delta;  // a NaN on either side drops the group (:2161)
     if (prev == key) atomicMin(&res->dup_peak, (unsigned long long)r);  // two selected rows with one (baitID, oeID)
@@ -311,6 +329,11 @@ __global__ __launch_bounds__(256) void cand_fill_kernel(const CandResult *__rest
     }
 }
 
+// out[i] = landau_tail(z[i]) as cand_overlap_kernel<CHICDIFF_CAND_HMP> calls it
+__global__ __launch_bounds__(256) void landau_selftest_kernel(const double *__restrict__ z, int64_t n, double *out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = landau_tail(z[i], kLandauTable);
+}
+
 int cand_grid(int64_t items) {
     int64_t b = (items + 255) / 256;
     return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
@@ -393,8 +416,12 @@ int launch_candidates(const CandArgs &a, char *ws, hipStream_t st, const CandRes
     t = tmp_bytes;
     if (rocprim::radix_sort_pairs(tmp, t, pka, pkb, pra, prb, (size_t)P, 0, 64, st) != hipSuccess) return 1;
     // join, compaction, fill
-    cand_overlap_kernel<<<(unsigned)((P + 255) / 256), 256, 0, st>>>(pkb, prb, P, delta, kb, ra, n, a.maxOE, a.p, span, a.pvcut, a.min_delta, keep,
-                                                                    kdeg, minp, first, mask, res);
+    if (a.method == CHICDIFF_CAND_HMP)
+        cand_overlap_kernel<CHICDIFF_CAND_HMP><<<(unsigned)((P + 255) / 256), 256, 0, st>>>(pkb, prb, P, delta, kb, ra, n, a.maxOE, a.p, span, a.pvcut,
+                                                                                           a.min_delta, keep, kdeg, minp, first, mask, res);
+    else
+        cand_overlap_kernel<CHICDIFF_CAND_MIN><<<(unsigned)((P + 255) / 256), 256, 0, st>>>(pkb, prb, P, delta, kb, ra, n, a.maxOE, a.p, span, a.pvcut,
+                                                                                           a.min_delta, keep, kdeg, minp, first, mask, res);
     t = tmp_bytes;
     if (rocprim::exclusive_scan(tmp, t, keep, slot, (int32_t)0, Q, rocprim::plus<int32_t>(), st) != hipSuccess) return 1;
     t = tmp_bytes;
@@ -403,6 +430,10 @@ int launch_candidates(const CandArgs &a, char *ws, hipStream_t st, const CandRes
                                                          a.group_min_p, a.group_delta, g_first, g_mask, g_oe, res);
     cand_fill_kernel<<<cand_grid(P), 256, 0, st>>>(res, a.pair_capacity, a.group_ptr, g_first, g_mask, g_oe, ra, n, a.maxOE, a.pair_row);
     return 0;
+}
+
+void launch_landau_selftest(const double *z, int64_t n, double *out, hipStream_t st) {
+    landau_selftest_kernel<<<cand_grid(n), 256, 0, st>>>(z, n, out);
 }
 
 }  // namespace cd

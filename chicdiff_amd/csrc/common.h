@@ -334,6 +334,7 @@ struct CandArgs {
     int64_t npeaks;
     int32_t ncols, ncond1, merged;
     double score, pvcut, min_delta;
+    int32_t method;                       // CHICDIFF_CAND_MIN | CHICDIFF_CAND_HMP: what group_min_p carries
     int64_t pair_capacity;
     int32_t *group_peak;
     int64_t *group_ptr;
@@ -347,6 +348,7 @@ struct CandResult {
 };
 size_t cand_workspace_bytes(int64_t n, int64_t npeaks);
 int launch_candidates(const CandArgs &a, char *ws, hipStream_t st, const CandResult **res_out);
+void launch_landau_selftest(const double *z, int64_t n, double *out, hipStream_t st);  // out[i] = landau_tail(z[i]) (devmath.h)
 // control_kernels.hip — the seeded draws of getControlRegionUniverse (chicdiff.R:430-481)
 struct CtrlArgs {
     const int32_t *ru_bait;               // RU rows in (regionID, otherEndID) order: baitID

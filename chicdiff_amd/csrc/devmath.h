@@ -10,6 +10,7 @@
 
 #include "exp_table.h"
 #include "fit_state.h"
+#include "landau_table.h"
 #include "log_table.h"
 
 namespace cd {
@@ -387,6 +388,68 @@ __device__ __forceinline__ void offsets_row16(double (&v)[N], int S, const doubl
         for (int j = 0; j < N; j++)
             if (j < S) v[j] = v[j] * i2;
     }
+}
+
+// ---- Q(z), the upper tail of the Landau distribution that harmonicmeanp::p.hmp evaluates ------------------------------------
+//   Q(z) = (1 / pi) int_0^inf exp(-t z - (2 / pi) t log t) sin(2 t) / t dt         (Wilson 2019, PNAS 116:1195, eq. 4, integrated once)
+// from the coefficients of landau_table.h (tools/make_landau_table.py): 1 below CD_LANDAU_ONE, where 1 - Q < 2^-54; a polynomial
+// of degree CD_LANDAU_DEG in the interval's own variable s in [-1, 1] on CD_LANDAU_NUNI intervals of width 1/4 up to z = 2 and on
+// four intervals per octave from there to CD_LANDAU_CUT; the expansion (1 / z) sum_n z^-n P_n(log z) beyond.  The interval comes from
+// arithmetic on z (below 2) or from its exponent and two top mantissa bits (from 2 on): no search, no divergent loop, and s is exact
+// from 2 on.  Every lane reads its own row of the table from global memory (lanes of one wave mostly share a few rows: 17 loads
+// that hit the cache) — no LDS, so a kernel that calls this keeps its LDS budget.  The result is clamped between Q at the
+// interval's two bounds, which makes it non-increasing across a seam whatever the last bits of two neighbouring polynomials do,
+// and never above 1.  NaN gives NaN.  The table is an argument: only the translation unit that calls this defines one
+// (CD_LANDAU_TABLE_INIT), so no other unit's code changes.
+struct LandauTable {
+    double coef[CD_LANDAU_NINT][CD_LANDAU_DEG + 2];  // s^0 as (hi, lo), s^1 .. s^DEG
+    double end[CD_LANDAU_NINT + 1];
+    double series[CD_LANDAU_NTERMS * (CD_LANDAU_NTERMS + 1) / 2 + 1];  // P_0 as (hi, lo), P_1's two coefficients, ...
+};
+#define CD_LANDAU_TABLE_INIT {{CD_LANDAU_COEF_INIT}, {CD_LANDAU_END_INIT}, {CD_LANDAU_SERIES_INIT}}
+
+__device__ __forceinline__ double landau_tail(double z, const LandauTable &t) {
+    if (!(z > CD_LANDAU_ONE)) return z != z ? z : 1.0;
+    if (z >= CD_LANDAU_CUT) {
+        if (z > 0x1p+100) return t.series[0] / z;  // the other terms are below 2^-90 of this one; +inf gives 0
+        const double L = flog(z), w = rcp(z);
+        double acc = 0.0;
+        int at = CD_LANDAU_NTERMS * (CD_LANDAU_NTERMS + 1) / 2 + 1;
+#pragma unroll
+        for (int n = CD_LANDAU_NTERMS - 1; n >= 1; n--) {
+            at -= n + 1;
+            double pn = t.series[at + n];
+#pragma unroll
+            for (int j = n - 1; j >= 0; j--) pn = fma(pn, L, t.series[at + j]);
+            acc = fma(acc, w, pn);
+        }
+        acc = fma(acc, w, t.series[1]) + t.series[0];
+        return fmin(acc / z, t.end[CD_LANDAU_NINT]);
+    }
+    int i;
+    double s;
+    if (z < 2.0) {
+        i = (int)((z - CD_LANDAU_ONE) * 4.0);
+        i = i > CD_LANDAU_NUNI - 1 ? CD_LANDAU_NUNI - 1 : i;
+        double lo = fma(0.25, (double)i, CD_LANDAU_ONE);  // exact
+        if (z < lo) {                                     // z - ONE was rounded up onto the bound (i >= 1 here: z > ONE)
+            i--;
+            lo -= 0.25;
+        }
+        s = (z - (lo + 0.125)) * 8.0;
+    } else {
+        const unsigned long long b = (unsigned long long)__double_as_longlong(z);  // 2 <= z < CUT: the biased exponent is 1024 ..
+        i = CD_LANDAU_NUNI + (int)(b >> 50) - 4096;
+        const double c = __longlong_as_double((long long)((b & ~((1ull << 50) - 1ull)) | (1ull << 49)));  // the interval's middle
+        const double sc = __longlong_as_double((long long)((unsigned long long)(2049 - (int)(b >> 52)) << 52));  // 8 / 2^e
+        s = (z - c) * sc;
+    }
+    const double *c = t.coef[i];
+    double r = c[CD_LANDAU_DEG + 1];
+#pragma unroll
+    for (int k = CD_LANDAU_DEG; k >= 1; k--) r = fma(r, s, c[k]);
+    r += c[0];
+    return fmin(fmax(r, t.end[i + 1]), t.end[i]);
 }
 
 }  // namespace cd

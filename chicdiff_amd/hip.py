@@ -27,7 +27,7 @@ EXPORTS = [
     "chicdiff_hip_offsets_dev", "chicdiff_hip_window_sums_dev", "chicdiff_hip_count_join_dev",
     "chicdiff_hip_fragment_background_dev", "chicdiff_hip_bh_adjust_dev", "chicdiff_hip_ihw_apply_dev",
     "chicdiff_hip_region_universe_count_dev", "chicdiff_hip_region_universe_fill_dev", "chicdiff_hip_region_universe_dev", "chicdiff_hip_count_table_dev",
-    "chicdiff_hip_candidate_interactions_dev", "chicdiff_hip_chicago_tables_dev", "chicdiff_hip_chicago_tables_caps",
+    "chicdiff_hip_candidate_interactions_dev", "chicdiff_hip_candidate_interactions_method_dev", "chicdiff_hip_selftest_landau_dev", "chicdiff_hip_chicago_tables_dev", "chicdiff_hip_chicago_tables_caps",
     "chicdiff_hip_control_draws_dev",
     "chicdiff_hip_chinput_read", "chicdiff_hip_chinput_table_dev", "chicdiff_hip_region_avdist_dev",
     "chicdiff_hip_count_join_inner_dev", "chicdiff_hip_count_join_multi_dev", "chicdiff_hip_region_assemble_dev",
@@ -69,6 +69,9 @@ class ResultsInfo(C.Structure):
 
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char_p), ("ms", C.c_double), ("launches", C.c_int32), ("_pad", C.c_int32), ("bytes", C.c_double)]
+
+
+CAND_METHODS = {"min": 0, "hmp": 1}   # CHICDIFF_CAND_MIN, CHICDIFF_CAND_HMP (include/chicdiff_hip.h)
 
 
 class ChicdiffHipError(RuntimeError):
@@ -139,6 +142,9 @@ def load_library() -> C.CDLL:
     L.chicdiff_hip_region_universe_dev.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
     L.chicdiff_hip_candidate_interactions_dev.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, dbl, dbl, dbl, i64,
                                                           vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
+    L.chicdiff_hip_candidate_interactions_method_dev.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, dbl, dbl, dbl, i32,
+                                                                 i64, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
+    L.chicdiff_hip_selftest_landau_dev.argtypes = [vp, vp, i64, vp]
     L.chicdiff_hip_chicago_tables_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp,
                                                   C.POINTER(i32)]
     L.chicdiff_hip_chicago_tables_caps.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
@@ -568,7 +574,7 @@ class HipContext:
 
     # -- getCandidateInteractions ----------------------------------------------------------------
     def candidate_interactions(self, d_baitID, d_minOE, d_maxOE, d_p, d_peak_baitID, d_peak_oeID, d_scores, ncond1, ncond2, merged,
-                               score, pvcut, minDeltaAsinhScore, pair_row=None):
+                               score, pvcut, minDeltaAsinhScore, pair_row=None, method="min"):
         """getCandidateInteractions' join and filter (chicdiff.R:2068-2163; the rules are above
         chicdiff_hip_candidate_interactions_dev in include/chicdiff_hip.h).  Region table: int32 (n,) tensors and the chosen
         p column, float64 (n,), in the rows' own order; peak matrix rows as read: int32 (npeaks,) IDs and ``d_scores`` of shape
@@ -577,8 +583,15 @@ class HipContext:
         Returns dict(group_peak, group_ptr, group_min_p, group_delta, pair_row, ngroups, npairs), the tensors trimmed to the
         surviving groups and their pairs.  The first call gives room for 16 npeaks pairs; if that is too little (duplicate
         regions have no bound) it is repeated once with exactly the reported need.  ``pair_row``: a caller's int32 buffer
-        instead — its length is the capacity, and there is no second call: too small raises, with ``.need = (ngroups, npairs)``."""
+        instead — its length is the capacity, and there is no second call: too small raises, with ``.need = (ngroups, npairs)``.
+
+        ``method``: "min" or "hmp" (or the C ABI's CHICDIFF_CAND_* number) — what ``group_min_p`` carries and the filter reads:
+        the minimum of the group's p values, or harmonicmeanp::p.hmp of them (chicdiff_hip_candidate_interactions_method_dev)."""
         torch = self.torch
+        if isinstance(method, str):
+            if method not in CAND_METHODS:
+                raise ValueError(f"candidate_interactions: unknown method {method!r} (should be 'min' or 'hmp')")
+            method = CAND_METHODS[method]
         n, (ncols, npeaks) = d_baitID.numel(), d_scores.shape
         for t in (d_baitID, d_minOE, d_maxOE, d_peak_baitID, d_peak_oeID):
             assert t.dtype == torch.int32 and t.is_contiguous()
@@ -591,10 +604,10 @@ class HipContext:
         ng, npairs = C.c_int64(0), C.c_int64(0)
 
         def call(pairs):
-            return self.lib.chicdiff_hip_candidate_interactions_dev(
+            return self.lib.chicdiff_hip_candidate_interactions_method_dev(
                 self.h, d_baitID.data_ptr(), d_minOE.data_ptr(), d_maxOE.data_ptr(), d_p.data_ptr(), n, d_peak_baitID.data_ptr(),
                 d_peak_oeID.data_ptr(), d_scores.data_ptr(), npeaks, ncols, int(ncond1), int(ncond2), int(bool(merged)), float(score),
-                float(pvcut), float(minDeltaAsinhScore), pairs.numel(), gpeak.data_ptr(), gptr.data_ptr(), gmin.data_ptr(),
+                float(pvcut), float(minDeltaAsinhScore), int(method), pairs.numel(), gpeak.data_ptr(), gptr.data_ptr(), gmin.data_ptr(),
                 gdelta.data_ptr(), pairs.data_ptr(), C.byref(ng), C.byref(npairs))
 
         own = pair_row is None
@@ -782,6 +795,13 @@ class HipContext:
     def selftest_math(self, op: int, d_x):
         out = self.torch.empty_like(d_x)
         self._check(self.lib.chicdiff_hip_selftest_math_dev(self.h, op, d_x.data_ptr(), d_x.numel(), out.data_ptr()))
+        return out
+
+    def selftest_landau(self, d_z):
+        """landau_tail(z) (devmath.h), the Landau tail behind method = "hmp", as the overlap kernel calls it."""
+        assert d_z.dtype == self.torch.float64 and d_z.is_contiguous()
+        out = self.torch.empty_like(d_z)
+        self._check(self.lib.chicdiff_hip_selftest_landau_dev(self.h, d_z.data_ptr(), d_z.numel(), out.data_ptr()))
         return out
 
     def selftest_math3(self, op: int, d_x, d_y):

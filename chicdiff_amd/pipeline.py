@@ -541,17 +541,20 @@ def _fmt_double(x):
 def getCandidateInteractions(output, peakFiles, chicdiff_settings, pcol="weighted_padj", method="min", minDeltaAsinhScore=1, pvcut=0.05,
                              ctx=None):
     """chicdiff.R:2068-2163: region-level results -> fragment-level candidate interactions.  The sort of the regions, the overlap
-    join of every peak against the regions of its bait, min(pcol) per (baitID, oeID) and the final filter run on the device
-    (chicdiff_hip_candidate_interactions_dev); only the surviving groups come back, and their four paste()d columns are built
-    here.  ``output``: the results table (a DataFrame, or the path of the _results.csv IHWcorrection wrote); ``peakFiles``: ONE
+    join of every peak against the regions of its bait, the combined pcol per (baitID, oeID) and the final filter run on the
+    device (chicdiff_hip_candidate_interactions_method_dev); only the surviving groups come back, and their four paste()d columns
+    are built here.  ``output``: the results table (a DataFrame, or the path of the _results.csv IHWcorrection wrote); ``peakFiles``: ONE
     peak matrix, read as it is — only the score filter applies (:2082-2087), not readAndFilterPeakMatrix's other filters.
-    ``method = "hmp"`` is not offered: harmonicmeanp::p.hmp stays R."""
+    ``method = "hmp"`` (:2135-2137, 2146) combines by harmonicmeanp::p.hmp: the column is then ``hm_<pcol>``, and the pasted
+    ``<pcol>`` column shows NA and values above 1 as 1, because the reference rewrites the column (:2136) before it pastes it.
+    The value is this library's restatement of p.hmp (the published Landau-tail formula, pinned with mpmath, unpinned against
+    FMStable's numerics), so the caller opts into it by passing an open HipContext: without ``ctx`` the call raises."""
     import pandas as pd
     if method not in ("min", "hmp"):                                               # :2095-2097
         raise ValueError("getCandidateInteractions error: Unknown method to combine p-values (should be 'min' or 'hmp')")
-    if method == "hmp":
-        raise ValueError("getCandidateInteractions: method = 'hmp' needs harmonicmeanp::p.hmp (the tail of a Landau distribution), "
-                         "which stays R; the device path offers method = 'min'")
+    if method == "hmp" and ctx is None:
+        raise ValueError("getCandidateInteractions: method = 'hmp' is harmonicmeanp::p.hmp (the tail of a Landau distribution) as this "
+                         "library restates it from the published formula, not R's own numerics: pass an open HipContext as ctx to opt into it")
     raw = chicdiff_settings["chicagoData"]
     raw = raw[0] if isinstance(raw, (list, tuple)) and len(raw) == 1 and isinstance(raw[0], dict) else raw
     conds = list(raw)
@@ -580,7 +583,8 @@ def getCandidateInteractions(output, peakFiles, chicdiff_settings, pcol="weighte
         scores = np.ascontiguousarray(x[names].to_numpy(np.float64).T)
         r = ctx.candidate_interactions(dev(output["baitID"], np.int32), dev(output["minOE"], np.int32), dev(output["maxOE"], np.int32),
                                        dev(output[pcol], np.float64), dev(x["baitID"], np.int32), dev(x["oeID"], np.int32),
-                                       dev(scores, np.float64), len(cnames[0]), len(cnames[1]), merged, score, pvcut, minDeltaAsinhScore)
+                                       dev(scores, np.float64), len(cnames[0]), len(cnames[1]), merged, score, pvcut, minDeltaAsinhScore,
+                                       method=method)
         gp, ptr, rows = r["group_peak"].cpu().numpy(), r["group_ptr"].cpu().numpy(), r["pair_row"].cpu().numpy()
         min_p, delta = r["group_min_p"].cpu().numpy(), r["group_delta"].cpu().numpy()
     finally:
@@ -593,9 +597,11 @@ def getCandidateInteractions(output, peakFiles, chicdiff_settings, pcol="weighte
              "baitName": px["baitName"].to_numpy()}
     for c in names:
         final[c] = px[c].to_numpy()
-    final["min_" + pcol] = min_p
+    final[("hm_" if method == "hmp" else "min_") + pcol] = min_p
     final["deltaAsinhScore"] = delta
     rid, lfc, pv = output["regionID"].to_numpy(), output["log2FoldChange"].to_numpy(np.float64), output[pcol].to_numpy(np.float64)
+    if method == "hmp":
+        pv = np.where((pv != pv) | (pv > 1), 1.0, pv)                              # :2136 rewrites the column before :2153 pastes it
     oes, oee = output["OEstart"].to_numpy(), output["OEend"].to_numpy()
     groups = [rows[ptr[g]:ptr[g + 1]] for g in range(len(gp))]
     final["regionIDs"] = [",".join(str(rid[k]) for k in g) for g in groups]

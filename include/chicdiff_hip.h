@@ -419,14 +419,36 @@ int chicdiff_hip_region_universe_dev(chicdiff_hip_ctx *ctx, const int32_t *d_bai
  * CHICDIFF_E_INVALID, the message naming the offending row: a region row with minOE > maxOE or an INT32_MIN (NA) key (foverlaps stops
  * on both); two SELECTED peak rows with the same (baitID, oeID) (the reference would merge them into one group; Chicago's peak
  * matrix has one row per pair); a selected peak row with baitID = oeID = INT32_MAX.  Also n < 1, n >= 2^31, ncols < 2,
- * npeaks >= 2^31.  npeaks = 0 or no survivor: CHICDIFF_OK with zero groups (d_group_ptr[0] = 0).
- * method = "hmp" (harmonicmeanp::p.hmp) is not offered: it stays R. */
+ * npeaks >= 2^31.  npeaks = 0 or no survivor: CHICDIFF_OK with zero groups (d_group_ptr[0] = 0). */
 int chicdiff_hip_candidate_interactions_dev(chicdiff_hip_ctx *ctx, const int32_t *d_baitID, const int32_t *d_minOE, const int32_t *d_maxOE,
                                             const double *d_p, int64_t n, const int32_t *d_peak_baitID, const int32_t *d_peak_oeID,
                                             const double *d_scores, int64_t npeaks, int32_t ncols, int32_t ncond1, int32_t ncond2,
                                             int32_t merged, double score, double pvcut, double minDeltaAsinhScore, int64_t pair_capacity,
                                             int32_t *d_group_peak, int64_t *d_group_ptr, double *d_group_min_p, double *d_group_delta,
                                             int32_t *d_pair_row, int64_t *ngroups_host, int64_t *npairs_host);
+
+/* The same call with the reference's `method` argument (method = c("min", "hmp"), chicdiff.R:2135-2137, 2146): how the pcol values of
+ * a group's regions are combined.  d_group_min_p carries the combined p of the chosen method, and the filter (:2161) reads it.
+ * CHICDIFF_CAND_MIN is the call above.  CHICDIFF_CAND_HMP is harmonicmeanp::p.hmp(pcol) as the reference calls it (no w, no L), for
+ * a group of L regions with values p_1 .. p_L in the group's pair order:
+ *   p'_k = 1 if p_k is NA or p_k > 1 (:2136), p_k otherwise
+ *   x    = (sum_k 1 / p'_k) / L, the sum formed sequentially in pair order, each 1 / p'_k a correctly rounded division
+ *   z    = (x - (log L + c)) / (pi / 2),   c = 1 + digamma(1) - log(2 / pi) = 0.874367040387922004
+ *   hm_p = Q(z) = (1 / pi) int_0^inf exp(-t z - (2 / pi) t log t) sin(2 t) / t dt
+ * Q is the upper tail of the Landau density of Wilson 2019 (PNAS 116:1195), eq. 4.  p_k = 0 gives x = inf and hm_p = 0; x >= 1, so
+ * z > -14 for every L < 2^31; below z = -3.5 Q is 1 to double precision and the call returns exactly 1, never more.  A negative p
+ * is outside the contract: it is not checked, and the arithmetic runs as written.  The value is pinned by the published formula,
+ * evaluated with mpmath (tests/golden/landau_tail.json, and the paper's Table 1), and unpinned against the numerics of FMStable,
+ * from which harmonicmeanp takes the Landau tail.  Any other method: CHICDIFF_E_INVALID. */
+#define CHICDIFF_CAND_MIN 0
+#define CHICDIFF_CAND_HMP 1
+int chicdiff_hip_candidate_interactions_method_dev(chicdiff_hip_ctx *ctx, const int32_t *d_baitID, const int32_t *d_minOE,
+                                                   const int32_t *d_maxOE, const double *d_p, int64_t n, const int32_t *d_peak_baitID,
+                                                   const int32_t *d_peak_oeID, const double *d_scores, int64_t npeaks, int32_t ncols,
+                                                   int32_t ncond1, int32_t ncond2, int32_t merged, double score, double pvcut,
+                                                   double minDeltaAsinhScore, int32_t method, int64_t pair_capacity, int32_t *d_group_peak,
+                                                   int64_t *d_group_ptr, double *d_group_min_p, double *d_group_delta, int32_t *d_pair_row,
+                                                   int64_t *ngroups_host, int64_t *npairs_host);
 
 /* limits of chicdiff_hip_control_draws_dev (below) */
 #define CHICDIFF_CONTROL_MAX_CHR 1024     /* chromosome codes: the per-chromosome tables are kept per workgroup in LDS */
@@ -546,6 +568,9 @@ int chicdiff_hip_wald_pvalues_dev(chicdiff_hip_ctx *ctx, const double *d_stat, i
  * 3 lgamma, 4 digamma, 5 2*pnorm(-|x|), 8 exp (table) — the special functions the fit kernels are built on —, 9 qnorm (AS 241
  * with the polynomial log in its tails, 0 < x < 1), as chicdiff_hip_control_draws_dev calls it. */
 int chicdiff_hip_selftest_math_dev(chicdiff_hip_ctx *ctx, int32_t op, const double *d_x, int64_t n, double *d_out);
+/* out[i] = Q(z[i]), the Landau tail of CHICDIFF_CAND_HMP, as the overlap kernel of chicdiff_hip_candidate_interactions_method_dev
+ * calls it: 1 for z <= -3.5, 0 for +inf, NaN for NaN. */
+int chicdiff_hip_selftest_landau_dev(chicdiff_hip_ctx *ctx, const double *d_z, int64_t n, double *d_out);
 /* The same for the functions of two arguments / two results that carry the dispersion objective, the constant part of the NB
  * log-likelihood and the reported deviance, each called as the kernels call it; y[i] is an integer count held in a double:
  * op 10 lgr_eval_t(lgr_make_t(x), y) and 11 lgr_eval(lgr_make(x), y) = lgamma(y + x) - lgamma(x), 12 lgr_eval(lgr_one(), y) = log(y!),

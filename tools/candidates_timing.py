@@ -3,6 +3,13 @@ the same computation written as vectorised numpy.
 
     python3 tools/candidates_timing.py [--shapes 2000000x8,250000x8] [--reps 7] [--out FILE] [--no-host]
     python3 tools/candidates_timing.py --merge-stats KERNEL_STATS.csv --out FILE      # append rocprofv3's per-kernel figures
+    python3 tools/candidates_timing.py --method hmp ...                               # time method = "hmp" (default "min")
+    python3 tools/candidates_timing.py --ab [--parent-lib OLD.so] --out FILE          # A/B lines instead, see below
+
+--ab: in one process, alternating within each repeat, device events around the raw C-ABI calls on buffers allocated once:
+(a) method "min" through chicdiff_hip_candidate_interactions_dev of this build against the same entry point of --parent-lib (an
+earlier build of the library, loaded beside this one with a context of its own on the same stream), and (b) "hmp" against "min"
+through chicdiff_hip_candidate_interactions_method_dev of this build.  One JSON line per shape with the repeats, medians and ranges.
 
 Geometry: the synthetic generator's of tests/assemble_inputs.py — peaks on an 840 001-fragment map, the device's own region
 universe with RUexpand = 5 as the region table (one region per peak, span <= 10), handed over in random row order; S log-normal
@@ -29,6 +36,9 @@ ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--out", default=None)
 ap.add_argument("--no-host", action="store_true")
 ap.add_argument("--merge-stats", default=None)
+ap.add_argument("--method", default="min", choices=["min", "hmp"])
+ap.add_argument("--ab", action="store_true")
+ap.add_argument("--parent-lib", default=None)
 args = ap.parse_args()
 
 
@@ -116,14 +126,61 @@ def numpy_form(bait, minOE, maxOE, p, pb, po, scores, nc1, score, pvcut, mind):
     return int(keep.sum()), int(deg[has][keep].sum())
 
 
+def ab(ctx, d, S, shape):
+    """The A/B lines of --ab for one shape."""
+    import ctypes as C
+    nc1, P, nreg = S // 2, d["peak_baitID"].numel(), d["baitID"].numel()
+    dev = ctx.device
+    gpeak, gptr = torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P + 1, dtype=torch.int64, device=dev)
+    gmin, gdelta = (torch.empty(P, dtype=torch.float64, device=dev) for _ in range(2))
+    pairs = torch.empty(16 * P, dtype=torch.int32, device=dev)
+    ng, npairs = C.c_int64(0), C.c_int64(0)
+    head = [d[k].data_ptr() for k in ("baitID", "minOE", "maxOE", "p")] + [nreg] + [d[k].data_ptr() for k in ("peak_baitID", "peak_oeID", "scores")] + [
+        P, S, nc1, S - nc1, 0, SCORE, PVCUT, MIND]
+    tail = [pairs.numel(), gpeak.data_ptr(), gptr.data_ptr(), gmin.data_ptr(), gdelta.data_ptr(), pairs.data_ptr(), C.byref(ng), C.byref(npairs)]
+    runs = {"min_old_entry": lambda: ctx.lib.chicdiff_hip_candidate_interactions_dev(ctx.h, *head, *tail),
+            "min": lambda: ctx.lib.chicdiff_hip_candidate_interactions_method_dev(ctx.h, *head, 0, *tail),
+            "hmp": lambda: ctx.lib.chicdiff_hip_candidate_interactions_method_dev(ctx.h, *head, 1, *tail)}
+    if args.parent_lib:
+        old = C.CDLL(os.path.abspath(args.parent_lib))
+        old.chicdiff_hip_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32]
+        old.chicdiff_hip_set_stream.argtypes = [C.c_void_p, C.c_void_p]
+        old.chicdiff_hip_destroy.argtypes = [C.c_void_p]
+        old.chicdiff_hip_candidate_interactions_dev.argtypes = ctx.lib.chicdiff_hip_candidate_interactions_dev.argtypes
+        oh = C.c_void_p()
+        assert old.chicdiff_hip_create(C.byref(oh), 0) == 0
+        assert old.chicdiff_hip_set_stream(oh, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)) == 0
+        runs["min_parent_lib"] = lambda: old.chicdiff_hip_candidate_interactions_dev(oh, *head, *tail)
+    ms, counts = {k: [] for k in runs}, {}
+    for rep_ in range(args.reps + 2):   # two warm-up rounds
+        for k, f in runs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            rc = f()
+            e1.record()
+            torch.cuda.synchronize()
+            assert rc == 0, (k, rc)
+            counts[k] = [ng.value, npairs.value]
+            if rep_ >= 2:
+                ms[k].append(e0.elapsed_time(e1))
+    emit(dict(ab=True, shape=shape, regions=nreg, peaks=P, reps=args.reps, order=list(runs), counts=counts, events_ms=ms,
+              median_ms={k: float(np.median(v)) for k, v in ms.items()}, range_ms={k: [min(v), max(v)] for k, v in ms.items()}))
+    if args.parent_lib:
+        old.chicdiff_hip_destroy(oh)
+
+
 ctx = hip.HipContext(0)
-ctx.enable_timing(True)
+ctx.enable_timing(not args.ab)
 for shape in args.shapes.split(","):
     n, S = (int(x) for x in shape.split("x"))
     d = make(ctx, n, S)
+    if args.ab:
+        ab(ctx, d, S, shape)
+        del d
+        continue
     nc1 = S // 2
     call = lambda: ctx.candidate_interactions(d["baitID"], d["minOE"], d["maxOE"], d["p"], d["peak_baitID"], d["peak_oeID"], d["scores"],
-                                              nc1, S - nc1, False, SCORE, PVCUT, MIND)
+                                              nc1, S - nc1, False, SCORE, PVCUT, MIND, method=args.method)
     for _ in range(2 if args.reps > 1 else 0):
         call()
     events, kernels = [], []
@@ -137,7 +194,7 @@ for shape in args.shapes.split(","):
         kernels.append(ctx.last_candidates_ms)
     nreg, P = d["baitID"].numel(), d["peak_baitID"].numel()
     nsel = int((d["scores"] > SCORE).any(dim=0).sum())
-    line = dict(shape=shape, regions=nreg, peaks=P, selected=nsel, ngroups=r["ngroups"], npairs=r["npairs"], reps=args.reps,
+    line = dict(shape=shape, method=args.method, regions=nreg, peaks=P, selected=nsel, ngroups=r["ngroups"], npairs=r["npairs"], reps=args.reps,
                 events_ms=events, kernels_ms=kernels, events_median_ms=float(np.median(events)), kernels_median_ms=float(np.median(kernels)),
                 kernels_min_ms=min(kernels), kernels_max_ms=max(kernels),
                 # cand_overlap_kernel: per region key 8 + row 4 + maxOE 4 + p 8 read; per selected peak key 8 + row 4 + delta 8 read and
