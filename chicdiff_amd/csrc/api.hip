@@ -2187,6 +2187,68 @@ extern "C" int chicdiff_hip_chicago_tables_caps(int32_t *max_pairs, int32_t *max
     return CHICDIFF_OK;
 }
 
+// countput of one condition (chicdiff.R:708-735, 754-768): key pass, sort, heads, scan and reduce enqueued behind one another; the one
+// host stop is the read of the two counts
+extern "C" int chicdiff_hip_countput_dev(chicdiff_hip_ctx *c, int32_t nrep, const int32_t *const *d_bait, const int32_t *const *d_oe,
+                                         const int32_t *const *d_N, const double *const *d_Bmean, const double *const *d_score,
+                                         const double *const *d_distSign, const int64_t *nrows, int32_t id_min, int32_t nid,
+                                         const int64_t *d_midsum, const int32_t *d_chr, int32_t *d_out_bait, int32_t *d_out_oe,
+                                         double *d_Nav, double *d_Bav, double *d_out_score, double *d_mid, int64_t *ngroups_host) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (ngroups_host) *ngroups_host = 0;
+    if (nrep < 1 || nrep > CHICDIFF_COUNTPUT_MAX_REP)
+        return fail(c, CHICDIFF_E_INVALID, "countput: nrep = %d replicates (1 <= nrep <= %d: the capacity of the LDS table)", (int)nrep,
+                    CHICDIFF_COUNTPUT_MAX_REP);
+    if (!d_bait || !d_oe || !d_N || !d_Bmean || !d_score || !d_distSign || !nrows || !d_midsum || !d_chr || !ngroups_host)
+        return fail(c, CHICDIFF_E_INVALID, "countput: bad arguments (a NULL pointer)");
+    if (nid < 1) return fail(c, CHICDIFF_E_INVALID, "countput: nid = %d (an empty restriction map)", (int)nid);
+    if ((int64_t)id_min + (int64_t)nid > (int64_t)INT32_MAX)
+        return fail(c, CHICDIFF_E_INVALID, "countput: id_min + nid = %lld (map IDs must lie below INT32_MAX = 2147483647: the all-ones key marks "
+                    "a dropped row)", (long long)id_min + (long long)nid);
+    std::vector<CountputRep> reps((size_t)nrep);
+    int64_t n = 0;
+    for (int r = 0; r < nrep; r++) {
+        if (nrows[r] < 0) return fail(c, CHICDIFF_E_INVALID, "countput: nrows[%d] = %lld (a negative number of rows)", r, (long long)nrows[r]);
+        if (nrows[r] > 0 && (!d_bait[r] || !d_oe[r] || !d_N[r] || !d_Bmean[r] || !d_score[r] || !d_distSign[r]))
+            return fail(c, CHICDIFF_E_INVALID, "countput: replicate %d has %lld rows and a NULL column", r, (long long)nrows[r]);
+        reps[r].bait = d_bait[r]; reps[r].oe = d_oe[r]; reps[r].N = d_N[r];
+        reps[r].Bmean = d_Bmean[r]; reps[r].score = d_score[r]; reps[r].distSign = d_distSign[r];
+        reps[r].offset = n;
+        n += nrows[r];
+        if (n >= (1ll << 31))
+            return fail(c, CHICDIFF_E_INVALID, "countput: the replicates hold %lld rows or more up to replicate %d (sum of nrows < 2^31: the "
+                        "global row is a 32-bit sort value)", (long long)n, r);
+    }
+    if (n == 0) return CHICDIFF_OK;
+    if (!d_out_bait || !d_out_oe || !d_Nav || !d_Bav || !d_out_score || !d_mid)
+        return fail(c, CHICDIFF_E_INVALID, "countput: bad arguments (a NULL output)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_aux(c, countput_workspace_bytes(n))) return rc;
+    CountputArgs a;
+    a.nrep = nrep; a.reps = reps.data(); a.n = n; a.id_min = id_min; a.nid = nid; a.midsum = d_midsum; a.chr = d_chr;
+    a.out_bait = d_out_bait; a.out_oe = d_out_oe; a.Nav = d_Nav; a.Bav = d_Bav; a.score = d_out_score; a.mid = d_mid;
+    const CountputResult *d_res = nullptr;
+    timing_reset(c);
+    {
+        Scope t(c, "countput");
+        if (launch_countput(a, c->aux, c->stream, &d_res)) return fail(c, CHICDIFF_E_HIP, "countput: copy/sort/scan failed");
+    }
+    CountputResult h;
+    HIPCHK(c, hipMemcpyAsync(&h, d_res, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    timing_collect(c);
+    *ngroups_host = (int64_t)h.ngroups;
+    return CHICDIFF_OK;
+}
+
+extern "C" int chicdiff_hip_countput_caps(int32_t *max_rep, int32_t *key_rows_per_workgroup, int32_t *reduce_rows_per_workgroup) {
+    if (max_rep) *max_rep = CHICDIFF_COUNTPUT_MAX_REP;
+    if (key_rows_per_workgroup) *key_rows_per_workgroup = CHICDIFF_COUNTPUT_KEY_ROWS_PER_WORKGROUP;
+    if (reduce_rows_per_workgroup) *reduce_rows_per_workgroup = CHICDIFF_COUNTPUT_REDUCE_ROWS_PER_WORKGROUP;
+    return CHICDIFF_OK;
+}
+
 extern "C" int chicdiff_hip_count_table_dev(chicdiff_hip_ctx *c, const int32_t *d_bait, const int32_t *d_oe, const int32_t *d_N,
                                             int64_t nrows, const uint8_t *d_bait_in_RU, int32_t max_id, int64_t *d_keys,
                                             int32_t *d_vals, int64_t *nkeys_host) {

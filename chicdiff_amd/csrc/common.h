@@ -384,6 +384,28 @@ struct ChicagoArgs {
 };
 size_t chicago_workspace_bytes(int32_t nid);
 void launch_chicago_tables(const ChicagoArgs &a, int stage, int merge, char *ws, hipStream_t st, const uint32_t **status_out);
+// countput_kernels.hip — countput of one condition (chicdiff.R:708-735, 754-768)
+struct CountputRep {                                   // one replicate's columns (device pointers) and its first global row
+    const int32_t *bait, *oe, *N;
+    const double *Bmean, *score, *distSign;
+    int64_t offset;
+};
+struct CountputArgs {
+    int32_t nrep;
+    const CountputRep *reps;                           // HOST, nrep entries; must stay alive until the stream has been synchronised
+    int64_t n;                                         // sum of the replicates' rows, 1 <= n < 2^31
+    int32_t id_min, nid;
+    const int64_t *midsum;
+    const int32_t *chr;
+    int32_t *out_bait, *out_oe;                        // n entries each, the first ngroups written
+    double *Nav, *Bav, *score, *mid;
+};
+// what the host reads back
+struct CountputResult {
+    unsigned long long nkept, ngroups;
+};
+size_t countput_workspace_bytes(int64_t n);
+int launch_countput(const CountputArgs &a, char *ws, hipStream_t st, const CountputResult **res_out);
 void launch_math_selftest(int op, const double *x, int64_t n, double *out, hipStream_t st);
 void launch_math3_selftest(int op, const double *x, const double *y, int64_t n, const double *logfact, double *out, double *out2, hipStream_t st);
 // the dispersion objective on its own (disp_kernels.hip, objective_probe_kernel): K points a[i * K + k] per row of a prepared fit

@@ -28,7 +28,7 @@ EXPORTS = [
     "chicdiff_hip_fragment_background_dev", "chicdiff_hip_bh_adjust_dev", "chicdiff_hip_ihw_apply_dev",
     "chicdiff_hip_region_universe_count_dev", "chicdiff_hip_region_universe_fill_dev", "chicdiff_hip_region_universe_dev", "chicdiff_hip_count_table_dev",
     "chicdiff_hip_candidate_interactions_dev", "chicdiff_hip_candidate_interactions_method_dev", "chicdiff_hip_selftest_landau_dev", "chicdiff_hip_chicago_tables_dev", "chicdiff_hip_chicago_tables_caps",
-    "chicdiff_hip_control_draws_dev",
+    "chicdiff_hip_control_draws_dev", "chicdiff_hip_countput_dev", "chicdiff_hip_countput_caps",
     "chicdiff_hip_chinput_read", "chicdiff_hip_chinput_table_dev", "chicdiff_hip_region_avdist_dev",
     "chicdiff_hip_count_join_inner_dev", "chicdiff_hip_count_join_multi_dev", "chicdiff_hip_region_assemble_dev",
     "chicdiff_hip_malloc", "chicdiff_hip_free", "chicdiff_hip_outstanding_allocations", "chicdiff_hip_memcpy_h2d", "chicdiff_hip_memcpy_d2h",
@@ -150,6 +150,8 @@ def load_library() -> C.CDLL:
     L.chicdiff_hip_chicago_tables_caps.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.chicdiff_hip_control_draws_dev.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, vp, i64, C.POINTER(i32), C.POINTER(i32), i32, C.c_uint64,
                                                  vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
+    L.chicdiff_hip_countput_dev.argtypes = [vp, i32] + [C.POINTER(vp)] * 6 + [C.POINTER(i64), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
+    L.chicdiff_hip_countput_caps.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.chicdiff_hip_nbglm_fit_dev.argtypes = [vp, vp, vp, i64, i32, C.POINTER(i32), C.POINTER(Opts), C.POINTER(Out),
                                              C.POINTER(Scalars)]
     L.chicdiff_hip_nbglm_fit.argtypes = L.chicdiff_hip_nbglm_fit_dev.argtypes
@@ -186,6 +188,14 @@ def chicago_tables_caps() -> dict:
     a, b, r = C.c_int32(0), C.c_int32(0), C.c_int32(0)
     load_library().chicdiff_hip_chicago_tables_caps(C.byref(a), C.byref(b), C.byref(r))
     return dict(max_pairs=a.value, max_distbin=b.value, rows_per_workgroup=r.value)
+
+
+def countput_caps() -> dict:
+    """The limits of ``HipContext.countput`` as the library was built (include/chicdiff_hip.h, CHICDIFF_COUNTPUT_*): the most replicates
+    of one condition, and the consecutive rows a workgroup takes in the key pass and in the heads / reduce passes."""
+    m, k, r = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    load_library().chicdiff_hip_countput_caps(C.byref(m), C.byref(k), C.byref(r))
+    return dict(max_rep=m.value, key_rows_per_workgroup=k.value, reduce_rows_per_workgroup=r.value)
 
 
 def _scalars_dict(s: Scalars) -> dict:
@@ -717,6 +727,52 @@ class HipContext:
         kt = self.kernel_times()
         self.last_chicago_tables_ms = {k[len("chicago_tables_"):]: v[0] for k, v in kt.items() if k.startswith("chicago_tables_")}
         return ref, bool(flag.value)
+
+    # -- countput ---------------------------------------------------------------------------------
+    def countput(self, reps, id_min, d_midsum, d_chr):
+        """countput of ONE condition (chicdiff.R:708-735, 754-768; the rule is above chicdiff_hip_countput_dev in
+        include/chicdiff_hip.h): ``reps`` = [(baitID, otherEndID, N, Bmean, score, distSign)] per replicate, in the order the rows
+        are to be stacked — int32, int32, int32, float64, float64, float64 device tensors of one length per replicate (0 rows are
+        fine).  The map: ``id_min``, ``d_midsum`` int64 (nid,), ``d_chr`` int32 (nid,), -1 = not on the map.
+
+        Returns dict(baitID, otherEndID, Nav, Bav, score, oeID_mid): one entry per (baitID, otherEndID) group in order of first
+        appearance, int32 / float64 device tensors — pipeline._countput's frame for that condition, bit for bit."""
+        torch = self.torch
+        reps = [tuple(r) for r in reps]
+        caps = countput_caps()
+        if not 1 <= len(reps) <= caps["max_rep"]:
+            raise ValueError(f"countput: 1 <= replicates <= {caps['max_rep']} are supported, got {len(reps)}")
+        dtypes = (torch.int32, torch.int32, torch.int32, torch.float64, torch.float64, torch.float64)
+        names = ("baitID", "otherEndID", "N", "Bmean", "score", "distSign")
+        for r, cols in enumerate(reps):
+            if len(cols) != 6:
+                raise ValueError(f"countput: replicate {r} must be (baitID, otherEndID, N, Bmean, score, distSign), got {len(cols)} columns")
+            self._check_tensor(f"reps[{r}].baitID", cols[0], torch.int32, (-1,))
+            for name, t, dt in zip(names[1:], cols[1:], dtypes[1:]):
+                self._check_tensor(f"reps[{r}].{name}", t, dt, (cols[0].numel(),))
+        self._check_tensor("d_midsum", d_midsum, torch.int64, (-1,))
+        nid = d_midsum.numel()
+        if nid < 1:
+            raise ValueError("d_midsum: empty restriction map")
+        self._check_tensor("d_chr", d_chr, torch.int32, (nid,))
+        nrep = len(reps)
+        n = sum(cols[0].numel() for cols in reps)
+        if n >= 1 << 31:
+            raise ValueError(f"countput: the replicates of one condition must hold fewer than 2^31 rows together, got {n}")
+        ptrs = [(C.c_void_p * nrep)(*[cols[k].data_ptr() if cols[k].numel() else None for cols in reps]) for k in range(6)]
+        nrows = (C.c_int64 * nrep)(*[cols[0].numel() for cols in reps])
+        ob, oo = (torch.empty(n, dtype=torch.int32, device=self.device) for _ in range(2))
+        nav, bav, sc, mid = (torch.empty(n, dtype=torch.float64, device=self.device) for _ in range(4))
+        g = C.c_int64(0)
+        self._check(self.lib.chicdiff_hip_countput_dev(
+            self.h, nrep, *ptrs, nrows, int(id_min), nid, d_midsum.data_ptr(), d_chr.data_ptr(), ob.data_ptr(), oo.data_ptr(),
+            nav.data_ptr(), bav.data_ptr(), sc.data_ptr(), mid.data_ptr(), C.byref(g)))
+        self.last_countput_ms = self.kernel_times().get("countput", (0.0, 0))[0]
+        k = g.value
+        out = dict(baitID=ob[:k], otherEndID=oo[:k], Nav=nav[:k], Bav=bav[:k], score=sc[:k], oeID_mid=mid[:k])
+        if 2 * k < n:   # (a view would pin the whole n-entry allocation)
+            out = {name: t.clone() for name, t in out.items()}
+        return out
 
     # -- a6 + a7 ----------------------------------------------------------------------------
     def nbglm_fit(self, d_counts, d_nf, group, want=None, opts: Opts | None = None, outputs: dict | None = None):

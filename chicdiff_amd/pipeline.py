@@ -338,7 +338,41 @@ def _countput(xs, conditions, rmap):
     return pd.concat(out, ignore_index=True)
 
 
-def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, read_chicago=None, assemble=False, device_tables=False):
+def countput_dev(xs, conditions, ctx, id_min, midsum, chr_codes, id_columns=None):
+    """``_countput`` on the device (HipContext.countput, one call per condition in ``dict.fromkeys(conditions)`` order): the same
+    DataFrame — columns, dtypes, row order, ``condition`` — with Nav, Bav, score and oeID_mid equal bit for bit.  ``midsum`` /
+    ``chr_codes``: ``_rmap_tables``' dense per-ID tables (host arrays or device tensors); ``id_columns``: [(baitID, otherEndID)] per
+    replicate as int32 device tensors, when the caller has uploaded them already.  The rule (rows kept, Kahan means in row order,
+    strict maximum, groups in order of first appearance) is above chicdiff_hip_countput_dev in include/chicdiff_hip.h."""
+    import pandas as pd
+    torch = ctx.torch
+    dev = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, dtype=t)).to(ctx.device)
+    d_midsum = midsum if isinstance(midsum, torch.Tensor) else dev(midsum, np.int64)
+    d_chr = chr_codes if isinstance(chr_codes, torch.Tensor) else dev(chr_codes, np.int32)
+    out = []
+    for cond in dict.fromkeys(conditions):
+        reps, id_dtypes = [], []
+        for s, (x, c) in enumerate(zip(xs, conditions)):
+            if c != cond:
+                continue
+            sc = "newScore" if "newScore" in x.columns else "score"
+            d_bait, d_oe = id_columns[s] if id_columns is not None else (dev(x["baitID"].to_numpy(), np.int32), dev(x["otherEndID"].to_numpy(), np.int32))
+            reps.append((d_bait, d_oe, dev(x["N"].to_numpy(), np.int32), dev(x["Bmean"].to_numpy(np.float64), np.float64),
+                         dev(x[sc].to_numpy(np.float64), np.float64), dev(x["distSign"].to_numpy(np.float64), np.float64)))
+            id_dtypes.append((x["baitID"].dtype, x["otherEndID"].dtype))
+        r = ctx.countput(reps, id_min, d_midsum, d_chr)
+        host = {k: v.cpu().numpy() for k, v in r.items()}
+        # the twin's ID dtypes: as the replicates carry them (the inner merge with the map keeps the left key column's)
+        z = pd.DataFrame({"baitID": host["baitID"].astype(np.result_type(*[b for b, _ in id_dtypes])),
+                          "otherEndID": host["otherEndID"].astype(np.result_type(*[o for _, o in id_dtypes])),
+                          "Nav": host["Nav"], "Bav": host["Bav"], "score": host["score"], "oeID_mid": host["oeID_mid"]})
+        z["condition"] = cond
+        out.append(z)
+    return pd.concat(out, ignore_index=True)
+
+
+def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, read_chicago=None, assemble=False, device_tables=False,
+                      device_countput=False):
     """chicdiff.R:1460-1478 with the device path behind it: list(test block, control block, countput).  Every Chicago
     data set and every chinput file is read ONCE for both universes (what ``parallel = TRUE`` -> getFullRegionData2,
     :948-1456, does in the reference; the result does not depend on it).  The long "recast" table (one row per region,
@@ -347,7 +381,9 @@ def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, rea
     ``assemble=True`` (chinput branch only): a block holds the region-level ``regionN`` / ``regionFullMean`` (S, n) that DESeq2Wrap
     would sum from the fragment columns — from one kernel (HipContext.region_assemble), same bits — and no fragment columns.
     ``device_tables=True``: the Chicago background tables are built on the device (``background_tables_dev``) instead of by pandas
-    and uploaded — same bits; without countData the uploaded ID columns also feed ``ctx.count_table``."""
+    and uploaded — same bits; without countData the uploaded ID columns also feed ``ctx.count_table``.
+    ``device_countput=True``: countput is aggregated on the device (``countput_dev``) instead of by the pandas groupby — the same frame,
+    bit for bit and in the same row order."""
     s = asChicdiffSettings(chicdiff_settings)
     if assemble and s["countData"] is None:
         raise ValueError("getFullRegionData(assemble=True) covers the chinput branch only: without countData the counts are "
@@ -378,7 +414,10 @@ def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, rea
         bg = background_tables(xs, id_min, nid)
     bg.update(id_min=id_min, midsum=midsum)
     message("Saving counts\n")
-    countput = _countput(xs, conditions, rmap)
+    if device_countput:
+        countput = countput_dev(xs, conditions, ctx, id_min, midsum, chr_codes, id_columns=d_ids)
+    else:
+        countput = _countput(xs, conditions, rmap)
     countput.to_csv(f"{s['outprefix']}_countput.csv", index=False)                 # the reference: saveRDS(_countput.Rds), :769
 
     universes = [RU, RUcontrol]

@@ -535,6 +535,54 @@ int chicdiff_hip_chicago_tables_dev(chicdiff_hip_ctx *ctx, const int32_t *d_bait
                                     int32_t *d_tlb_of, double *d_T, double *d_ref, int32_t *status_host);
 int chicdiff_hip_chicago_tables_caps(int32_t *max_pairs, int32_t *max_distbin, int32_t *rows_per_workgroup);
 
+/* limits of chicdiff_hip_countput_dev (below) */
+#define CHICDIFF_COUNTPUT_MAX_REP 64                     /* replicates of one condition: their row offsets are kept per workgroup in LDS */
+#define CHICDIFF_COUNTPUT_KEY_ROWS_PER_WORKGROUP 1024    /* consecutive rows a workgroup of the key pass takes */
+#define CHICDIFF_COUNTPUT_REDUCE_ROWS_PER_WORKGROUP 256  /* consecutive sorted positions a workgroup of the heads / reduce passes takes */
+/* countput of ONE condition (chicdiff.R:708-735 the rows kept per replicate, :754-768 the aggregation): per observed (baitID,
+ * otherEndID) pair the mean N, the mean Bmean, the largest score and the other end's midpoint — what plotDiffBaits() draws.  Equal,
+ * bit for bit and in row order, to the host twin (chicdiff_amd.pipeline._countput, a pandas groupby); the rule, stated in full:
+ *
+ * Take the condition's replicates in the order given and concatenate their rows: global row index g, replicate 0's rows first, each
+ * replicate in its own row order.
+ *   rows kept    a row is kept when its distSign is not NaN (:715) AND its otherEndID is on the map, that is inside
+ *                [id_min, id_min + nid) with d_chr[otherEndID - id_min] >= 0 (the inner merge with the map, :724).  baitID is NOT
+ *                filtered.
+ *   groups       kept rows with equal (baitID, otherEndID) form a group, within and across replicates (a pair repeated inside one
+ *                replicate is legal and joins the same group).
+ *   Nav, Bav     over the group's rows in ascending g; Nav from N (int32 converted to double, never NA), Bav from Bmean.  A NaN value
+ *                is skipped; otherwise
+ *                    cnt += 1;  y = v - c;  t = s + y;  c = (t - s) - y;  if (c != c) c = 0;  s = t          (s = c = 0 at the start)
+ *                and the result is s / cnt, NaN when cnt = 0: a Kahan sum in row order, divided once.  Plain fp64, no reassociation,
+ *                no contraction.  The reset of c is what keeps [inf, 1, 2] at inf (c would be NaN from the second row on).
+ *   score        NaN is skipped; the first non-NaN value starts the maximum, and a later value replaces it only when it is STRICTLY
+ *                greater: of 0.0 and -0.0 the earlier one stays.  NaN when the group has no value.
+ *   oeID_mid     (start + end) / 2 of the other end = d_midsum[otherEndID - id_min] / 2.0, exact.
+ *   order        groups are ordered by the smallest g in them (first appearance) — the twin's order (groupby(sort = False)).  The
+ *                reference's own order differs: its merge(x, rmap_copy, by = "otherEndID") re-keys each replicate by otherEndID before
+ *                the rows are stacked.  Nothing downstream reads the order (plotDiffBaits subsets by bait).
+ * mean and max follow the twin, which is the project's statement of this stage: R's mean() carries a NA through and its max() has no
+ * na.rm here; both are kept as the twin has them.
+ *
+ * Inputs: nrep replicates; d_bait, d_oe, d_N, d_Bmean, d_score, d_distSign are HOST arrays of nrep entries with device pointers
+ * inside (as the key tables of chicdiff_hip_count_join_multi_dev): int32 baitID, otherEndID, N and double Bmean, score, distSign (NaN =
+ * NA), nrows[r] entries each (nrows: HOST, int64[nrep]; a replicate with 0 rows is valid and its pointers are not read).  The map:
+ * id_min, nid, d_midsum (int64[nid]), d_chr (int32[nid], -1 = not on the map).
+ * Outputs (device), room for sum(nrows) entries each, the first *ngroups_host written: d_out_bait, d_out_oe (int32), d_Nav, d_Bav,
+ * d_out_score, d_mid (double).  They may be NULL when sum(nrows) = 0.
+ * No value passes through an atomic; launch shape, workgroup size and arrival order do not show in any bit.  Everything is enqueued
+ * on the context's stream; the one host stop is the read of the count.
+ * CHICDIFF_E_INVALID, the message naming the limit: nrep < 1 or nrep > CHICDIFF_COUNTPUT_MAX_REP; nid < 1; id_min + nid > INT32_MAX
+ * (a map ID of INT32_MAX: the all-ones sort key marks a dropped row); a negative nrows[r]; sum(nrows) >= 2^31 (g is a 32-bit sort
+ * value).  sum(nrows) = 0 and every row dropped: CHICDIFF_OK with *ngroups_host = 0.
+ * chicdiff_hip_countput_caps: the three constants above, as the library was built (any pointer may be NULL). */
+int chicdiff_hip_countput_dev(chicdiff_hip_ctx *ctx, int32_t nrep, const int32_t *const *d_bait, const int32_t *const *d_oe,
+                              const int32_t *const *d_N, const double *const *d_Bmean, const double *const *d_score,
+                              const double *const *d_distSign, const int64_t *nrows, int32_t id_min, int32_t nid,
+                              const int64_t *d_midsum, const int32_t *d_chr, int32_t *d_out_bait, int32_t *d_out_oe, double *d_Nav,
+                              double *d_Bav, double *d_out_score, double *d_mid, int64_t *ngroups_host);
+int chicdiff_hip_countput_caps(int32_t *max_rep, int32_t *key_rows_per_workgroup, int32_t *reduce_rows_per_workgroup);
+
 /* a6 + a7 — estimateDispersions + nbinomWaldTest (chicdiff.R:1573-1574, 1602-1603, 1643-1644,
  * 1673-1674) for design ~condition (group[j] in {0,1}, both present) or ~1 (all group[j]==0).
  * d_nf = normalizationFactors (n x S).  `group` is a HOST array of S ints. */
