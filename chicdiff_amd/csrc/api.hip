@@ -31,6 +31,16 @@ struct ChinputCols {
     std::string error;
 };
 int64_t chinput_parse(const char *path, int nthreads, ChinputCols &c);
+struct ChinputFile {
+    const char *base = nullptr;
+    size_t size = 0, body = 0;
+    int ib = -1, io = -1, in = -1;
+    std::string error;
+};
+int chinput_open(const char *path, ChinputFile &f);
+void chinput_close(ChinputFile &f);
+std::string chinput_malformed(long long offset);
+hipError_t chinput_upload(const ChinputFile &f, char *d_text, char *pin, size_t half_bytes, int nthreads, hipStream_t st, hipEvent_t ev[2]);
 }  // namespace cd
 
 struct KTimer {
@@ -90,6 +100,13 @@ struct chicdiff_hip_ctx {
     char *io_dev = nullptr, *io_pin = nullptr;
     size_t io_dev_bytes = 0, io_pin_bytes = 0;
     ChinputCols *chin = nullptr;            // columns of the .chinput file read last (chicdiff_hip_chinput_read)
+    // chicdiff_hip_chinput_read_dev: the body's text and the three columns on the device (grow-only, apart from aux and the io arena:
+    // chicdiff_hip_count_table_dev's workspace must not overwrite the columns), and the two halves of the pinned staging area
+    char *chin_text = nullptr, *chin_pin = nullptr;
+    int32_t *chin_cols = nullptr;
+    size_t chin_text_bytes = 0, chin_pin_half = 0, chin_cols_rows = 0;
+    hipEvent_t chin_ev[2] = {nullptr, nullptr};
+    int64_t chin_dev_rows = -1;             // >= 0: the read that came last was a device read of this many rows (chin_cols holds them)
     // host-buffer entry point: columns that are final once the MAP dispersions exist leave for the host on a second
     // stream while the Wald stage runs (set for the duration of one chicdiff_hip_nbglm_fit call)
     struct EarlyCopy {
@@ -286,6 +303,11 @@ void chicdiff_hip_destroy(chicdiff_hip_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     delete c->chin;
+    if (c->chin_text) (void)hipFree(c->chin_text);
+    if (c->chin_cols) (void)hipFree(c->chin_cols);
+    if (c->chin_pin) (void)hipHostFree(c->chin_pin);
+    for (hipEvent_t e : c->chin_ev)
+        if (e) (void)hipEventDestroy(e);
     for (void *p : c->user_allocs) (void)hipFree(p);
     c->user_allocs.clear();
     if (c->io_dev) (void)hipFree(c->io_dev);
@@ -2402,12 +2424,151 @@ extern "C" int chicdiff_hip_chinput_read(chicdiff_hip_ctx *c, const char *path, 
     if (!c->chin) c->chin = new ChinputCols();
     const int64_t n = chinput_parse(path, nthreads > 0 ? nthreads : c->host.host_copy_threads, *c->chin);
     if (n < 0) return fail(c, CHICDIFF_E_INVALID, "chinput_read: %s", c->chin->error.c_str());
+    c->chin_dev_rows = -1;
     *nrows_host = n;
+    return CHICDIFF_OK;
+}
+
+extern "C" int chicdiff_hip_chinput_caps(int32_t *tile_bytes, int32_t *lane_bytes, int32_t *window_bytes) {
+    if (tile_bytes) *tile_bytes = CHICDIFF_CHINPUT_TILE_BYTES;
+    if (lane_bytes) *lane_bytes = CHICDIFF_CHINPUT_LANE_BYTES;
+    if (window_bytes) *window_bytes = CHICDIFF_CHINPUT_WINDOW_BYTES;
+    return CHICDIFF_OK;
+}
+
+// f2, text part on the device (chinput_kernels.hip): mark pass, scan, host stop for the row count, parse pass, host stop for the verdict.
+// `what` names the entry point in messages; file_offset = the body's place in its file (what a reported offset counts from).
+static int chinput_parse_impl(chicdiff_hip_ctx *c, const char *what, const uint8_t *d_text, int64_t nbytes, int ib, int io, int in,
+                              int32_t *d_bait, int32_t *d_oe, int32_t *d_N, int64_t cap, bool grow_cols, int64_t file_offset,
+                              int64_t *nrows_host, int64_t *bad_offset_host) {
+    *nrows_host = 0;
+    if (bad_offset_host) *bad_offset_host = -1;
+    if (nbytes == 0) return CHICDIFF_OK;
+    if (int rc = ensure_aux(c, chinput_workspace_bytes(nbytes))) return rc;
+    const int64_t *d_nrows = nullptr;
+    const unsigned long long *d_bad = nullptr;
+    {
+        Scope t(c, "chinput_mark");
+        if (launch_chinput_count(d_text, nbytes, c->aux, c->stream, &d_nrows, &d_bad)) return fail(c, CHICDIFF_E_HIP, "%s: memset failed", what);
+    }
+    {
+        Scope t(c, "chinput_scan");
+        if (launch_chinput_scan(nbytes, c->aux, c->stream)) return fail(c, CHICDIFF_E_HIP, "%s: scan failed", what);
+    }
+    int64_t nrows = 0;
+    HIPCHK(c, hipMemcpyAsync(&nrows, d_nrows, sizeof nrows, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    *nrows_host = nrows;
+    if (grow_cols) {  // the context's columns: room for the rows now that their number is known
+        if (c->chin_cols_rows < (size_t)nrows) {
+            if (c->chin_cols) { (void)hipFree(c->chin_cols); c->chin_cols = nullptr; c->chin_cols_rows = 0; }
+            const size_t rows = ((size_t)nrows + 63) & ~(size_t)63;
+            hipError_t e = hipMalloc((void **)&c->chin_cols, 3 * sizeof(int32_t) * rows);
+            if (e != hipSuccess)
+                return fail(c, CHICDIFF_E_NOMEM, "%s: device columns of %lld rows for a file of %lld bytes: %s", what, (long long)nrows,
+                            (long long)(file_offset + nbytes), hipGetErrorString(e));
+            c->chin_cols_rows = rows;
+        }
+        d_bait = c->chin_cols; d_oe = d_bait + c->chin_cols_rows; d_N = d_oe + c->chin_cols_rows;
+        cap = nrows;
+    }
+    if (nrows > cap) return fail(c, CHICDIFF_E_INVALID, "%s: the text holds %lld rows, the columns have room for %lld", what, (long long)nrows, (long long)cap);
+    if (nrows == 0) return CHICDIFF_OK;  // blank lines only
+    {
+        Scope t(c, "chinput_parse");
+        launch_chinput_parse(d_text, nbytes, ib, io, in, d_bait, d_oe, d_N, cap, c->aux, c->stream);
+    }
+    unsigned long long bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    if (bad != ~0ull) {
+        if (bad_offset_host) *bad_offset_host = (int64_t)bad;
+        return fail(c, CHICDIFF_E_INVALID, "%s: %s", what, chinput_malformed((long long)bad + (long long)file_offset).c_str());
+    }
+    return CHICDIFF_OK;
+}
+
+extern "C" int chicdiff_hip_chinput_parse_dev(chicdiff_hip_ctx *c, const uint8_t *d_text, int64_t nbytes, int32_t ib, int32_t io, int32_t in,
+                                              int32_t *d_bait, int32_t *d_oe, int32_t *d_N, int64_t cap, int64_t *nrows_host,
+                                              int64_t *bad_offset_host) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (!nrows_host || nbytes < 0 || cap < 0 || (nbytes > 0 && !d_text) || (cap > 0 && (!d_bait || !d_oe || !d_N)))
+        return fail(c, CHICDIFF_E_INVALID, "chinput_parse: bad arguments");
+    if (ib < 0 || io < 0 || in < 0 || ib == io || ib == in || io == in)
+        return fail(c, CHICDIFF_E_INVALID, "chinput_parse: columns (%d, %d, %d) must be distinct and not negative", (int)ib, (int)io, (int)in);
+    if ((uintptr_t)d_text & 15) return fail(c, CHICDIFF_E_INVALID, "chinput_parse: d_text must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    const int rc = chinput_parse_impl(c, "chinput_parse", d_text, nbytes, ib, io, in, d_bait, d_oe, d_N, cap, false, 0, nrows_host, bad_offset_host);
+    timing_collect(c);
+    return rc;
+}
+
+extern "C" int chicdiff_hip_chinput_read_dev(chicdiff_hip_ctx *c, const char *path, int64_t *nrows_host) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (!path || !nrows_host) return fail(c, CHICDIFF_E_INVALID, "chinput_read: bad arguments");
+    ChinputFile f;
+    if (chinput_open(path, f) != 0) return fail(c, CHICDIFF_E_INVALID, "chinput_read: %s", f.error.c_str());
+    struct Closer { ChinputFile &f; ~Closer() { chinput_close(f); } } closer{f};
+    const size_t body = f.size - f.body;
+    HIPCHK(c, hipSetDevice(c->device));
+    c->chin_dev_rows = -1;  // nothing to serve until this read has succeeded: an earlier read's columns are given up
+    delete c->chin;
+    c->chin = nullptr;
+    timing_reset(c);
+    if (body > 0) {
+        constexpr size_t kHalfMax = (size_t)64 << 20;  // the pinned area is two halves of at most 64 MiB, whatever the file's size
+        const size_t half = body < kHalfMax ? ((body + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1)) : kHalfMax;
+        hipError_t e = hipSuccess;
+        if (c->chin_text_bytes < body) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (c->chin_text) { (void)hipFree(c->chin_text); c->chin_text = nullptr; c->chin_text_bytes = 0; }
+            const size_t bytes = align256(body);
+            if ((e = hipMalloc((void **)&c->chin_text, bytes)) != hipSuccess)
+                return fail(c, CHICDIFF_E_NOMEM, "chinput_read: device text buffer for a file of %zu bytes: %s", f.size, hipGetErrorString(e));
+            c->chin_text_bytes = bytes;
+        }
+        if (c->chin_pin_half < half) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (c->chin_pin) { (void)hipHostFree(c->chin_pin); c->chin_pin = nullptr; c->chin_pin_half = 0; }
+            if ((e = hipHostMalloc((void **)&c->chin_pin, 2 * half)) != hipSuccess)
+                return fail(c, CHICDIFF_E_NOMEM, "chinput_read: pinned staging of %zu bytes for a file of %zu bytes: %s", 2 * half, f.size,
+                            hipGetErrorString(e));
+            c->chin_pin_half = half;
+        }
+        for (hipEvent_t &ev : c->chin_ev)
+            if (!ev) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        {
+            Scope t(c, "chinput_upload");
+            e = chinput_upload(f, c->chin_text, c->chin_pin, c->chin_pin_half, c->host.host_copy_threads, c->stream, c->chin_ev);
+        }
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(c->stream);  // the staging area may still be read
+            timing_collect(c);
+            return fail(c, CHICDIFF_E_HIP, "chinput_read: upload: %s", hipGetErrorString(e));
+        }
+    }
+    const int rc = chinput_parse_impl(c, "chinput_read", (const uint8_t *)c->chin_text, (int64_t)body, f.ib, f.io, f.in, nullptr, nullptr, nullptr, 0,
+                                      true, (int64_t)f.body, nrows_host, nullptr);
+    if (rc) (void)hipStreamSynchronize(c->stream);
+    timing_collect(c);
+    if (rc) return rc;
+    c->chin_dev_rows = *nrows_host;
     return CHICDIFF_OK;
 }
 extern "C" int chicdiff_hip_chinput_table_dev(chicdiff_hip_ctx *c, const uint8_t *d_bait_in_RU, int32_t max_id, int64_t *d_keys,
                                               int32_t *d_vals, int64_t *nkeys_host) {
     if (!c) return CHICDIFF_E_INVALID;
+    if (c->chin_dev_rows >= 0) {  // the read that came last left its columns on the device
+        if (!nkeys_host) return fail(c, CHICDIFF_E_INVALID, "chinput_table: bad arguments");
+        *nkeys_host = 0;
+        if (c->chin_dev_rows == 0) return CHICDIFF_OK;  // as below: a header without data rows
+        const int32_t *d_b = c->chin_cols;
+        return chicdiff_hip_count_table_dev(c, d_b, d_b + c->chin_cols_rows, d_b + 2 * c->chin_cols_rows, c->chin_dev_rows, d_bait_in_RU, max_id,
+                                            d_keys, d_vals, nkeys_host);
+    }
     if (!c->chin) return fail(c, CHICDIFF_E_INVALID, "chinput_table: nothing read (call chicdiff_hip_chinput_read first)");
     if (!nkeys_host) return fail(c, CHICDIFF_E_INVALID, "chinput_table: bad arguments");
     if (c->chin->bait.empty()) {  // a header without data rows: fread gives an empty table, merge(all.x = TRUE) then N = 0 for every RU row

@@ -7,6 +7,8 @@
 // line boundaries; every thread parses its slice straight into the context's pinned staging area (three int32 columns),
 // which one DMA then moves to the device, where chicdiff_hip_count_table_dev's kernels (bait filter, radix sort) build
 // the key table the count join searches.  No R, no data.table: plain POSIX + std::thread.
+// The opt-in device path (chicdiff_hip_chinput_read_dev) shares the header reading (chinput_open) and sends the body up as text
+// (chinput_upload); chinput_kernels.hip parses it there.
 #include <fcntl.h>
 #include <stdlib.h>
 #include <string.h>
@@ -56,17 +58,31 @@ static inline bool parse_line(const char *p, const char *e, int ib, int io, int 
     return got == 3;
 }
 
-// Parses the whole file with `nthreads` threads.  Returns the row count, or -1 with `err` set.
-int64_t chinput_parse(const char *path, int nthreads, ChinputCols &c) {
+// The file mapped, and what its comment lines and header say: both parsers start here.  body = the bytes after the header line;
+// ib, io, in = the 0-based columns of baitID, otherEndID, N (quoted names and any column order accepted).
+struct ChinputFile {
+    const char *base = nullptr;
+    size_t size = 0, body = 0;  // body: offset of the first byte after the header line
+    int ib = -1, io = -1, in = -1;
+    std::string error;
+};
+
+void chinput_close(ChinputFile &f) {
+    if (f.base) munmap((void *)f.base, f.size);
+    f.base = nullptr;
+}
+
+// Returns 0, or -1 with f.error set (nothing stays mapped then).
+int chinput_open(const char *path, ChinputFile &f) {
     const int fd = open(path, O_RDONLY);
-    if (fd < 0) { c.error = std::string("cannot open ") + path; return -1; }
+    if (fd < 0) { f.error = std::string("cannot open ") + path; return -1; }
     struct stat stt;
-    if (fstat(fd, &stt) != 0) { close(fd); c.error = "fstat failed"; return -1; }
+    if (fstat(fd, &stt) != 0) { close(fd); f.error = "fstat failed"; return -1; }
     const size_t size = (size_t)stt.st_size;
-    if (size == 0) { close(fd); c.error = "empty file"; return -1; }
+    if (size == 0) { close(fd); f.error = "empty file"; return -1; }
     const char *base = (const char *)mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
     close(fd);
-    if (base == MAP_FAILED) { c.error = "mmap failed"; return -1; }
+    if (base == MAP_FAILED) { f.error = "mmap failed"; return -1; }
     const char *end = base + size, *p = base;
     // comment lines, then the header
     auto line_end = [&](const char *s) { const char *q = (const char *)memchr(s, '\n', (size_t)(end - s)); return q ? q : end; };
@@ -77,24 +93,40 @@ int64_t chinput_parse(const char *path, int nthreads, ChinputCols &c) {
         const char *he = e;
         if (he > p && he[-1] == '\r') he--;
         int col = 0;
-        for (const char *f = p; f <= he; col++) {
-            const char *q = f;
+        for (const char *fs = p; fs <= he; col++) {
+            const char *q = fs;
             while (q < he && !is_sep(*q)) q++;
-            std::string name(f, q);
+            std::string name(fs, q);
             if (name.size() >= 2 && name.front() == '"' && name.back() == '"') name = name.substr(1, name.size() - 2);
             if (name == "baitID") ib = col;
             else if (name == "otherEndID") io = col;
             else if (name == "N") in = col;
             if (q >= he) break;
-            f = q + 1;
+            fs = q + 1;
         }
         p = e < end ? e + 1 : end;
     }
     if (ib < 0 || io < 0 || in < 0) {
         munmap((void *)base, size);
-        c.error = "chinput header must name the columns baitID, otherEndID and N";
+        f.error = "chinput header must name the columns baitID, otherEndID and N";
         return -1;
     }
+    f.base = base; f.size = size; f.body = (size_t)(p - base);
+    f.ib = ib; f.io = io; f.in = in;
+    return 0;
+}
+
+std::string chinput_malformed(long long offset) {
+    return "malformed chinput row at byte offset " + std::to_string(offset) + " (baitID, otherEndID and N must be integers)";
+}
+
+// Parses the whole file with `nthreads` threads.  Returns the row count, or -1 with `err` set.
+int64_t chinput_parse(const char *path, int nthreads, ChinputCols &c) {
+    ChinputFile file;
+    if (chinput_open(path, file) != 0) { c.error = file.error; return -1; }
+    const char *base = file.base, *end = base + file.size, *p = base + file.body;
+    const int ib = file.ib, io = file.io, in = file.in;
+    auto line_end = [&](const char *s) { const char *q = (const char *)memchr(s, '\n', (size_t)(end - s)); return q ? q : end; };
     if (nthreads < 1) nthreads = 1;
     const size_t body = (size_t)(end - p);
     if ((size_t)nthreads > body / 65536 + 1) nthreads = (int)(body / 65536 + 1);
@@ -131,10 +163,10 @@ int64_t chinput_parse(const char *path, int nthreads, ChinputCols &c) {
             });
         for (auto &w : th) w.join();
     }
-    munmap((void *)base, size);
+    chinput_close(file);
     for (int t = 0; t < nthreads; t++)
         if (bad[t] >= 0) {
-            c.error = "malformed chinput row at byte offset " + std::to_string(bad[t]) + " (baitID, otherEndID and N must be integers)";
+            c.error = chinput_malformed(bad[t]);
             return -1;
         }
     size_t total = 0;
@@ -148,6 +180,39 @@ int64_t chinput_parse(const char *path, int nthreads, ChinputCols &c) {
         off += tb[t].size();
     }
     return (int64_t)total;
+}
+
+// The body of an open file -> d_text (device), through the two halves of a bounded pinned area: `nthreads` threads copy a chunk from
+// the page cache into one half while the DMA of the other half runs.  ev[h] marks the end of the last DMA out of half h.
+hipError_t chinput_upload(const ChinputFile &f, char *d_text, char *pin, size_t half_bytes, int nthreads, hipStream_t st, hipEvent_t ev[2]) {
+    const char *src = f.base + f.body;
+    const size_t body = f.size - f.body;
+    if (nthreads < 1) nthreads = 1;
+    hipError_t e = hipSuccess;
+    bool used[2] = {false, false};
+    int h = 0;
+    for (size_t off = 0; off < body && e == hipSuccess; off += half_bytes, h ^= 1) {
+        const size_t len = body - off < half_bytes ? body - off : half_bytes;
+        char *dst = pin + (size_t)h * half_bytes;
+        if (used[h] && (e = hipEventSynchronize(ev[h])) != hipSuccess) break;  // the half's previous DMA has read it
+        int nt = (int)(len / (1u << 20)) + 1;                                    // a thread per MiB at least
+        if (nt > nthreads) nt = nthreads;
+        if (nt <= 1) {
+            memcpy(dst, src + off, len);
+        } else {
+            std::vector<std::thread> th;
+            const size_t per = (len / (size_t)nt + 4095) & ~(size_t)4095;
+            for (int t = 0; t < nt; t++) {
+                const size_t a = per * (size_t)t, b = a + per < len ? a + per : len;
+                if (a < b) th.emplace_back([=]() { memcpy(dst + a, src + off + a, b - a); });
+            }
+            for (auto &w : th) w.join();
+        }
+        if ((e = hipMemcpyAsync(d_text + off, dst, len, hipMemcpyHostToDevice, st)) != hipSuccess) break;
+        e = hipEventRecord(ev[h], st);
+        used[h] = true;
+    }
+    return e;
 }
 
 }  // namespace cd

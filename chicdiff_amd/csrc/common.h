@@ -406,6 +406,15 @@ struct CountputResult {
 };
 size_t countput_workspace_bytes(int64_t n);
 int launch_countput(const CountputArgs &a, char *ws, hipStream_t st, const CountputResult **res_out);
+// chinput_kernels.hip — the body of a .chinput file on the device -> its three int32 columns (chicdiff.R:828, :849).  `text` is 16-byte
+// aligned and holds nbytes >= 1 bytes; ws holds chinput_workspace_bytes(nbytes).  _count (mark pass) and _scan leave the row count in
+// **nrows_out; _parse then writes the rows below `cap` and takes the minimum offset of the malformed lines into **bad_out (all ones: none)
+size_t chinput_workspace_bytes(int64_t nbytes);
+int launch_chinput_count(const unsigned char *text, int64_t nbytes, char *ws, hipStream_t st, const int64_t **nrows_out,
+                         const unsigned long long **bad_out);
+int launch_chinput_scan(int64_t nbytes, char *ws, hipStream_t st);
+void launch_chinput_parse(const unsigned char *text, int64_t nbytes, int ib, int io, int in, int32_t *bait, int32_t *oe, int32_t *N, int64_t cap,
+                          char *ws, hipStream_t st);
 void launch_math_selftest(int op, const double *x, int64_t n, double *out, hipStream_t st);
 void launch_math3_selftest(int op, const double *x, const double *y, int64_t n, const double *logfact, double *out, double *out2, hipStream_t st);
 // the dispersion objective on its own (disp_kernels.hip, objective_probe_kernel): K points a[i * K + k] per row of a prepared fit

@@ -30,6 +30,7 @@ EXPORTS = [
     "chicdiff_hip_candidate_interactions_dev", "chicdiff_hip_candidate_interactions_method_dev", "chicdiff_hip_selftest_landau_dev", "chicdiff_hip_chicago_tables_dev", "chicdiff_hip_chicago_tables_caps",
     "chicdiff_hip_control_draws_dev", "chicdiff_hip_countput_dev", "chicdiff_hip_countput_caps",
     "chicdiff_hip_chinput_read", "chicdiff_hip_chinput_table_dev", "chicdiff_hip_region_avdist_dev",
+    "chicdiff_hip_chinput_parse_dev", "chicdiff_hip_chinput_read_dev", "chicdiff_hip_chinput_caps",
     "chicdiff_hip_count_join_inner_dev", "chicdiff_hip_count_join_multi_dev", "chicdiff_hip_region_assemble_dev",
     "chicdiff_hip_malloc", "chicdiff_hip_free", "chicdiff_hip_outstanding_allocations", "chicdiff_hip_memcpy_h2d", "chicdiff_hip_memcpy_d2h",
     "chicdiff_hip_rccl_unique_id", "chicdiff_hip_rccl_init", "chicdiff_hip_cooks_filter_dev",
@@ -130,6 +131,9 @@ def load_library() -> C.CDLL:
     L.chicdiff_hip_count_table_dev.argtypes = [vp, vp, vp, vp, i64, vp, i32, vp, vp, C.POINTER(i64)]
     L.chicdiff_hip_chinput_read.argtypes = [vp, C.c_char_p, i32, C.POINTER(i64)]
     L.chicdiff_hip_chinput_table_dev.argtypes = [vp, vp, i32, vp, vp, C.POINTER(i64)]
+    L.chicdiff_hip_chinput_parse_dev.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.chicdiff_hip_chinput_read_dev.argtypes = [vp, C.c_char_p, C.POINTER(i64)]
+    L.chicdiff_hip_chinput_caps.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.chicdiff_hip_bh_adjust_dev.argtypes = [vp, vp, i64, vp]
     L.chicdiff_hip_region_avdist_dev.argtypes = [vp, vp, vp, i64, vp, i64, i32, i32, vp, vp, vp]
     L.chicdiff_hip_count_join_inner_dev.argtypes = [vp, vp, vp, i64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp]
@@ -196,6 +200,15 @@ def countput_caps() -> dict:
     m, k, r = C.c_int32(0), C.c_int32(0), C.c_int32(0)
     load_library().chicdiff_hip_countput_caps(C.byref(m), C.byref(k), C.byref(r))
     return dict(max_rep=m.value, key_rows_per_workgroup=k.value, reduce_rows_per_workgroup=r.value)
+
+
+def chinput_caps() -> dict:
+    """The limits of the device path of ``HipContext.read_chinput`` / ``parse_chinput_text`` as the library was built
+    (include/chicdiff_hip.h, CHICDIFF_CHINPUT_*): the body bytes a workgroup takes, the bytes of it one lane marks, and the bytes staged
+    in LDS per tile (the tile and its overhang)."""
+    t, l, w = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    load_library().chicdiff_hip_chinput_caps(C.byref(t), C.byref(l), C.byref(w))
+    return dict(tile_bytes=t.value, lane_bytes=l.value, window_bytes=w.value)
 
 
 def _scalars_dict(s: Scalars) -> dict:
@@ -501,12 +514,44 @@ class HipContext:
             d_bait_in_RU.numel() - 1 if d_bait_in_RU is not None else 0, keys.data_ptr(), vals.data_ptr(), C.byref(nk)))
         return keys[: nk.value], vals[: nk.value]
 
-    def read_chinput(self, path, d_bait_in_RU=None, nthreads=0):
+    def parse_chinput_text(self, d_text, cols):
+        """The body of a .chinput file (the bytes after its header line) as a uint8 device tensor -> (bait, oe, N), int32 device
+        tensors in file order; ``cols`` = the 0-based columns (ib, io, in) of baitID, otherEndID, N.  The rule stands above
+        chicdiff_hip_chinput_parse_dev in include/chicdiff_hip.h.  A malformed line raises, the message naming its byte offset."""
+        torch = self.torch
+        if d_text.dtype != torch.uint8 or d_text.dim() != 1:
+            raise ValueError("parse_chinput_text: d_text is a one-dimensional uint8 tensor")
+        d_text = d_text.contiguous()
+        if d_text.data_ptr() % 16:
+            d_text = d_text.clone()
+        n = d_text.numel()
+        ib, io, in_ = (int(x) for x in cols)
+        nrows, bad = C.c_int64(0), C.c_int64(-1)
+        # first with no room at all: the call reports the row count before it writes anything
+        rc = self.lib.chicdiff_hip_chinput_parse_dev(self.h, d_text.data_ptr(), n, ib, io, in_, None, None, None, 0, C.byref(nrows), C.byref(bad))
+        if rc and nrows.value == 0:
+            self._check(rc)
+        out = [torch.empty(nrows.value, dtype=torch.int32, device=self.device) for _ in range(3)]
+        if nrows.value:
+            rc = self.lib.chicdiff_hip_chinput_parse_dev(self.h, d_text.data_ptr(), n, ib, io, in_, out[0].data_ptr(), out[1].data_ptr(),
+                                                         out[2].data_ptr(), nrows.value, C.byref(nrows), C.byref(bad))
+            if rc:
+                err = ChicdiffHipError(f"[{rc}] " + self.lib.chicdiff_hip_last_error(self.h).decode())
+                err.offset = bad.value if bad.value >= 0 else None   # body-relative offset of the first malformed line
+                raise err
+        return tuple(out)
+
+    def read_chinput(self, path, d_bait_in_RU=None, nthreads=0, device=False):
         """fread(chinput)[, c("baitID", "otherEndID", "N")] restricted to the RU baits -> (keys, vals) of ``count_join``
-        (chicdiff.R:828-831, :849): text parsed by host threads, bait filter + sort on the device."""
+        (chicdiff.R:828-831, :849): text parsed by host threads, bait filter + sort on the device.  ``device=True``: the text goes up
+        as bytes and is parsed there (chicdiff_hip_chinput_read_dev; ``nthreads`` is not used: the upload runs with the context's
+        host_copy_threads) — the same triple."""
         torch = self.torch
         nrows = C.c_int64(0)
-        self._check(self.lib.chicdiff_hip_chinput_read(self.h, os.fsencode(path), int(nthreads), C.byref(nrows)))
+        if device:
+            self._check(self.lib.chicdiff_hip_chinput_read_dev(self.h, os.fsencode(path), C.byref(nrows)))
+        else:
+            self._check(self.lib.chicdiff_hip_chinput_read(self.h, os.fsencode(path), int(nthreads), C.byref(nrows)))
         keys = torch.empty(nrows.value, dtype=torch.int64, device=self.device)
         vals = torch.empty(nrows.value, dtype=torch.int32, device=self.device)
         nk = C.c_int64(0)

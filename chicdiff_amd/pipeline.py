@@ -372,7 +372,7 @@ def countput_dev(xs, conditions, ctx, id_min, midsum, chr_codes, id_columns=None
 
 
 def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, read_chicago=None, assemble=False, device_tables=False,
-                      device_countput=False):
+                      device_countput=False, device_chinput=False):
     """chicdiff.R:1460-1478 with the device path behind it: list(test block, control block, countput).  Every Chicago
     data set and every chinput file is read ONCE for both universes (what ``parallel = TRUE`` -> getFullRegionData2,
     :948-1456, does in the reference; the result does not depend on it).  The long "recast" table (one row per region,
@@ -383,7 +383,9 @@ def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, rea
     ``device_tables=True``: the Chicago background tables are built on the device (``background_tables_dev``) instead of by pandas
     and uploaded — same bits; without countData the uploaded ID columns also feed ``ctx.count_table``.
     ``device_countput=True``: countput is aggregated on the device (``countput_dev``) instead of by the pandas groupby — the same frame,
-    bit for bit and in the same row order."""
+    bit for bit and in the same row order.
+    ``device_chinput=True``: the text of every chinput file is parsed on the device (``ctx.read_chinput(..., device=True)``) instead of
+    by host threads — the same key tables; without countData no chinput file is read and it has no effect."""
     s = asChicdiffSettings(chicdiff_settings)
     if assemble and s["countData"] is None:
         raise ValueError("getFullRegionData(assemble=True) covers the chinput branch only: without countData the counts are "
@@ -431,7 +433,7 @@ def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, rea
         cnames = sample_names(countData)
         for i, p in enumerate(cpaths):
             message("Reading count data for ", cnames[i])
-            keys, vals, _ = ctx.read_chinput(p, d_flags)
+            keys, vals, _ = ctx.read_chinput(p, d_flags, device=device_chinput)
             tables.append((keys, vals))
     else:                                                                          # chicdiff.R:742-747, 774-807
         message("Reconstructing countData")

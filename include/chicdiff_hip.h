@@ -308,7 +308,8 @@ int chicdiff_hip_fragment_background_dev(chicdiff_hip_ctx *ctx, const int32_t *d
  * setkey(x, baitID); x <- x[J(baits)] (chicdiff.R:828-831: only rows whose bait is an RU bait) and
  * setkey(temp, baitID, otherEndID) (:849).  d_bait_in_RU: one byte per ID 0..max_id (non-zero = keep) or NULL =
  * keep every row.  d_keys / d_vals hold nrows entries; the first *nkeys_host are the table, ascending in
- * (baitID << 32 | otherEndID).  Reading the chinput text stays host code. */
+ * (baitID << 32 | otherEndID).  The chinput text is read by host threads (chicdiff_hip_chinput_read) or, opt-in, parsed on the
+ * device (chicdiff_hip_chinput_read_dev); only the header line is host code in both. */
 int chicdiff_hip_count_table_dev(chicdiff_hip_ctx *ctx, const int32_t *d_bait, const int32_t *d_oe, const int32_t *d_N,
                                  int64_t nrows, const uint8_t *d_bait_in_RU, int32_t max_id, int64_t *d_keys,
                                  int32_t *d_vals, int64_t *nkeys_host);
@@ -321,6 +322,50 @@ int chicdiff_hip_count_table_dev(chicdiff_hip_ctx *ctx, const int32_t *d_bait, c
 int chicdiff_hip_chinput_read(chicdiff_hip_ctx *ctx, const char *path, int32_t nthreads, int64_t *nrows_host);
 int chicdiff_hip_chinput_table_dev(chicdiff_hip_ctx *ctx, const uint8_t *d_bait_in_RU, int32_t max_id, int64_t *d_keys,
                                    int32_t *d_vals, int64_t *nkeys_host);
+
+/* limits of the device path of f2's text part (below) */
+#define CHICDIFF_CHINPUT_TILE_BYTES 16384    /* consecutive body bytes a workgroup takes in the mark pass and in the parse pass */
+#define CHICDIFF_CHINPUT_LANE_BYTES 64       /* consecutive bytes of the tile one lane marks (four 16-byte loads) */
+#define CHICDIFF_CHINPUT_WINDOW_BYTES 16640  /* bytes staged in LDS per tile: the tile and an overhang; a line that runs on is read from global memory */
+/* f2 (text part) on the device, opt-in: the same rows as chicdiff_hip_chinput_read, parsed by two kernels from the text in device
+ * memory.  The rule is the host parser's, stated in full:
+ *
+ *   header     the leading '#' comment lines and the header line are read on the HOST, exactly as chicdiff_hip_chinput_read reads
+ *              them (one function serves both paths): the header's fields are split at tab / blank / comma, a name may be quoted, the
+ *              columns may come in any order; ib, io, in = the 0-based positions of baitID, otherEndID, N.  A header that does not
+ *              name all three is CHICDIFF_E_INVALID with the host path's message.
+ *   body       the bytes after the header line's '\n' (none when the header line is the file's last).
+ *   lines      a line runs from a line start — the body's first byte, or the byte after a '\n' — to the next '\n', or to the end of
+ *              the body.  ONE trailing '\r' is dropped.  A line that is empty after that is skipped: not a row, not an error.
+ *   fields     split at every single tab, blank or comma; two separators in a row make an empty field.
+ *   values     only fields ib, io, in are parsed: an optional single '+' or '-', then at least one digit, then digits only; the
+ *              magnitude is at most 2147483647 (so -2147483648 is malformed).  Scanning stops after the largest of the three
+ *              positions: whatever follows on the line is never looked at, however long.  A line on which fewer than three of them were
+ *              found is malformed.
+ *   output     rows in file order.  Any malformed line fails the call; the offset reported is that of the SMALLEST malformed line
+ *              start.
+ * Row r's place is the number of non-blank line starts before it, from one scan of per-tile counts and one inside the tile: no value
+ * passes through an atomic, and launch shape and arrival order cannot show in the result (the one atomic is a 64-bit minimum over
+ * the offsets of malformed lines).
+ *
+ * _parse_dev: the device stage alone.  d_text: the body, nbytes >= 0 bytes of device memory, 16-byte aligned; ib, io, in >= 0 and
+ * distinct; d_bait, d_oe, d_N: room for `cap` rows.  *nrows_host = the rows of the body.  nrows > cap: CHICDIFF_E_INVALID before
+ * anything is written (the count is known before the parse pass starts).  A malformed line: CHICDIFF_E_INVALID, *bad_offset_host =
+ * its body-relative offset (-1 otherwise), message `malformed chinput row at byte offset K (...)`; the rows' contents are then
+ * unspecified.  One host stop for the count, one for the verdict.
+ * _read_dev: header on the host, the body through a bounded pinned staging area to the device (host_copy_threads threads copy
+ * chunks into its two halves; the DMA of one half runs while the other is filled), then the stage above.  The text and the three
+ * columns stay in grow-only buffers of the context (released by chicdiff_hip_destroy), apart from every workspace:
+ * chicdiff_hip_chinput_table_dev then builds the key table from them with no host copy.  The context remembers which of _read and
+ * _read_dev came last, and _table_dev serves that one.  Messages are the host path's (`cannot open ...`, `empty file`, the header
+ * message, `malformed chinput row at byte offset K (...)` with K counted from the start of the FILE); an allocation that fails is
+ * CHICDIFF_E_NOMEM, the message naming the file size.
+ * chicdiff_hip_chinput_caps: the three constants above, as the library was built (any pointer may be NULL); host only, no context. */
+int chicdiff_hip_chinput_parse_dev(chicdiff_hip_ctx *ctx, const uint8_t *d_text, int64_t nbytes, int32_t ib, int32_t io, int32_t in,
+                                   int32_t *d_bait, int32_t *d_oe, int32_t *d_N, int64_t cap, int64_t *nrows_host,
+                                   int64_t *bad_offset_host);
+int chicdiff_hip_chinput_read_dev(chicdiff_hip_ctx *ctx, const char *path, int64_t *nrows_host);
+int chicdiff_hip_chinput_caps(int32_t *tile_bytes, int32_t *lane_bytes, int32_t *window_bytes);
 
 /* f1/f3 — p.adjust(p, method = "BH") (DESeq2 results() on the independent-filtering survivors; chicdiff.R:2049
  * on the weighted p-values).  NaN = NA: not counted, stays NaN.  n < 2^32. */
