@@ -212,7 +212,13 @@ __device__ __forceinline__ double harmonic_row(const RowConsts &c, unsigned int 
     w0 &= a == 4u ? 0xffffffffu : ((1u << (8u * a)) - 1u);
     w1 &= b == 4u ? 0xffffffffu : ((1u << (8u * b)) - 1u);
     w2 &= (1u << (8u * d)) - 1u;
-    double P = 1.0, Hr = 0.0, zz = c.r;
+    // The sum is carried as a numerator over the prefix product, N_{i+1} = N_i (r + i) + c_i P_i with H = N_10 / P_10 (the P / Q
+    // recurrence of lgamma_digamma(), devmath.h): one reciprocal per tick instead of one per step (round 22: ten v_rcp_f64 with two
+    // Newton steps each were 9 % of a bulk tick's issue cycles).  P's own operations and their order are those of the table, so the
+    // table keeps its bits; a lane whose profile is masked to zero (nr = 0) has N = 0 and H = 0 as long as P is finite — 0 x inf would be
+    // NaN where the former sum of c_i / (r + i) was an exact 0.  P_10 < r^10 (1 + 9 / r)^10 is finite for r below ~ 1e30, and every caller
+    // keeps a = log(alpha) inside [-30, 10] (the searches clamp their steps to it, the grid starts at log(1e-8)): r <= e^30 ~ 1.1e13.
+    double P = 1.0, N = 0.0, zz = c.r;
 #ifdef HR_ROLLED
 #pragma unroll 1
 #else
@@ -221,17 +227,15 @@ __device__ __forceinline__ double harmonic_row(const RowConsts &c, unsigned int 
     for (int i = 0; i < 10; i++) {
         const unsigned int w = i < 4 ? w0 : (i < 8 ? w1 : w2);
         const double ci = (double)((w >> (8 * (i & 3))) & 0xffu);
-        Hr = fma(ci, rcp(zz), Hr);
-        if (TABLE) {
-            P *= zz;
-            s_tab[i * 64 + lane] = P;
-        }
+        N = fma(N, zz, ci * P);
+        P *= zz;
+        if (TABLE) s_tab[i * 64 + lane] = P;
         zz += 1.0;
 #ifdef HR_SCHED_BARRIER
         __builtin_amdgcn_sched_barrier(0);
 #endif
     }
-    return Hr;
+    return N * rcp(P);
 }
 __device__ __forceinline__ void finish_point(const Acc &acc, const RowConsts &c, double Hrow, bool p2, bool use_prior,
                                              double prior_mean, double prior_isig, double &lp, double &dlp,

@@ -40,7 +40,7 @@ extern "C" __global__ void part_sample(const double *in, const int *iy, double *
     LT;
     RowConsts c;
     c.a = in[0]; c.alpha = in[1]; c.r = in[2]; c.lgS0 = in[3]; c.dgS0 = in[4]; c.nr = iy[0];
-    const SampleVals v = sample_values(c, in[8 + threadIdx.x], iy[8 + threadIdx.x], in[72 + threadIdx.x], in[136 + threadIdx.x], s_lt);
+    const SampleVals v = sample_values(c, in[8 + threadIdx.x], iy[8 + threadIdx.x], in[72 + threadIdx.x], s_lt);
     out[threadIdx.x] = v.wj + v.pm + v.tll + v.tsd + (double)v.pe;
 }
 // the same with the Stirling difference compiled out (a sample with y <= nr)
@@ -48,7 +48,7 @@ extern "C" __global__ void part_sample_no_stirling(const double *in, const int *
     LT;
     RowConsts c;
     c.a = in[0]; c.alpha = in[1]; c.r = in[2]; c.lgS0 = in[3]; c.dgS0 = in[4]; c.nr = 0x7fffffff;
-    const SampleVals v = sample_values(c, in[8 + threadIdx.x], iy[8 + threadIdx.x] & 0xff, in[72 + threadIdx.x], in[136 + threadIdx.x], s_lt);
+    const SampleVals v = sample_values(c, in[8 + threadIdx.x], iy[8 + threadIdx.x] & 0xff, in[72 + threadIdx.x], s_lt);
     out[threadIdx.x] = v.wj + v.pm + v.tll + v.tsd + (double)v.pe;
 }
 extern "C" __global__ void part_accumulate(const double *in, double *out, int g) {
@@ -67,16 +67,17 @@ extern "C" __global__ void part_finish(const double *in, double *out, int p2, in
     RowConsts c;
     c.a = in[0]; c.alpha = in[1]; c.r = in[2]; c.lgS0 = in[3]; c.dgS0 = in[4]; c.nr = 0;
     double lp, dlp;
-    finish_point(acc, c, p2 != 0, prior != 0, in[5], in[6], lp, dlp, s_lt);
+    finish_point(acc, c, in[7], p2 != 0, prior != 0, in[5], in[6], lp, dlp, s_lt);
     out[threadIdx.x] = lp + dlp;
 }
-// one step of the prefix walk / table: P *= z; H += rcp(z); z += 1
+// one step of harmonic_row's table: N = N z + c P; P *= z; z += 1 (the numerator of the harmonic sum beside the prefix product)
 extern "C" __global__ void part_prefix_step(const double *in, double *out) {
-    double P = in[threadIdx.x], H = in[64 + threadIdx.x], zz = in[128 + threadIdx.x];
+    double P = in[threadIdx.x], N = in[64 + threadIdx.x], zz = in[128 + threadIdx.x];
+    const double ci = in[192 + threadIdx.x];
+    N = fma(N, zz, ci * P);
     P *= zz;
-    H += rcp(zz);
     zz += 1.0;
-    out[threadIdx.x] = P + H + zz;
+    out[threadIdx.x] = P + N + zz;
 }
 
 }  // namespace cd
