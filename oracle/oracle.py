@@ -160,8 +160,9 @@ def arbitrate_disp(counts, nf, group, rows, fit, stage="gene") -> np.ndarray:
     return out
 
 
-def irls_trace(counts, nf, group, row, alpha, steps=12):
-    """One row's IRLS iterates without the stopping rule: (lfc on the log2 scale per step, conv_test per step)."""
+def irls_trace(counts, nf, group, row, alpha, steps=12, with_intercept=False):
+    """One row's IRLS iterates without the stopping rule: (lfc on the log2 scale per step, conv_test per step); with_intercept:
+    (intercept, lfc, conv_test)."""
     k = _cm(counts, np.int32)
     f = _cm(nf, np.float64)
     n, S = k.shape
@@ -170,6 +171,8 @@ def irls_trace(counts, nf, group, row, alpha, steps=12):
     rc = lib().oracle_irls_trace(_pi(k), _pd(f), n, S, _pi(g), int(row), float(alpha), steps, _pd(b0), _pd(b1), _pd(cv))
     if rc:
         raise RuntimeError(f"oracle_irls_trace rc={rc}")
+    if with_intercept:
+        return b0 / np.log(2.0), b1 / np.log(2.0), cv
     return b1 / np.log(2.0), cv
 
 
