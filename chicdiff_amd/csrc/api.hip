@@ -78,7 +78,7 @@ struct chicdiff_hip_ctx {
     int device = 0;
     bool no_persistent_trend = false;  // set after a grid-barrier timeout (see fit_dev_impl)
     // tuning / test options (chicdiff_hip_set_option, the only writer): `tune` is what make_opts starts from, its tuning tail
-    // (spread .. trend_blocks) is the storage of those options
+    // (spread .. mad_value_cap) is the storage of those options
     Opts tune{};
     HostOpts host;
     char *tg_buf = nullptr;    // ... the gathered rows (grow-only)
@@ -232,6 +232,9 @@ static const OptionDef kOptions[] = {
     {"trend_one_launch_per_pass", nullptr, &HostOpts::trend_one_launch_per_pass, 0, 1, 1, 0},
     {"sharded_trend_gather", nullptr, &HostOpts::sharded_trend_gather, 0, 1, 1, 0},
     {"trend_persistent_blocks", &Opts::trend_blocks, nullptr, 0, 256, 1, 0},
+    {"trend_speculate", &Opts::trend_speculate, nullptr, 0, 1, 1, 0},
+    {"mad_select_route", &Opts::mad_route, nullptr, 0, 1, 1, 0},
+    {"mad_value_cap", &Opts::mad_value_cap, nullptr, 0, kVbCap, 1, 0},
     {"trend_mad_in_kernel", nullptr, &HostOpts::trend_mad_in_kernel, 0, 1, 1, 0},
     {"fuse_offsets", nullptr, &HostOpts::fuse_offsets, 0, 2, 1, 0},
     {"prep_blocks", nullptr, &HostOpts::prep_blocks, 0, kRedBlocks, 1, 0},

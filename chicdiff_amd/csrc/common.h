@@ -102,6 +102,9 @@ struct Opts {
     int32_t fillers = -1;   // gene-wise line search: a third wave per SIMD at priority 0 that takes only rows which cannot be long (0 off, 1 on, -1 = by launch_disp's rule); option "line_search_fillers"
     int32_t filler_stop = -1;  // ... fillers stop claiming once the front waves have claimed this share (percent) of their own chunks (100 = never, -1 = kFillerStopDefault); option "line_search_filler_stop"
     int32_t trend_blocks = 0;  // persistent trend kernel: at most this many workgroups (0 = one per CU); option "trend_persistent_blocks"
+    int32_t trend_speculate = 1;  // persistent trend kernel: passes announced by fit_state.h trend_step_spec also sum the next glm() call's start pass; option "trend_speculate"
+    int32_t mad_route = 1;        // ... its MAD step: 1 = value-binned select (three grid barriers), 0 = two radix selects (six); option "mad_select_route"
+    int32_t mad_value_cap = 0;    // ... keys a candidate list of the value-binned select may hold (0 = kVbCap); test hook, option "mad_value_cap"
 };
 
 // ---- schedule of a row-queue kernel (disp_kernels.hip order_*): rows in class order; the class counts per tile of rows come from

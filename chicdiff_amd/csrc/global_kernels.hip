@@ -77,6 +77,28 @@ __device__ __forceinline__ void trend_row_dev(const FitScalars *sc, double x, do
     v[5] += wt * x * disp;
     v[6] += 1;
 }
+// A row of a speculative pass (fit_state.h trend_step_spec): v as above, and u, what the start pass of the next glm() call adds
+// for this row if this pass converges.  That pass runs with coefs := b, so its filter ratio disp * rcp(fma(coefs[1], x, coefs[0]))
+// is q, bit for bit, and its seven terms are the ones formed here — each is computed once and added to v, to u, or to both.  A row
+// whose mu is not positive and finite never enters u: rcp(mu) is then negative, zero or NaN and q fails the filter, as in the real
+// start pass, so u[7] stays zero.  Rows the current filter rejects (which return early above) are looked at here.
+__device__ __forceinline__ void trend_row_spec_dev(const FitScalars *sc, double x, double disp, double *v, double *u, const LogEntry *lt) {
+    const double r = disp * rcp(fma(sc->coefs[1], x, sc->coefs[0]));
+    const bool in_v = r > 1e-4 && r < 15;
+    const double mu = fma(sc->b[1], x, sc->b[0]);
+    if (!(mu > 0) || !isfinite(mu)) {
+        if (in_v) v[7] += 1;
+        return;
+    }
+    const double rmu = rcp(mu), q = disp * rmu;
+    const bool in_u = q > 1e-4 && q < 15;
+    if (!in_v && !in_u) return;
+    const double t0 = -2.0 * (tlog(q, lt) - fma(-mu, rmu, q));
+    const double wt = rmu * rmu;
+    const double t2 = wt * x, t3 = wt * x * x, t4 = wt * disp, t5 = wt * x * disp;
+    if (in_v) { v[0] += t0; v[1] += wt; v[2] += t2; v[3] += t3; v[4] += t4; v[5] += t5; v[6] += 1; }
+    if (in_u) { u[0] += t0; u[1] += wt; u[2] += t2; u[3] += t3; u[4] += t4; u[5] += t5; u[6] += 1; }
+}
 
 __global__ __launch_bounds__(256) void trend_pass_kernel(FitDims d, FitWork w, double minDisp) {
     __shared__ LogEntry s_lt[64];
@@ -118,9 +140,13 @@ __global__ void trend_step_kernel(FitWork w) { trend_step(w.sc, w.partials + (si
 // One 1024-thread workgroup per CU; each owns a contiguous block of rows and keeps their
 // (baseMean, dispGeneEst) pairs in LDS (2 M rows = 125 KB per CU of the 160 KB), so the ~20 IRLS passes
 // of glm.fit read HBM once instead of 20 times and need no kernel boundary: per pass every workgroup
-// publishes 8 partial sums, a grid barrier (monotonic counter, agent-scope release/acquire, cdna guide
+// publishes 8 partial sums (16 in a speculative pass, see trend_row_spec_dev), a grid barrier (monotonic counter, agent-scope release/acquire, cdna guide
 // G16) follows, and every workgroup adds the partials in the same fixed order and advances its own copy
 // of the state machine (fit_state.h) — identical in all workgroups, no broadcast needed.
+// The start pass of every glm() call after the first is not run where the pass before it, the converging one, was announced as
+// speculative by the state machine and has summed the start pass's values on the side: 2 passes of 13 at 200 k x 8, 3 of 18 at
+// 30 k x 4 (option "trend_speculate" = 0: every pass as before; same bits either way).
+constexpr int kTpSums = 2 * kTrendSums;  // a workgroup's slot per pass: v[8], then u[8] of a speculative pass
 constexpr int kTpBlocks = 256, kTpThreads = 1024, kTpCap = 8000, kTpMinRows = 2048;  // rows cached per workgroup (2 x 64 000 B of LDS)
 
 // Two-level grid barrier: workgroups arrive at one of 8 group counters (blockIdx % 8, i.e. one per XCD under
@@ -195,12 +221,22 @@ __device__ __forceinline__ double wave_sum_to_lane63(double x) {
 constexpr int kMadSortMax = 512;  // candidates per slot that are sorted rather than narrowed down by another round (<= kSelCap)
 constexpr int kMadHistWords = 2 * 6 * 2 * kSelBins;
 constexpr int kMadCntWords = 8;                                  // 2 x 2 counters (+ pad)
-constexpr int kMadScratchWords = kMadHistWords + kMadCntWords;   // what must be zero; the candidate lists follow (8-byte aligned)
+constexpr int kMadScratchWords = kMadHistWords + kMadCntWords;   // the radix select's words that must be zero
+// ... then the value-binned route's (below): its histogram and vcnt[0] median candidates, [1] candidates of the MAD, [2] rows below
+// the MAD's bracket, [3] population of |x - med|; all of it is zeroed by the kernel.  The candidate lists follow (8-byte aligned):
+// the radix select's four of kSelCap keys, then the value route's two of kVbCap.
+constexpr int kVbCntWords = 8;
+constexpr int kMadZeroWords = kMadScratchWords + kVbBins + kVbCntWords;
+constexpr int kVbPer = kVbBins / 1024, kVbList2 = 1024;  // bins per thread of the kernel; keys a narrowed list may hold
+static_assert(kVbBins == kVbPer * 1024 && kMadZeroWords % 2 == 0 && kVbCap * 8 <= 64000, "value-binned select: layout");
 struct MadArgs {
     int enabled;       // 0: the kernel stops after the trend (the host launches the separate MAD step)
     int S, p;
     double prior_in;   // NaN = estimate; the closed-form prior variance is finished here unless by_simulation
     int by_simulation; // residual d.f. <= 3: the host follows up with the residual histogram and prior_mc
+    int speculate;     // the trend's passes may speculate (option "trend_speculate")
+    int value_route;   // median and MAD by the value-binned select, three grid barriers instead of six (option "mad_select_route")
+    int value_cap;     // ... keys a candidate list may hold (option "mad_value_cap": a test can force the radix select)
 };
 
 #ifdef CHICDIFF_MAD_STAMPS
@@ -232,6 +268,30 @@ __device__ __forceinline__ void hist_add(unsigned int *h, bool valid, unsigned i
     if ((todo >> lane) & 1ull) atomicAdd(&h[digit], 1u);  // (digits of the later rounds differ from lane to lane)
 }
 
+// The order statistics wanted, read off a list of m <= 1024 keys in LDS by COUNTING instead of sorting it: P = 1024 / (m rounded
+// up to a power of two) threads share one candidate, each counts the keys that come before it (smaller, or equal with a lower
+// index) in its slice of the list, the P counts are added by shuffles, and the candidate whose count is a wanted rank is an answer.
+__device__ __forceinline__ void lds_count_select(const uint64_t *buf, int m, int wantA, int wantB, uint64_t *sh_res /*[2]*/) {
+    const int tid = threadIdx.x;
+    int mp = 64;
+    while (mp < m) mp <<= 1;
+    const int P = kTpThreads / mp;  // 1 .. 16 threads per candidate, neighbouring lanes
+    const int e = tid / P, part = tid - e * P;
+    int before = 0;
+    const uint64_t mine = e < m ? buf[e] : 0ull;
+    if (e < m)
+        for (int j = part; j < m; j += P) {
+            const uint64_t o = buf[j];
+            before += (o < mine || (o == mine && j < e)) ? 1 : 0;
+        }
+    for (int off = 1; off < P; off <<= 1) before += __shfl_xor(before, off);
+    if (e < m && part == 0) {  // (ranks are distinct: exactly one candidate has each)
+        if (before == wantA) sh_res[0] = mine;
+        if (before == wantB) sh_res[1] = mine;
+    }
+    __syncthreads();
+}
+
 // One exact select over the keys key_fn(k) of this workgroup's rows; returns the two middle order statistics as keys.
 // `sel` picks the scratch; s_a / s_b: two LDS histograms of kSelBins words; sortbuf: kSelCap 64-bit words (may alias them).
 // Every workgroup executes the same barriers and reaches the same result.  Returns false if a grid barrier timed out.
@@ -245,7 +305,7 @@ __device__ bool mad_select(KeyFn key_fn, int64_t nrows_block, int sel, unsigned 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     unsigned int *ghist = gscratch + (size_t)sel * 6 * 2 * kSelBins;
     unsigned int *gcnt = gscratch + kMadHistWords + sel * 2;
-    uint64_t *gcand = reinterpret_cast<uint64_t *>(gscratch + kMadScratchWords) + (size_t)sel * 2 * kSelCap;
+    uint64_t *gcand = reinterpret_cast<uint64_t *>(gscratch + kMadZeroWords) + (size_t)sel * 2 * kSelCap;
     uint64_t p0 = 0, p1 = 0;
     double rank0 = 0, rank1 = 0;
     int fixed_hi = 64;  // bits [fixed_hi, 64) of the two prefixes are decided
@@ -352,9 +412,7 @@ __device__ bool mad_select(KeyFn key_fn, int64_t nrows_block, int sel, unsigned 
     MSTAMP(5);
     // The order statistics wanted, read off each list by COUNTING instead of sorting it (round 4: a bitonic sort of ~100 keys cost
     // 4 us — 28 rounds of compare-exchange with a workgroup barrier each — and there are up to four lists per MAD): the list goes
-    // to LDS, P = 1024 / (its length rounded up to a power of two) threads share one candidate, each counts the keys that come
-    // before it (smaller, or equal with a lower index) in its slice of the list, the P counts are added by shuffles, and the
-    // candidate whose count is the wanted rank is the answer.  Lists longer than 512 keep the sort.
+    // to LDS and lds_count_select reads the ranks off it.  Lists longer than 512 keep the sort.
     for (int slot = 0; slot < 2; slot++) {
         const int hslot = (slot == 1 && !same) ? 1 : 0;
         const int m = (int)gcnt[hslot];
@@ -364,25 +422,9 @@ __device__ bool mad_select(KeyFn key_fn, int64_t nrows_block, int sel, unsigned 
         const int wantA = rkA < m ? rkA : m - 1, wantB = rkB < 0 ? -1 : (rkB < m ? rkB : m - 1);
         __syncthreads();
         if (m <= kMadSortMax) {
-            int mp = 64;
-            while (mp < m) mp <<= 1;
-            const int P = kTpThreads / mp;  // 2 .. 16 threads per candidate, neighbouring lanes
             for (int e = tid; e < m; e += kTpThreads) sortbuf[e] = gcand[(size_t)hslot * kSelCap + e];
             __syncthreads();
-            const int e = tid / P, part = tid - e * P;
-            int before = 0;
-            const uint64_t mine = e < m ? sortbuf[e] : 0ull;
-            if (e < m)
-                for (int j = part; j < m; j += P) {
-                    const uint64_t o = sortbuf[j];
-                    before += (o < mine || (o == mine && j < e)) ? 1 : 0;
-                }
-            for (int off = 1; off < P; off <<= 1) before += __shfl_xor(before, off);
-            if (e < m && part == 0) {  // (ranks are distinct: exactly one candidate has each)
-                if (before == wantA) sh_res[0] = mine;
-                if (before == wantB) sh_res[1] = mine;
-            }
-            __syncthreads();
+            lds_count_select(sortbuf, m, wantA, wantB, sh_res);
             result[slot] = sh_res[0];
             if (wantB >= 0) result[1] = sh_res[1];
             continue;
@@ -411,12 +453,188 @@ __device__ bool mad_select(KeyFn key_fn, int64_t nrows_block, int sel, unsigned 
     return true;
 }
 
+// ---- value-binned route of the MAD step (fit_state.h "value-binned select"): three grid barriers instead of six -------------
+// Residual pass: every valid residual also goes into an LDS histogram over its VALUE, merged into a global one; barrier 1.  Every
+// workgroup scans that histogram (vb_pick), the rows of the median's bin(s) go to one candidate list; barrier 2; every workgroup
+// reads the two middle ranks off the list on its own.  With the median known the same histogram brackets the two middle values
+// of |x - med| (vb_bracket); one more pass counts the rows below the bracket and lists those inside it, both by comparing
+// |x - med| itself; barrier 3; every workgroup checks the counts (vb_check) and selects from the list.  A list that does not fit
+// or a failed check sends that select to mad_select above: the decision comes from the histogram or from counters read behind a
+// barrier, so every workgroup takes the same turn.
+
+// LDS of the value route besides the freed row cache: second-level histogram, narrowed list, and a few words
+struct VbShared {
+    unsigned int sub[kVbSub];
+    uint64_t list2[kVbList2];
+    uint64_t res[2];
+    unsigned int wave[16], n, base, pop, below;
+    unsigned int total, pbin[2], pbelow[2], pcnt[2];  // lds_hist_pick: entries in all; per rank its bin, the entries before that bin, in it
+    int ia, ib;                                       // vb_bracket_par
+    double lo, hi;
+};
+
+// Over the histogram h[0 .. PER * 1024), thread t owning PER consecutive words: the total, and for two ranks the bin that holds
+// each (fit_state.h cum_locate), the entries before that bin and in it — found by the thread that owns the bin, no search.
+// middle: the ranks are the two middle ranks of the total (R median()) instead of rA, rB.  cumulate: h becomes its inclusive
+// prefix sums.  A rank beyond the total leaves its pick at the last bin.
+template <int PER>
+__device__ __forceinline__ void lds_hist_pick(unsigned int *h, VbShared &sh, bool middle, unsigned int rA, unsigned int rB, bool cumulate) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned int mine[PER], acc = 0;
+#pragma unroll
+    for (int q = 0; q < PER; q++) {
+        mine[q] = h[tid * PER + q];
+        acc += mine[q];
+    }
+    unsigned int incl = acc;
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned int o = __shfl_up(incl, off);
+        if (lane >= off) incl += o;
+    }
+    if (lane == 63) sh.wave[wave] = incl;
+    if (tid == 0) {
+        sh.pbin[0] = sh.pbin[1] = PER * kTpThreads - 1;
+        sh.pbelow[0] = sh.pbelow[1] = sh.pcnt[0] = sh.pcnt[1] = 0;
+    }
+    __syncthreads();
+    unsigned int before = incl - acc, total = 0;
+    for (int q = 0; q < kTpThreads / 64; q++) {
+        if (q < wave) before += sh.wave[q];
+        total += sh.wave[q];
+    }
+    if (tid == 0) sh.total = total;
+    if (middle) {
+        rA = total ? (total - 1) / 2 : 0;
+        rB = total / 2;
+    }
+#pragma unroll
+    for (int slot = 0; slot < 2; slot++) {
+        const unsigned int r = slot ? rB : rA;
+        if (before <= r && r - before < acc) {
+            unsigned int c = before;
+            int q = 0;
+            for (; q < PER - 1; q++) {
+                if (c + mine[q] > r) break;
+                c += mine[q];
+            }
+            sh.pbin[slot] = tid * PER + q;
+            sh.pbelow[slot] = c;
+            sh.pcnt[slot] = mine[q];
+        }
+    }
+    if (cumulate) {
+        unsigned int run = before;
+#pragma unroll
+        for (int q = 0; q < PER; q++) {
+            run += mine[q];
+            h[tid * PER + q] = run;
+        }
+    }
+    __syncthreads();
+}
+
+// fit_state.h vb_bracket by all threads at once (its two conditions are monotone in rho, so any search finds the same grid
+// points): the 8 * kVbBins = 1024 x 120 steps of a quarter bin are cut into 1024 intervals, every thread tests the two ends of
+// its own, and 120 threads then test the points inside the interval where the condition turns.  cum: inclusive prefix sums.
+__device__ __forceinline__ void vb_bracket_par(const unsigned int *cum, double med, unsigned int rankA, unsigned int rankB, VbShared &sh) {
+    constexpr int kStride = 8 * kVbBins / kTpThreads;  // 120
+    const double step = 1.0 / (4.0 * kVbScale);
+    const int tid = threadIdx.x;
+    auto pa = [&](int p) { return p == 0 || (p <= 8 * kVbBins && vb_upper(cum, med, p * step) <= rankA); };  // lo: the largest p with pa
+    auto pb = [&](int p) { return p <= 8 * kVbBins && vb_lower(cum, med, p * step) > rankB; };                 // hi: the smallest p with pb
+    if (tid == 0) { sh.ia = 0; sh.ib = -1; }
+    __syncthreads();
+    const int p0 = tid * kStride, p1 = p0 + kStride;
+    if (pa(p0) && !pa(p1)) sh.ia = p0;      // lo in [p0, p1)
+    if (tid == kTpThreads - 1 && pa(p1)) sh.ia = p1;  // (a median far outside the bins: the last point qualifies)
+    if (!pb(p0) && pb(p1)) sh.ib = p0;      // hi in (p0, p1]; none: no p has pb, hi = +inf
+    __syncthreads();
+    const int ia = sh.ia, ib = sh.ib;
+    __syncthreads();
+    if (tid < kStride) {
+        const int q = ia + tid;
+        if (pa(q) && (tid == kStride - 1 || !pa(q + 1))) sh.ia = q;
+    } else if (tid >= 128 && tid < 128 + kStride && ib >= 0) {
+        const int q = ib + 1 + (tid - 128);
+        if (pb(q) && !pb(q - 1)) sh.ib = q;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        sh.lo = sh.ia * step;
+        sh.hi = sh.ib < 0 ? INFINITY : sh.ib * step;
+    }
+    __syncthreads();
+}
+
+// Ranks kA <= kB <= kA + 1 of the global list glist[0, m), m <= kVbCap, whose values lie (mostly) in [vlo, vlo + kVbSub / scale).
+// The list goes to LDS; up to kMadSortMax keys are counted at once, a longer list is first narrowed to the second-level bin(s) of
+// the two ranks.  false: more than kVbList2 keys share those bins (ties) — the same verdict in every workgroup.
+__device__ bool vb_list_select(const uint64_t *glist, int m, double vlo, double scale, int kA, int kB, uint64_t *lst, VbShared &sh, uint64_t (&res)[2]) {
+    const int tid = threadIdx.x;
+    for (int e = tid; e < m; e += kTpThreads) lst[e] = glist[e];
+    for (int k = tid; k < kVbSub; k += kTpThreads) sh.sub[k] = 0;
+    if (tid == 0) sh.n = 0;
+    __syncthreads();
+    if (m <= kMadSortMax) {
+        lds_count_select(lst, m, kA, kB, sh.res);
+    } else {
+        for (int e = tid; e < m; e += kTpThreads) atomicAdd(&sh.sub[vb_sub(value_of(lst[e]), vlo, scale)], 1u);
+        __syncthreads();
+        lds_hist_pick<kVbSub / kTpThreads>(sh.sub, sh, false, (unsigned int)kA, (unsigned int)kB, false);
+        const int sA = (int)sh.pbin[0], sB = (int)sh.pbin[1], below = (int)sh.pbelow[0];
+        const int m2 = (int)(sA == sB ? sh.pcnt[0] : sh.pcnt[0] + sh.pcnt[1]);  // (no key lies between two neighbouring ranks)
+        if (m2 > kVbList2) return false;
+        for (int e = tid; e < m; e += kTpThreads) {
+            const int sb = vb_sub(value_of(lst[e]), vlo, scale);
+            if (sb == sA || sb == sB) sh.list2[atomicAdd(&sh.n, 1u)] = lst[e];  // (no key between two neighbouring ranks: m2 in all)
+        }
+        __syncthreads();
+        lds_count_select(sh.list2, m2, kA - below, kB - below, sh.res);
+    }
+    res[0] = sh.res[0];
+    res[1] = sh.res[1];
+    __syncthreads();
+    return true;
+}
+
+// the global value histogram -> LDS
+__device__ __forceinline__ void vb_load(const unsigned int *vhist, unsigned int *s_h) {
+    for (int k = threadIdx.x; k < kVbBins; k += kTpThreads) s_h[k] = vhist[k];
+    __syncthreads();
+}
+
+// Workgroup-aggregated append: the keys for which pred(k, key) holds go to an LDS stage first, one global atomic reserves their
+// place in the list.  A workgroup with more than `cap` of them adds its count all the same (the list has overflowed then).
+template <class Pred>
+__device__ __forceinline__ void vb_append(Pred pred, int64_t nrows_block, uint64_t *stage, unsigned int cap, unsigned int *gcount, uint64_t *glist,
+                                          VbShared &sh) {
+    const int tid = threadIdx.x;
+    if (tid == 0) sh.n = 0;
+    __syncthreads();
+    for (int64_t k = tid; k < nrows_block; k += kTpThreads) {
+        uint64_t key;
+        if (!pred(k, key)) continue;
+        const unsigned int pos = atomicAdd(&sh.n, 1u);
+        if (pos < cap) stage[pos] = key;
+    }
+    __syncthreads();
+    const unsigned int n = sh.n;
+    if (tid == 0 && n) sh.base = atomicAdd(gcount, n);
+    __syncthreads();
+    if (n && n <= cap) {
+        const unsigned int base = sh.base;
+        for (unsigned int e = tid; e < n; e += kTpThreads)
+            if (base + e < cap) glist[base + e] = stage[e];
+    }
+}
+
 __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d, FitWork w, double minDisp, MadArgs madargs) {
     const bool mad = madargs.enabled != 0;
     __shared__ double s_bm[kTpCap], s_y[kTpCap];  // 1 / baseMean and dispGeneEst (NaN = not used for the fit)
-    __shared__ double red[kTrendSums][16];
+    __shared__ double red[kTpSums][16];
     __shared__ FitScalars st;  // only the trend fields are used
     __shared__ LogEntry s_lt[64];
+    __shared__ VbShared vsh;
     if (threadIdx.x < 64) s_lt[threadIdx.x] = kLogTable[threadIdx.x];  // (the barrier below covers it)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t per = (d.n + gridDim.x - 1) / gridDim.x;
@@ -432,12 +650,13 @@ __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d,
     if (tid == 0) trend_init(&st);
     __syncthreads();
     unsigned int *ctr = reinterpret_cast<unsigned int *>(w.barrier), *grp = ctr + 16;  // top counter, then 8 group counters 64 B apart
-    double *slots = w.partials;  // [2][gridDim.x][kTrendSums], double-buffered by pass parity
+    double *slots = w.partials;  // [2][gridDim.x][kTpSums], double-buffered by pass parity
+    const bool speculate = madargs.speculate != 0;
     const double thr = 100 * minDisp;
     // scratch of the MAD step (below): zeroed here, by one workgroup; the barriers of the trend passes publish it
     unsigned int *gscratch = reinterpret_cast<unsigned int *>(w.hist);
     if (mad && blockIdx.x == 0)
-        for (int k = tid; k < kMadScratchWords; k += kTpThreads) gscratch[k] = 0;
+        for (int k = tid; k < kMadZeroWords; k += kTpThreads) gscratch[k] = 0;
     bool alive = true;
     unsigned int pass = 0;
 #ifdef CHICDIFF_TREND_STAMPS
@@ -447,14 +666,27 @@ __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d,
     for (; pass < 11 * 27 + 16; pass++) {
         if (st.finished) break;
         TSTAMP(10);
-        double v[kTrendSums] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int k = tid; k < ncache; k += kTpThreads) {
-            const double y = s_y[k];
-            if (y > thr) trend_row_dev(&st, s_bm[k], y, v, s_lt);  // (NaN fails)
-        }
-        for (int64_t i = r0 + kTpCap + tid; i < r1; i += kTpThreads) {  // rows beyond the LDS cache stream from HBM
-            const double y = w.dispGene[i];
-            if (!w.allZero[i] && (y > 100 * minDisp)) trend_row_dev(&st, 1.0 / w.baseMean[i], y, v, s_lt);
+        const bool spec = st.spec_next != 0;  // set by the step before this pass: the same in every workgroup
+        const int nsums = spec ? kTpSums : kTrendSums;
+        double v[kTrendSums] = {0, 0, 0, 0, 0, 0, 0, 0}, u[kTrendSums] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (spec) {
+            for (int k = tid; k < ncache; k += kTpThreads) {
+                const double y = s_y[k];
+                if (y > thr) trend_row_spec_dev(&st, s_bm[k], y, v, u, s_lt);
+            }
+            for (int64_t i = r0 + kTpCap + tid; i < r1; i += kTpThreads) {
+                const double y = w.dispGene[i];
+                if (!w.allZero[i] && (y > 100 * minDisp)) trend_row_spec_dev(&st, 1.0 / w.baseMean[i], y, v, u, s_lt);
+            }
+        } else {
+            for (int k = tid; k < ncache; k += kTpThreads) {
+                const double y = s_y[k];
+                if (y > thr) trend_row_dev(&st, s_bm[k], y, v, s_lt);  // (NaN fails)
+            }
+            for (int64_t i = r0 + kTpCap + tid; i < r1; i += kTpThreads) {  // rows beyond the LDS cache stream from HBM
+                const double y = w.dispGene[i];
+                if (!w.allZero[i] && (y > 100 * minDisp)) trend_row_dev(&st, 1.0 / w.baseMean[i], y, v, s_lt);
+            }
         }
         TSTAMP(11);
 #pragma unroll
@@ -462,9 +694,16 @@ __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d,
             const double x = wave_sum_to_lane63(v[k]);
             if (lane == 63) red[k][wave] = x;
         }
+        if (spec) {  // (u through the same wave sum, workgroup sum and partial sum as v: the summation tree of a start pass)
+#pragma unroll
+            for (int k = 0; k < kTrendSums; k++) {
+                const double x = wave_sum_to_lane63(u[k]);
+                if (lane == 63) red[kTrendSums + k][wave] = x;
+            }
+        }
         __syncthreads();
-        double *mine = slots + ((size_t)(pass & 1) * gridDim.x + blockIdx.x) * kTrendSums;
-        if (tid < kTrendSums) {
+        double *mine = slots + ((size_t)(pass & 1) * gridDim.x + blockIdx.x) * kTpSums;
+        if (tid < nsums) {
             double acc = 0;
             for (int q = 0; q < kTpThreads / 64; q++) acc += red[tid][q];
             mine[tid] = acc;
@@ -475,19 +714,21 @@ __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d,
         if (!alive) break;
         // every workgroup: fixed-order sum of all partials (wave k sums quantity k: 64 lanes x strided
         // partials, then a shuffle tree — the same order in every workgroup), then the same state-machine step
-        const double *all = slots + (size_t)(pass & 1) * gridDim.x * kTrendSums;
-        if (wave < kTrendSums) {
+        const double *all = slots + (size_t)(pass & 1) * gridDim.x * kTpSums;
+        if (wave < nsums) {
             double acc = 0;
-            for (unsigned int b = lane; b < gridDim.x; b += 64) acc += all[(size_t)b * kTrendSums + wave];
+            for (unsigned int b = lane; b < gridDim.x; b += 64) acc += all[(size_t)b * kTpSums + wave];
             acc = wave_sum_to_lane63(acc);
             if (lane == 63) red[wave][0] = acc;
         }
         __syncthreads();
         TSTAMP(14);
         if (tid == 0) {
-            double sums[kTrendSums];
-            for (int k = 0; k < kTrendSums; k++) sums[k] = red[k][0];
-            trend_step(&st, sums);
+            double sv[kTrendSums], su[kTrendSums];  // (su is stale unless the pass speculated: not looked at then)
+#pragma unroll
+            for (int k = 0; k < kTrendSums; k++) { sv[k] = red[k][0]; su[k] = red[kTrendSums + k][0]; }
+            if (spec) trend_step_spec(&st, sv, su, speculate);
+            else trend_step_spec(&st, sv, nullptr, speculate);
         }
         __syncthreads();
         TSTAMP(15);
@@ -500,6 +741,16 @@ __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d,
         if (blockIdx.x == 0 && threadIdx.x == 0) { g_mad_t0 = __builtin_amdgcn_s_memrealtime(); g_mad_n = 0; }
 #endif
         const double c0 = st.coefs[0], c1 = st.coefs[1];
+        const bool vroute = madargs.value_route != 0;
+        const unsigned int vcap = (unsigned int)madargs.value_cap;
+        // the freed 1 / baseMean cache holds the selects' LDS histograms, staged candidates and the lists being searched
+        unsigned int *s_h = reinterpret_cast<unsigned int *>(s_bm);
+        unsigned int *vhist = gscratch + kMadScratchWords, *vcnt = vhist + kVbBins;
+        uint64_t *vcand = reinterpret_cast<uint64_t *>(gscratch + kMadZeroWords) + (size_t)4 * kSelCap;  // two lists of kVbCap keys
+        if (vroute) {
+            for (int k = tid; k < kVbBins; k += kTpThreads) s_h[k] = 0;
+            __syncthreads();
+        }
         // residuals as resid_kernel forms them (same expressions: same bits), to w.resid and — cached rows — over y in LDS
         for (int64_t k = tid; k < nrows; k += kTpThreads) {
             const int64_t i = r0 + k;
@@ -508,10 +759,10 @@ __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d,
             if (y >= thr) r = log(y) - log(c0 + c1 / w.baseMean[i]);
             w.resid[i] = r;
             if (k < ncache) s_y[k] = r;
+            if (vroute && r == r) atomicAdd(&s_h[vb_bin(r)], 1u);
         }
         __syncthreads();
         MSTAMP(0);
-        // the freed 1 / baseMean cache holds the select's LDS histograms and, afterwards, the candidates being sorted
         unsigned int *s_a = reinterpret_cast<unsigned int *>(s_bm), *s_b = s_a + kSelBins;
         uint64_t *sortbuf = reinterpret_cast<uint64_t *>(s_bm);
         const double *resid_g = w.resid + r0;
@@ -523,7 +774,50 @@ __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d,
             key = key_of(x);
             return true;
         };
-        alive = mad_select(key_resid, nrows, 0, gscratch, s_a, s_b, sortbuf, ctr, grp, pass, res, pop);
+        bool med_done = false, mad_done = false, empty = false;
+        VbPick pk = {};
+        if (vroute) {
+            for (int k = tid; k < kVbBins; k += kTpThreads)
+                if (s_h[k]) atomicAdd(&vhist[k], s_h[k]);
+            MSTAMP(21);
+            alive = grid_sync(ctr, grp, pass++);
+            MSTAMP(22);
+            if (alive) {
+                vb_load(vhist, s_h);
+                lds_hist_pick<kVbPer>(s_h, vsh, true, 0u, 0u, false);  // fit_state.h vb_pick; (its last barrier: the stage below overwrites the histogram)
+                pk.pop = vsh.total;
+                pk.rankA = pk.pop ? (pk.pop - 1) / 2 : 0;
+                pk.rankB = pk.pop / 2;
+                pk.binA = (int)vsh.pbin[0];
+                pk.binB = (int)vsh.pbin[1];
+                pk.below = vsh.pbelow[0];
+                pk.count = pk.binA == pk.binB ? vsh.pcnt[0] : vsh.pcnt[0] + vsh.pcnt[1];
+                empty = pk.pop == 0;
+                MSTAMP(23);
+                if (!empty && pk.count <= vcap) {
+                    const int binA = pk.binA, binB = pk.binB;
+                    auto in_bins = [&](int64_t k, uint64_t &key) {
+                        const double x = k < ncache ? s_y[k] : resid_g[k];
+                        if (x != x) return false;
+                        const int b = vb_bin(x);
+                        if (b != binA && b != binB) return false;
+                        key = key_of(x);
+                        return true;
+                    };
+                    vb_append(in_bins, nrows, sortbuf, vcap, &vcnt[0], vcand, vsh);
+                    MSTAMP(24);
+                    alive = grid_sync(ctr, grp, pass++);
+                    MSTAMP(25);
+                    if (alive && vcnt[0] == pk.count) {
+                        const double vlo = (double)binA / kVbScale - kVbOffset, scale = (double)kVbSub * kVbScale / (double)(binB + 1 - binA);
+                        med_done = vb_list_select(vcand, (int)pk.count, vlo, scale, (int)(pk.rankA - pk.below), (int)(pk.rankB - pk.below), sortbuf, vsh, res);
+                        pop = (double)pk.pop;
+                    }
+                    MSTAMP(26);
+                }
+            }
+        }
+        if (alive && !empty && !med_done) alive = mad_select(key_resid, nrows, 0, gscratch, s_a, s_b, sortbuf, ctr, grp, pass, res, pop);
         if (alive) {
             nres = pop;
             med = pop > 0 ? (value_of(res[0]) + value_of(res[1])) / 2.0 : NAN;  // R median(): mean of the two middles
@@ -536,7 +830,46 @@ __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d,
                 key = key_of(x);
                 return true;
             };
-            alive = mad_select(key_absdev, nrows, 1, gscratch, s_a, s_b, sortbuf, ctr, grp, pass, res, pop);
+            if (vroute && !empty && pop > 0) {
+                vb_load(vhist, s_h);
+                lds_hist_pick<kVbPer>(s_h, vsh, true, 0u, 0u, true);
+                vb_bracket_par(s_h, m0, pk.rankA, pk.rankB, vsh);  // (its last barrier: the stage below overwrites the histogram)
+                if (tid == 0) { vsh.pop = 0; vsh.below = 0; }
+                const double lo = vsh.lo, hi = vsh.hi;
+                MSTAMP(27);
+                // every row is classified by |x - med| itself: counted below the bracket, listed inside it, ignored above
+                unsigned int npop = 0, nbelow = 0;
+                auto in_bracket = [&](int64_t k, uint64_t &key) {
+                    if (!key_absdev(k, key)) return false;
+                    const double a = value_of(key);
+                    npop++;
+                    if (a < lo) nbelow++;
+                    return a >= lo && a < hi;
+                };
+                vb_append(in_bracket, nrows, sortbuf, vcap, &vcnt[1], vcand + kVbCap, vsh);
+                for (int off = 32; off > 0; off >>= 1) {
+                    npop += __shfl_down(npop, off);
+                    nbelow += __shfl_down(nbelow, off);
+                }
+                if (lane == 0 && npop) atomicAdd(&vsh.pop, npop);
+                if (lane == 0 && nbelow) atomicAdd(&vsh.below, nbelow);
+                __syncthreads();
+                if (tid == 0 && vsh.pop) atomicAdd(&vcnt[3], vsh.pop);
+                if (tid == 0 && vsh.below) atomicAdd(&vcnt[2], vsh.below);
+                MSTAMP(28);
+                alive = grid_sync(ctr, grp, pass++);
+                MSTAMP(29);
+                if (alive) {
+                    uint32_t kA = 0, kB = 0;
+                    if (vb_check(vcnt[3], vcnt[2], vcnt[1], vcap, &kA, &kB)) {
+                        const double scale = (double)kVbSub / (hi - lo);  // (0 for hi = +inf: a longer list is then not narrowed but refused)
+                        mad_done = vb_list_select(vcand + kVbCap, (int)vcnt[1], lo, scale, (int)kA, (int)kB, sortbuf, vsh, res);
+                        pop = (double)vcnt[3];
+                    }
+                }
+                MSTAMP(30);
+            }
+            if (alive && !mad_done) alive = mad_select(key_absdev, nrows, 1, gscratch, s_a, s_b, sortbuf, ctr, grp, pass, res, pop);
             if (alive) madv = 1.4826 * (pop > 0 ? (value_of(res[0]) + value_of(res[1])) / 2.0 : NAN);  // R mad(): constant 1.4826
         }
     }
@@ -614,6 +947,9 @@ void launch_trend_persistent(FitDims d, FitWork w, Opts o, hipStream_t st, bool 
     m.p = d.p;
     m.prior_in = o.dispPriorVarIn;
     m.by_simulation = (!(o.dispPriorVarIn == o.dispPriorVarIn) && d.S - d.p <= 3 && d.S > d.p) ? 1 : 0;
+    m.speculate = o.trend_speculate ? 1 : 0;
+    m.value_route = o.mad_route ? 1 : 0;
+    m.value_cap = (o.mad_value_cap > 0 && o.mad_value_cap < kVbCap) ? o.mad_value_cap : kVbCap;
     trend_persistent_kernel<<<(unsigned)blocks, kTpThreads, 0, st>>>(d, w, o.minDisp, m);
 }
 

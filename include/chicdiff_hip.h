@@ -111,6 +111,12 @@ int32_t chicdiff_hip_last_refits(const chicdiff_hip_ctx *ctx);
  *   "trend_persistent_blocks"   0 (default: one workgroup per CU), 1 .. 256: cap on the workgroups of the single-launch trend
  *                               kernel, for fits that share one GPU (its grid barrier needs all of them resident at once); the
  *                               coefficients then differ in summation order only (1e-13)
+ *   "trend_speculate"           1 (default) | 0: passes of the single-launch trend kernel that are likely to end a glm() call also sum
+ *                               what the next call's start pass would, so that pass is not run; 0 = every pass is run: same bits
+ *   "mad_select_route"          1 (default) | 0: the single-launch trend kernel takes the median and MAD of the residuals from one histogram over
+ *                               their values (three grid-wide rounds, radix select only where a candidate list does not fit); 0 = two
+ *                               radix selects (six rounds): same bits
+ *   "mad_value_cap"             0 (default: 8000) | 1 .. 8000: test hook, keys a candidate list of that histogram route may hold
  *   "trend_mad_in_kernel"       1 (default) | 0: the single-launch trend kernel goes on to the residuals, their exact median and MAD
  *                               and the closed-form prior variance; 0 = separate launches (residuals, two radix selects): same bits
  *   "fuse_offsets"              1 (default) | 0 | 2: chicdiff_hip_wald_test_dev and the theta grid form the offsets inside the fit's
