@@ -19,29 +19,13 @@
 
 #include <dlfcn.h>
 
+#include "chinput.h"
 #include "common.h"
+#include "peaks.h"
 #include "philox.h"
 #include "prior_mc.h"
 
 using namespace cd;
-
-namespace cd {  // chinput.hip
-struct ChinputCols {
-    std::vector<int32_t> bait, oe, N;
-    std::string error;
-};
-int64_t chinput_parse(const char *path, int nthreads, ChinputCols &c);
-struct ChinputFile {
-    const char *base = nullptr;
-    size_t size = 0, body = 0;
-    int ib = -1, io = -1, in = -1;
-    std::string error;
-};
-int chinput_open(const char *path, ChinputFile &f);
-void chinput_close(ChinputFile &f);
-std::string chinput_malformed(long long offset);
-hipError_t chinput_upload(const ChinputFile &f, char *d_text, char *pin, size_t half_bytes, int nthreads, hipStream_t st, hipEvent_t ev[2]);
-}  // namespace cd
 
 struct KTimer {
     std::string name;
@@ -107,6 +91,12 @@ struct chicdiff_hip_ctx {
     size_t chin_text_bytes = 0, chin_pin_half = 0, chin_cols_rows = 0;
     hipEvent_t chin_ev[2] = {nullptr, nullptr};
     int64_t chin_dev_rows = -1;             // >= 0: the read that came last was a device read of this many rows (chin_cols holds them)
+    // chicdiff_hip_peaks_read_dev: the columns of the peak matrix read last (grow-only, apart from every workspace; the text goes
+    // through chin_text / chin_pin): (6, pk_stride) int32, dist, (pk_nscore, pk_stride) scores, line offsets
+    char *pk_buf = nullptr;
+    size_t pk_buf_bytes = 0;
+    int64_t pk_stride = 0, pk_rows = -1;    // pk_rows >= 0: a successful read of this many rows
+    int pk_nscore = 0;
     // host-buffer entry point: columns that are final once the MAP dispersions exist leave for the host on a second
     // stream while the Wald stage runs (set for the duration of one chicdiff_hip_nbglm_fit call)
     struct EarlyCopy {
@@ -308,6 +298,7 @@ void chicdiff_hip_destroy(chicdiff_hip_ctx *c) {
     delete c->chin;
     if (c->chin_text) (void)hipFree(c->chin_text);
     if (c->chin_cols) (void)hipFree(c->chin_cols);
+    if (c->pk_buf) (void)hipFree(c->pk_buf);
     if (c->chin_pin) (void)hipHostFree(c->chin_pin);
     for (hipEvent_t e : c->chin_ev)
         if (e) (void)hipEventDestroy(e);
@@ -2509,6 +2500,44 @@ extern "C" int chicdiff_hip_chinput_parse_dev(chicdiff_hip_ctx *c, const uint8_t
     return rc;
 }
 
+// The body of an open file -> c->chin_text through the bounded pinned area (chinput_upload), both grow-only.  `what` names the entry
+// point in messages, `scope` the timer.
+static int upload_body(chicdiff_hip_ctx *c, const char *what, const char *scope, const ChinputFile &f) {
+    const size_t body = f.size - f.body;
+    if (body == 0) return CHICDIFF_OK;
+    constexpr size_t kHalfMax = (size_t)64 << 20;  // the pinned area is two halves of at most 64 MiB, whatever the file's size
+    const size_t half = body < kHalfMax ? ((body + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1)) : kHalfMax;
+    hipError_t e = hipSuccess;
+    if (c->chin_text_bytes < body) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->chin_text) { (void)hipFree(c->chin_text); c->chin_text = nullptr; c->chin_text_bytes = 0; }
+        const size_t bytes = align256(body);
+        if ((e = hipMalloc((void **)&c->chin_text, bytes)) != hipSuccess)
+            return fail(c, CHICDIFF_E_NOMEM, "%s: device text buffer for a file of %zu bytes: %s", what, f.size, hipGetErrorString(e));
+        c->chin_text_bytes = bytes;
+    }
+    if (c->chin_pin_half < half) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->chin_pin) { (void)hipHostFree(c->chin_pin); c->chin_pin = nullptr; c->chin_pin_half = 0; }
+        if ((e = hipHostMalloc((void **)&c->chin_pin, 2 * half)) != hipSuccess)
+            return fail(c, CHICDIFF_E_NOMEM, "%s: pinned staging of %zu bytes for a file of %zu bytes: %s", what, 2 * half, f.size,
+                        hipGetErrorString(e));
+        c->chin_pin_half = half;
+    }
+    for (hipEvent_t &ev : c->chin_ev)
+        if (!ev) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    {
+        Scope t(c, scope);
+        e = chinput_upload(f, c->chin_text, c->chin_pin, c->chin_pin_half, c->host.host_copy_threads, c->stream, c->chin_ev);
+    }
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);  // the staging area may still be read
+        timing_collect(c);
+        return fail(c, CHICDIFF_E_HIP, "%s: upload: %s", what, hipGetErrorString(e));
+    }
+    return CHICDIFF_OK;
+}
+
 extern "C" int chicdiff_hip_chinput_read_dev(chicdiff_hip_ctx *c, const char *path, int64_t *nrows_host) {
     if (!c) return CHICDIFF_E_INVALID;
     if (!path || !nrows_host) return fail(c, CHICDIFF_E_INVALID, "chinput_read: bad arguments");
@@ -2521,38 +2550,7 @@ extern "C" int chicdiff_hip_chinput_read_dev(chicdiff_hip_ctx *c, const char *pa
     delete c->chin;
     c->chin = nullptr;
     timing_reset(c);
-    if (body > 0) {
-        constexpr size_t kHalfMax = (size_t)64 << 20;  // the pinned area is two halves of at most 64 MiB, whatever the file's size
-        const size_t half = body < kHalfMax ? ((body + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1)) : kHalfMax;
-        hipError_t e = hipSuccess;
-        if (c->chin_text_bytes < body) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->chin_text) { (void)hipFree(c->chin_text); c->chin_text = nullptr; c->chin_text_bytes = 0; }
-            const size_t bytes = align256(body);
-            if ((e = hipMalloc((void **)&c->chin_text, bytes)) != hipSuccess)
-                return fail(c, CHICDIFF_E_NOMEM, "chinput_read: device text buffer for a file of %zu bytes: %s", f.size, hipGetErrorString(e));
-            c->chin_text_bytes = bytes;
-        }
-        if (c->chin_pin_half < half) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->chin_pin) { (void)hipHostFree(c->chin_pin); c->chin_pin = nullptr; c->chin_pin_half = 0; }
-            if ((e = hipHostMalloc((void **)&c->chin_pin, 2 * half)) != hipSuccess)
-                return fail(c, CHICDIFF_E_NOMEM, "chinput_read: pinned staging of %zu bytes for a file of %zu bytes: %s", 2 * half, f.size,
-                            hipGetErrorString(e));
-            c->chin_pin_half = half;
-        }
-        for (hipEvent_t &ev : c->chin_ev)
-            if (!ev) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        {
-            Scope t(c, "chinput_upload");
-            e = chinput_upload(f, c->chin_text, c->chin_pin, c->chin_pin_half, c->host.host_copy_threads, c->stream, c->chin_ev);
-        }
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(c->stream);  // the staging area may still be read
-            timing_collect(c);
-            return fail(c, CHICDIFF_E_HIP, "chinput_read: upload: %s", hipGetErrorString(e));
-        }
-    }
+    if (int rc = upload_body(c, "chinput_read", "chinput_upload", f)) return rc;
     const int rc = chinput_parse_impl(c, "chinput_read", (const uint8_t *)c->chin_text, (int64_t)body, f.ib, f.io, f.in, nullptr, nullptr, nullptr, 0,
                                       true, (int64_t)f.body, nrows_host, nullptr);
     if (rc) (void)hipStreamSynchronize(c->stream);
@@ -2587,6 +2585,296 @@ extern "C" int chicdiff_hip_chinput_table_dev(chicdiff_hip_ctx *c, const uint8_t
     HIPCHK(c, hipMemcpyAsync(d_o, c->chin->oe.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_n, c->chin->N.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
     return chicdiff_hip_count_table_dev(c, d_b, d_o, d_n, (int64_t)n, d_bait_in_RU, max_id, d_keys, d_vals, nkeys_host);
+}
+
+// ---- readAndFilterPeakMatrix on the device (chicdiff.R:218-277; peaks_kernels.hip, peaks.hip) -------------------------------------------
+extern "C" int chicdiff_hip_peaks_caps(int32_t *tile_bytes, int32_t *window_bytes, int32_t *max_scores, int32_t *max_slow) {
+    if (tile_bytes) *tile_bytes = CHICDIFF_CHINPUT_TILE_BYTES;
+    if (window_bytes) *window_bytes = CHICDIFF_CHINPUT_WINDOW_BYTES;
+    if (max_scores) *max_scores = CHICDIFF_PEAKS_MAX_SCORES;
+    if (max_slow) *max_slow = CHICDIFF_PEAKS_MAX_SLOW;
+    return CHICDIFF_OK;
+}
+
+static void peaks_info_clear(int64_t *info, int sep, int nscore, int64_t body) {
+    for (int k = 0; k < CHICDIFF_PEAKS_INFO_WORDS; k++) info[k] = 0;
+    info[CHICDIFF_PEAKS_INFO_MAXBAIT] = -1;
+    info[CHICDIFF_PEAKS_INFO_BAD] = -1;
+    info[CHICDIFF_PEAKS_INFO_BODY] = body;
+    info[CHICDIFF_PEAKS_INFO_SEP] = sep;
+    info[CHICDIFF_PEAKS_INFO_NSCORE] = nscore;
+}
+
+// the context's columns of `rows` rows and nscore score columns, as one grow-only allocation
+static PeaksOut peaks_ctx_out(chicdiff_hip_ctx *c, int64_t rows, int nscore) {
+    PeaksOut o;
+    const int64_t st = c->pk_stride;
+    o.ints = (int32_t *)c->pk_buf;
+    o.dist = (double *)(c->pk_buf + align256(sizeof(int32_t) * 6 * (size_t)st));
+    o.scores = o.dist + st;
+    o.line_off = (int64_t *)(o.scores + (size_t)nscore * (size_t)st);
+    o.stride = st;
+    o.cap = rows;
+    return o;
+}
+
+// Mark pass, scan, quote pass; host stop for the row count; parse pass; host stop for the verdict; the slow tokens settled from
+// h_body (the body in host memory; NULL: it is copied back from the device when a slow token turns up).  `grow`: the rows go to the
+// context's columns, sized once their number is known; otherwise to `out` (nrows > out.cap is refused before anything is written).
+static int peaks_parse_impl(chicdiff_hip_ctx *c, const char *what, const uint8_t *d_text, int64_t nbytes, const char *h_body, int sep,
+                            const int32_t *score_cols, int nscore, PeaksOut out, bool grow, int64_t file_offset, int64_t *info) {
+    if (nbytes == 0) return CHICDIFF_OK;
+    if (int rc = ensure_aux(c, peaks_parse_workspace_bytes(nbytes) + align256(sizeof(double) * CHICDIFF_PEAKS_MAX_SLOW))) return rc;
+    double *d_slow_val = (double *)(c->aux + peaks_parse_workspace_bytes(nbytes));
+    const int64_t *d_nrows = nullptr;
+    const unsigned long long *d_bad = nullptr;
+    {
+        Scope t(c, "peaks_mark");
+        if (launch_chinput_count(d_text, nbytes, c->aux, c->stream, &d_nrows, &d_bad)) return fail(c, CHICDIFF_E_HIP, "%s: memset failed", what);
+        if (launch_peaks_prepare(d_text, nbytes, score_cols, nscore, c->aux, c->stream)) return fail(c, CHICDIFF_E_HIP, "%s: workspace setup failed", what);
+    }
+    {
+        Scope t(c, "peaks_scan");
+        if (launch_chinput_scan(nbytes, c->aux, c->stream)) return fail(c, CHICDIFF_E_HIP, "%s: scan failed", what);
+    }
+    int64_t nrows = 0;
+    PeaksCounters cnt;
+    PeaksCounters *d_cnt = peaks_counters(c->aux, nbytes);
+    HIPCHK(c, hipMemcpyAsync(&nrows, d_nrows, sizeof nrows, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    info[CHICDIFF_PEAKS_INFO_NROWS] = nrows;
+    if (cnt.quote) {
+        info[CHICDIFF_PEAKS_INFO_STATUS] |= CHICDIFF_PEAKS_ST_QUOTE;
+        return CHICDIFF_OK;
+    }
+    if (nrows >= ((int64_t)1 << 31)) return fail(c, CHICDIFF_E_INVALID, "%s: %lld rows: the device reader takes fewer than 2^31", what, (long long)nrows);
+    if (grow) {
+        const size_t rows = ((size_t)nrows + 63) & ~(size_t)63;
+        const size_t need = align256(sizeof(int32_t) * 6 * rows) + sizeof(double) * rows * (size_t)(1 + nscore) + sizeof(int64_t) * rows;
+        if (c->pk_buf_bytes < need) {
+            if (c->pk_buf) { (void)hipFree(c->pk_buf); c->pk_buf = nullptr; c->pk_buf_bytes = 0; }
+            hipError_t e = hipMalloc((void **)&c->pk_buf, need);
+            if (e != hipSuccess)
+                return fail(c, CHICDIFF_E_NOMEM, "%s: device columns of %lld rows for a file of %lld bytes: %s", what, (long long)nrows,
+                            (long long)(file_offset + nbytes), hipGetErrorString(e));
+            c->pk_buf_bytes = need;
+        }
+        c->pk_stride = (int64_t)rows;
+        out = peaks_ctx_out(c, nrows, nscore);
+    }
+    if (nrows > out.cap) return fail(c, CHICDIFF_E_INVALID, "%s: the text holds %lld rows, the columns have room for %lld", what, (long long)nrows, (long long)out.cap);
+    if (nrows == 0) return CHICDIFF_OK;  // blank lines only
+    {
+        Scope t(c, "peaks_parse");
+        launch_peaks_parse(d_text, nbytes, sep, nscore, out, c->aux, c->stream);
+    }
+    unsigned long long bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    if (bad != ~0ull) {
+        info[CHICDIFF_PEAKS_INFO_BAD] = (int64_t)bad;
+        return fail(c, CHICDIFF_E_INVALID, "%s: %s", what, peaks_malformed((long long)bad + (long long)file_offset).c_str());
+    }
+    info[CHICDIFF_PEAKS_INFO_MAXBAIT] = cnt.maxbait;
+    info[CHICDIFF_PEAKS_INFO_NSLOW] = (int64_t)cnt.nslow;
+    if (cnt.nslow > (unsigned int)CHICDIFF_PEAKS_MAX_SLOW) {
+        info[CHICDIFF_PEAKS_INFO_STATUS] |= CHICDIFF_PEAKS_ST_SLOW_OVERFLOW;
+        return CHICDIFF_OK;
+    }
+    if (cnt.nslow > 0) {  // the tokens the device left undecided: strtod on the host, one kernel writes the cells
+        Scope t(c, "peaks_patch");
+        const size_t ns = cnt.nslow;
+        std::vector<PeaksSlow> list(ns);
+        std::vector<double> val(ns);
+        std::vector<char> copy;
+        HIPCHK(c, hipMemcpyAsync(list.data(), peaks_slow_list(c->aux, nbytes), sizeof(PeaksSlow) * ns, hipMemcpyDeviceToHost, c->stream));
+        if (!h_body) {
+            copy.resize((size_t)nbytes);
+            HIPCHK(c, hipMemcpyAsync(copy.data(), d_text, (size_t)nbytes, hipMemcpyDeviceToHost, c->stream));
+            h_body = copy.data();
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < ns; i++) {
+            const int64_t off = list[i].off;
+            if (off < 0 || off >= nbytes || list[i].row < 0 || list[i].row >= nrows || list[i].col < -1 || list[i].col >= nscore)
+                return fail(c, CHICDIFF_E_HIP, "%s: slow-token list entry %zu out of range", what, i);
+            const char *p = h_body + off;
+            if (!peaks_decimal_host(p, peaks_field_end(p, h_body + nbytes, sep), &val[i]))
+                return fail(c, CHICDIFF_E_HIP, "%s: the host refuses a token the device took (body offset %lld)", what, (long long)off);
+        }
+        HIPCHK(c, hipMemcpyAsync(d_slow_val, val.data(), sizeof(double) * ns, hipMemcpyHostToDevice, c->stream));
+        launch_peaks_patch(d_slow_val, (int)ns, out, c->aux, nbytes, c->stream);
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // val and list leave scope
+        HIPCHK(c, hipGetLastError());
+    }
+    return CHICDIFF_OK;
+}
+
+static int peaks_check_cols(chicdiff_hip_ctx *c, const char *what, int32_t sep, const int32_t *score_cols, int32_t nscore) {
+    if (sep != '\t' && sep != ',' && sep != ' ') return fail(c, CHICDIFF_E_INVALID, "%s: the separator is a tab, a comma or a blank", what);
+    if (nscore < 0 || nscore > CHICDIFF_PEAKS_MAX_SCORES || (nscore > 0 && !score_cols))
+        return fail(c, CHICDIFF_E_INVALID, "%s: 0 .. %d score columns", what, CHICDIFF_PEAKS_MAX_SCORES);
+    for (int j = 0; j < nscore; j++)
+        if (score_cols[j] < CHICDIFF_PEAKS_KEY_COLUMNS || (j > 0 && score_cols[j] <= score_cols[j - 1]))
+            return fail(c, CHICDIFF_E_INVALID, "%s: score columns are fields from %d on, ascending", what, CHICDIFF_PEAKS_KEY_COLUMNS);
+    return CHICDIFF_OK;
+}
+
+extern "C" int chicdiff_hip_peaks_parse_dev(chicdiff_hip_ctx *c, const uint8_t *d_text, int64_t nbytes, int32_t sep, const int32_t *score_cols,
+                                            int32_t nscore, int32_t *d_ints, double *d_dist, double *d_scores, int64_t *d_line_off, int64_t cap,
+                                            int64_t *info) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (!info || nbytes < 0 || cap < 0 || (nbytes > 0 && !d_text) || (cap > 0 && (!d_ints || !d_dist || !d_line_off)))
+        return fail(c, CHICDIFF_E_INVALID, "peaks_parse: bad arguments");
+    if (int rc = peaks_check_cols(c, "peaks_parse", sep, score_cols, nscore)) return rc;
+    if (cap > 0 && nscore > 0 && !d_scores) return fail(c, CHICDIFF_E_INVALID, "peaks_parse: bad arguments");
+    if ((uintptr_t)d_text & 15) return fail(c, CHICDIFF_E_INVALID, "peaks_parse: d_text must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    peaks_info_clear(info, sep, nscore, 0);
+    timing_reset(c);
+    const PeaksOut out{d_ints, d_dist, d_scores, d_line_off, cap, cap};
+    const int rc = peaks_parse_impl(c, "peaks_parse", d_text, nbytes, nullptr, sep, score_cols, nscore, out, false, 0, info);
+    if (rc) (void)hipStreamSynchronize(c->stream);
+    timing_collect(c);
+    return rc;
+}
+
+extern "C" int chicdiff_hip_peaks_read_dev(chicdiff_hip_ctx *c, const char *path, const char *const *targets, int32_t ntargets,
+                                           int32_t *score_target, int64_t *info) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (!path || !info || ntargets < 0 || (ntargets > 0 && (!targets || !score_target))) return fail(c, CHICDIFF_E_INVALID, "peaks_read: bad arguments");
+    c->pk_rows = -1;  // nothing to serve until this read has succeeded
+    PeaksFile f;
+    if (peaks_open(path, targets, ntargets, f) != 0) return fail(c, CHICDIFF_E_INVALID, "peaks_read: %s", f.error.c_str());
+    struct Closer { PeaksFile &f; ~Closer() { peaks_close(f); } } closer{f};
+    const size_t body = f.file.size - f.file.body;
+    peaks_info_clear(info, f.sep, f.nscore, (int64_t)f.file.body);
+    for (int j = 0; j < f.nscore; j++) score_target[j] = f.score_target[j];
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    if (int rc = upload_body(c, "peaks_read", "peaks_upload", f.file)) return rc;
+    const int rc = peaks_parse_impl(c, "peaks_read", (const uint8_t *)c->chin_text, (int64_t)body, f.file.base + f.file.body, f.sep, f.score_col,
+                                    f.nscore, PeaksOut{}, true, (int64_t)f.file.body, info);
+    if (rc) (void)hipStreamSynchronize(c->stream);
+    timing_collect(c);
+    if (rc) return rc;
+    if (info[CHICDIFF_PEAKS_INFO_STATUS] == 0) {
+        c->pk_rows = info[CHICDIFF_PEAKS_INFO_NROWS];
+        c->pk_nscore = f.nscore;
+    }
+    return CHICDIFF_OK;
+}
+
+extern "C" int chicdiff_hip_peaks_columns_dev(chicdiff_hip_ctx *c, int32_t *d_ints, double *d_dist, double *d_scores, int64_t *d_line_off,
+                                              int64_t cap) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (c->pk_rows < 0) return fail(c, CHICDIFF_E_INVALID, "peaks_columns: nothing read (call chicdiff_hip_peaks_read_dev first)");
+    const int64_t n = c->pk_rows;
+    if (cap < n || (n > 0 && (!d_ints || !d_dist || !d_line_off || (c->pk_nscore > 0 && !d_scores))))
+        return fail(c, CHICDIFF_E_INVALID, "peaks_columns: the columns hold %lld rows, the caller's have room for %lld", (long long)n, (long long)cap);
+    if (n == 0) return CHICDIFF_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const PeaksOut o = peaks_ctx_out(c, n, c->pk_nscore);
+    HIPCHK(c, hipMemcpy2DAsync(d_ints, sizeof(int32_t) * (size_t)cap, o.ints, sizeof(int32_t) * (size_t)o.stride, sizeof(int32_t) * (size_t)n, 6,
+                               hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_dist, o.dist, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+    if (c->pk_nscore > 0)
+        HIPCHK(c, hipMemcpy2DAsync(d_scores, sizeof(double) * (size_t)cap, o.scores, sizeof(double) * (size_t)o.stride, sizeof(double) * (size_t)n,
+                                   (size_t)c->pk_nscore, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_line_off, o.line_off, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CHICDIFF_OK;
+}
+
+extern "C" int chicdiff_hip_peaks_filter_dev(chicdiff_hip_ctx *c, const int32_t *d_bait, const int32_t *d_oe, const double *d_dist,
+                                             const double *d_scores, int64_t n, int32_t nscore, double score, const int32_t *cond_of_col,
+                                             int32_t ncond, int32_t replicate_rule, int64_t maxbait, int64_t *d_kept_idx, int32_t *d_kept_bait,
+                                             int32_t *d_kept_oe, int32_t *d_filtered, int64_t *nkept_host, int64_t *nfiltered_host) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (!nkept_host || !nfiltered_host || n < 0 || n >= ((int64_t)1 << 31) || nscore < 0 || nscore > CHICDIFF_PEAKS_MAX_SCORES || ncond < 0 ||
+        maxbait < -1 || maxbait > 2147483647LL || (nscore > 0 && !cond_of_col) ||
+        (n > 0 && (!d_bait || !d_oe || !d_dist || (nscore > 0 && !d_scores) || !d_kept_idx || !d_kept_bait || !d_kept_oe || !d_filtered)))
+        return fail(c, CHICDIFF_E_INVALID, "peaks_filter: bad arguments");
+    *nkept_host = *nfiltered_host = 0;
+    if (n == 0) return CHICDIFF_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_aux(c, peaks_filter_workspace_bytes(n, maxbait))) return rc;
+    timing_reset(c);
+    const int64_t *d_totals = nullptr;
+    {
+        Scope t(c, "peaks_filter");
+        if (launch_peaks_filter(d_bait, d_oe, d_dist, d_scores, n, n, nscore, score, cond_of_col, ncond, replicate_rule, maxbait, d_kept_idx,
+                                d_kept_bait, d_kept_oe, d_filtered, c->aux, c->stream, &d_totals)) {
+            (void)hipStreamSynchronize(c->stream);
+            return fail(c, CHICDIFF_E_HIP, "peaks_filter: %s", hipGetErrorString(hipGetLastError()));
+        }
+    }
+    int64_t totals = 0;
+    HIPCHK(c, hipMemcpyAsync(&totals, d_totals, sizeof totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    timing_collect(c);
+    *nkept_host = totals & 0xffffffffll;
+    *nfiltered_host = totals >> 32;
+    return CHICDIFF_OK;
+}
+
+// the host statement of the same rule (peaks.hip): no device, no context
+extern "C" int chicdiff_hip_selftest_peaks(const char *path, const char *const *targets, int32_t ntargets, double score, const int32_t *cond_of_target,
+                                           int32_t ncond, int32_t replicate_rule, int64_t cap, int32_t *ints, double *dist, double *scores,
+                                           int64_t *line_off, int64_t *kept_idx, int32_t *filtered, int32_t *score_target, int64_t *info, char *err,
+                                           int32_t errcap) {
+    if (!path || !info || ntargets < 0 || cap < 0 || (ntargets > 0 && (!targets || !cond_of_target))) return CHICDIFF_E_INVALID;
+    auto refuse = [&](const std::string &msg) {
+        if (err && errcap > 0) snprintf(err, (size_t)errcap, "%s", msg.c_str());
+        return CHICDIFF_E_INVALID;
+    };
+    PeaksFile f;
+    if (peaks_open(path, targets, ntargets, f) != 0) return refuse(f.error);
+    struct Closer { PeaksFile &f; ~Closer() { peaks_close(f); } } closer{f};
+    peaks_info_clear(info, f.sep, f.nscore, (int64_t)f.file.body);
+    const char *body = f.file.base + f.file.body;
+    const size_t nbytes = f.file.size - f.file.body;
+    // first the count, then the rows into columns of the statement's own
+    long long bad = -1;
+    int quote = 0, maxbait = -1;
+    const int64_t nrows = peaks_parse_host(body, nbytes, f.sep, f.score_col, f.nscore, PeaksOut{nullptr, nullptr, nullptr, nullptr, 0, 0}, &bad, &quote, &maxbait);
+    info[CHICDIFF_PEAKS_INFO_NROWS] = nrows;
+    if (quote) {
+        info[CHICDIFF_PEAKS_INFO_STATUS] = CHICDIFF_PEAKS_ST_QUOTE;
+        return CHICDIFF_OK;
+    }
+    if (bad >= 0) {
+        info[CHICDIFF_PEAKS_INFO_BAD] = bad;
+        return refuse(peaks_malformed(bad + (long long)f.file.body));
+    }
+    const size_t n = (size_t)nrows;
+    std::vector<int32_t> vi(6 * n + 1), cond(f.nscore + 1);
+    std::vector<double> vd(n + 1), vs((size_t)f.nscore * n + 1);
+    std::vector<int64_t> vo(n + 1);
+    (void)peaks_parse_host(body, nbytes, f.sep, f.score_col, f.nscore, PeaksOut{vi.data(), vd.data(), vs.data(), vo.data(), nrows, nrows}, &bad, &quote, &maxbait);
+    info[CHICDIFF_PEAKS_INFO_MAXBAIT] = maxbait;
+    for (int j = 0; j < f.nscore; j++) {
+        cond[j] = cond_of_target[f.score_target[j]];
+        if (score_target) score_target[j] = f.score_target[j];
+    }
+    std::vector<int64_t> kept;
+    std::vector<int32_t> filt;
+    peaks_filter_host(vi.data() + 2 * n, vi.data() + 5 * n, vd.data(), vs.data(), nrows, nrows, f.nscore, score, cond.data(), ncond, replicate_rule, kept, filt);
+    info[CHICDIFF_PEAKS_INFO_NKEPT] = (int64_t)kept.size();
+    info[CHICDIFF_PEAKS_INFO_NFILTERED] = (int64_t)filt.size();
+    const size_t m = (size_t)(nrows < cap ? nrows : cap);
+    for (int k = 0; k < 6 && ints; k++) memcpy(ints + (size_t)k * (size_t)cap, vi.data() + (size_t)k * n, 4 * m);
+    if (dist) memcpy(dist, vd.data(), 8 * m);
+    for (int j = 0; j < f.nscore && scores; j++) memcpy(scores + (size_t)j * (size_t)cap, vs.data() + (size_t)j * n, 8 * m);
+    if (line_off) memcpy(line_off, vo.data(), 8 * m);
+    if (kept_idx) memcpy(kept_idx, kept.data(), 8 * (kept.size() < (size_t)cap ? kept.size() : (size_t)cap));
+    if (filtered) memcpy(filtered, filt.data(), 4 * (filt.size() < (size_t)cap ? filt.size() : (size_t)cap));
+    return CHICDIFF_OK;
 }
 
 // ---- device memory for hosts without their own GPU arrays (the R shim) ---------------------------------------

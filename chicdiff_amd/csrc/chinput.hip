@@ -20,14 +20,10 @@
 #include <thread>
 #include <vector>
 
+#include "chinput.h"
 #include "common.h"
 
 namespace cd {
-
-struct ChinputCols {
-    std::vector<int32_t> bait, oe, N;
-    std::string error;
-};
 
 static inline bool is_sep(char ch) { return ch == '\t' || ch == ' ' || ch == ','; }
 
@@ -57,15 +53,6 @@ static inline bool parse_line(const char *p, const char *e, int ib, int io, int 
     }
     return got == 3;
 }
-
-// The file mapped, and what its comment lines and header say: both parsers start here.  body = the bytes after the header line;
-// ib, io, in = the 0-based columns of baitID, otherEndID, N (quoted names and any column order accepted).
-struct ChinputFile {
-    const char *base = nullptr;
-    size_t size = 0, body = 0;  // body: offset of the first byte after the header line
-    int ib = -1, io = -1, in = -1;
-    std::string error;
-};
 
 void chinput_close(ChinputFile &f) {
     if (f.base) munmap((void *)f.base, f.size);

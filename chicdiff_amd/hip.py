@@ -31,6 +31,8 @@ EXPORTS = [
     "chicdiff_hip_control_draws_dev", "chicdiff_hip_countput_dev", "chicdiff_hip_countput_caps",
     "chicdiff_hip_chinput_read", "chicdiff_hip_chinput_table_dev", "chicdiff_hip_region_avdist_dev",
     "chicdiff_hip_chinput_parse_dev", "chicdiff_hip_chinput_read_dev", "chicdiff_hip_chinput_caps",
+    "chicdiff_hip_peaks_parse_dev", "chicdiff_hip_peaks_read_dev", "chicdiff_hip_peaks_columns_dev", "chicdiff_hip_peaks_filter_dev",
+    "chicdiff_hip_peaks_caps", "chicdiff_hip_selftest_peaks",
     "chicdiff_hip_count_join_inner_dev", "chicdiff_hip_count_join_multi_dev", "chicdiff_hip_region_assemble_dev",
     "chicdiff_hip_malloc", "chicdiff_hip_free", "chicdiff_hip_outstanding_allocations", "chicdiff_hip_memcpy_h2d", "chicdiff_hip_memcpy_d2h",
     "chicdiff_hip_rccl_unique_id", "chicdiff_hip_rccl_init", "chicdiff_hip_cooks_filter_dev",
@@ -134,6 +136,14 @@ def load_library() -> C.CDLL:
     L.chicdiff_hip_chinput_parse_dev.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
     L.chicdiff_hip_chinput_read_dev.argtypes = [vp, C.c_char_p, C.POINTER(i64)]
     L.chicdiff_hip_chinput_caps.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.chicdiff_hip_peaks_parse_dev.argtypes = [vp, vp, i64, i32, C.POINTER(i32), i32, vp, vp, vp, vp, i64, C.POINTER(i64)]
+    L.chicdiff_hip_peaks_read_dev.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), i32, C.POINTER(i32), C.POINTER(i64)]
+    L.chicdiff_hip_peaks_columns_dev.argtypes = [vp, vp, vp, vp, vp, i64]
+    L.chicdiff_hip_peaks_filter_dev.argtypes = [vp, vp, vp, vp, vp, i64, i32, dbl, C.POINTER(i32), i32, i32, i64, vp, vp, vp, vp,
+                                                C.POINTER(i64), C.POINTER(i64)]
+    L.chicdiff_hip_peaks_caps.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.chicdiff_hip_selftest_peaks.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), i32, dbl, C.POINTER(i32), i32, i32, i64, vp, vp, vp, vp, vp, vp,
+                                              C.POINTER(i32), C.POINTER(i64), C.c_char_p, i32]
     L.chicdiff_hip_bh_adjust_dev.argtypes = [vp, vp, i64, vp]
     L.chicdiff_hip_region_avdist_dev.argtypes = [vp, vp, vp, i64, vp, i64, i32, i32, vp, vp, vp]
     L.chicdiff_hip_count_join_inner_dev.argtypes = [vp, vp, vp, i64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp]
@@ -209,6 +219,83 @@ def chinput_caps() -> dict:
     t, l, w = C.c_int32(0), C.c_int32(0), C.c_int32(0)
     load_library().chicdiff_hip_chinput_caps(C.byref(t), C.byref(l), C.byref(w))
     return dict(tile_bytes=t.value, lane_bytes=l.value, window_bytes=w.value)
+
+
+# include/chicdiff_hip.h, CHICDIFF_PEAKS_*
+PEAKS_ST_QUOTE, PEAKS_ST_SLOW_OVERFLOW = 1, 2
+PEAKS_INFO = ("nrows", "status", "maxbait", "nslow", "bad", "body", "sep", "nscore", "nkept", "nfiltered")
+PEAKS_INT_COLUMNS = ("baitStart", "baitEnd", "baitID", "oeStart", "oeEnd", "oeID")
+
+
+def peaks_caps() -> dict:
+    """The limits of ``HipContext.read_peaks`` / ``parse_peaks_text`` as the library was built (include/chicdiff_hip.h): the tile and
+    the staged window (chinput's), the most score columns, and the entries of the slow-token list."""
+    t, w, m, sl = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    load_library().chicdiff_hip_peaks_caps(C.byref(t), C.byref(w), C.byref(m), C.byref(sl))
+    return dict(tile_bytes=t.value, window_bytes=w.value, max_scores=m.value, max_slow=sl.value)
+
+
+def _c_strings(names):
+    arr = (C.c_char_p * max(len(names), 1))()
+    for k, v in enumerate(names):
+        arr[k] = str(v).encode()
+    return arr
+
+
+def selftest_peaks(path, targetColumns, score=5.0, cond_of_target=None, replicate_rule=False):
+    """The library's HOST statement of the peak-matrix rule (chicdiff_hip_selftest_peaks: no device, no context) on a file: a dict
+    with ``info`` (PEAKS_INFO), the columns of all rows (``ints`` (6, n), ``dist``, ``scores`` (nscore, n), ``line_off``),
+    ``score_target``, ``kept_idx`` and ``filtered``.  A header or malformed-row error raises ValueError with the library's message
+    (``.offset``: the body offset of a malformed row, else None)."""
+    lib = load_library()
+    targets = list(targetColumns)
+    T = len(targets)
+    cond = np.zeros(max(T, 1), dtype=np.int32)
+    if cond_of_target is not None:
+        cond[:T] = np.asarray(cond_of_target, dtype=np.int32)
+    ncond = int(cond[:T].max()) + 1 if T else 0
+    names = _c_strings(targets)
+    info = (C.c_int64 * len(PEAKS_INFO))()
+    err = C.create_string_buffer(512)
+    st = np.zeros(max(T, 1), dtype=np.int32)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+
+    def call(cap, ints, dist, scores, line_off, kept, filt):
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        rc = lib.chicdiff_hip_selftest_peaks(os.fsencode(path), names, T, float(score), ip(cond), ncond, int(bool(replicate_rule)), cap, ptr(ints),
+                                             ptr(dist), ptr(scores), ptr(line_off), ptr(kept), ptr(filt), ip(st), info, err, 512)
+        if rc:
+            e = ValueError(err.value.decode() or f"selftest_peaks: error {rc}")
+            e.offset = info[4] if info[4] >= 0 else None
+            raise e
+    call(0, None, None, None, None, None, None)
+    d = dict(zip(PEAKS_INFO, info))
+    n, ns = d["nrows"], d["nscore"]
+    if d["status"]:
+        return dict(info=d)
+    ints, dist = np.zeros((6, n), dtype=np.int32), np.zeros(n)
+    scores, line_off = np.zeros((ns, n)), np.zeros(n, dtype=np.int64)
+    kept, filt = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+    if n:
+        call(n, ints, dist, scores, line_off, kept, filt)
+    d = dict(zip(PEAKS_INFO, info))
+    return dict(info=d, ints=ints, dist=dist, scores=scores, line_off=line_off, score_target=st[:ns].copy(), kept_idx=kept[:d["nkept"]],
+                filtered=filt[:d["nfiltered"]])
+
+
+class Peaks:
+    """A peak matrix on the device (``HipContext.read_peaks`` / ``parse_peaks_text``): ``ints`` (6, n) int32 — PEAKS_INT_COLUMNS, also
+    as attributes —, ``dist`` (n) and ``scores`` (nscore, n) float64, ``line_off`` (n) int64: the offset of every row's line in the body;
+    ``info``: the words of PEAKS_INFO; ``score_names``: the score rows' column names (file order).  ``status`` != 0 (PEAKS_ST_*): the
+    device did not parse this body and no column is held."""
+
+    def __init__(self, info, ints=None, dist=None, scores=None, line_off=None, score_names=None, path=None):
+        self.info, self.ints, self.dist, self.scores, self.line_off = info, ints, dist, scores, line_off
+        self.score_names, self.path = score_names, path
+        self.n, self.nscore, self.status, self.maxbait = info["nrows"], info["nscore"], info["status"], info["maxbait"]
+        if ints is not None:
+            for k, name in enumerate(PEAKS_INT_COLUMNS):
+                setattr(self, name, ints[k])
 
 
 def _scalars_dict(s: Scalars) -> dict:
@@ -559,6 +646,83 @@ class HipContext:
             self.h, d_bait_in_RU.data_ptr() if d_bait_in_RU is not None else None,
             d_bait_in_RU.numel() - 1 if d_bait_in_RU is not None else 0, keys.data_ptr(), vals.data_ptr(), C.byref(nk)))
         return keys[: nk.value], vals[: nk.value], nrows.value
+
+    # -- readAndFilterPeakMatrix on the device (chicdiff.R:218-277) -------------------------------------
+    def _peaks_empty(self, n, ns):
+        torch = self.torch
+        return (torch.empty((6, n), dtype=torch.int32, device=self.device), torch.empty(n, dtype=torch.float64, device=self.device),
+                torch.empty((ns, n), dtype=torch.float64, device=self.device), torch.empty(n, dtype=torch.int64, device=self.device))
+
+    def parse_peaks_text(self, d_text, sep, score_cols):
+        """The body of a peak matrix (the bytes after its header line) as a uint8 device tensor -> ``Peaks``; ``sep``: the separator
+        (one character), ``score_cols``: the 0-based fields of the score columns, ascending, from 11 on.  The rule stands above
+        chicdiff_hip_peaks_parse_dev in include/chicdiff_hip.h.  A malformed line raises, ``.offset`` its body offset."""
+        torch = self.torch
+        if d_text.dtype != torch.uint8 or d_text.dim() != 1:
+            raise ValueError("parse_peaks_text: d_text is a one-dimensional uint8 tensor")
+        d_text = d_text.contiguous()
+        if d_text.data_ptr() % 16:
+            d_text = d_text.clone()
+        n = d_text.numel()
+        cols = np.ascontiguousarray(score_cols, dtype=np.int32)
+        ns = len(cols)
+        cp = cols.ctypes.data_as(C.POINTER(C.c_int32))
+        sepb = ord(sep) if isinstance(sep, str) else int(sep)
+        info = (C.c_int64 * len(PEAKS_INFO))()
+        # first with no room at all: the call reports the row count before it writes anything
+        rc = self.lib.chicdiff_hip_peaks_parse_dev(self.h, d_text.data_ptr(), n, sepb, cp, ns, None, None, None, None, 0, info)
+        if rc and info[0] == 0:
+            self._check(rc)
+        if info[1]:
+            return Peaks(dict(zip(PEAKS_INFO, info)))
+        ints, dist, scores, line_off = self._peaks_empty(info[0], ns)
+        if info[0]:
+            rc = self.lib.chicdiff_hip_peaks_parse_dev(self.h, d_text.data_ptr(), n, sepb, cp, ns, ints.data_ptr(), dist.data_ptr(),
+                                                       scores.data_ptr(), line_off.data_ptr(), info[0], info)
+            if rc:
+                err = ChicdiffHipError(f"[{rc}] " + self.lib.chicdiff_hip_last_error(self.h).decode())
+                err.offset = info[4] if info[4] >= 0 else None
+                raise err
+        d = dict(zip(PEAKS_INFO, info))
+        return Peaks(d) if d["status"] else Peaks(d, ints, dist, scores, line_off)
+
+    def read_peaks(self, path, targetColumns):
+        """fread(peakFile)[, c(1:11, sel)] on the device (chicdiff_hip_peaks_read_dev): header on the host, the body uploaded as bytes
+        and parsed there -> ``Peaks`` (its tensors are copies of the context's columns).  ``status`` != 0: the caller reads the file
+        some other way.  A header the rule refuses or a malformed row raises."""
+        targets = list(targetColumns)
+        info = (C.c_int64 * len(PEAKS_INFO))()
+        st = (C.c_int32 * max(len(targets), 1))()
+        self._check(self.lib.chicdiff_hip_peaks_read_dev(self.h, os.fsencode(path), _c_strings(targets), len(targets), st, info))
+        d = dict(zip(PEAKS_INFO, info))
+        names = [targets[st[j]] for j in range(d["nscore"])]
+        if d["status"]:
+            return Peaks(d, score_names=names, path=path)
+        ints, dist, scores, line_off = self._peaks_empty(d["nrows"], d["nscore"])
+        if d["nrows"]:
+            self._check(self.lib.chicdiff_hip_peaks_columns_dev(self.h, ints.data_ptr(), dist.data_ptr(), scores.data_ptr(), line_off.data_ptr(),
+                                                                d["nrows"]))
+        return Peaks(d, ints, dist, scores, line_off, score_names=names, path=path)
+
+    def filter_peaks(self, peaks, score, cond_of_col, replicate_rule):
+        """The four filters of readAndFilterPeakMatrix (chicdiff.R:246-270) on a ``Peaks``: ``cond_of_col[j]`` = the condition (0-based,
+        -1 = none) of score row j.  Returns ``kept_idx`` (int64, file order), the kept rows' ``baitID`` / ``oeID`` (int32) and
+        ``filtered_baits`` (int32: the baits without a kept row, in order of first appearance), device tensors."""
+        torch = self.torch
+        n, ns = peaks.n, peaks.nscore
+        cond = np.ascontiguousarray(cond_of_col, dtype=np.int32)
+        if len(cond) != ns:
+            raise ValueError("filter_peaks: one condition per score column")
+        ncond = int(cond.max()) + 1 if ns else 0
+        kept = torch.empty(n, dtype=torch.int64, device=self.device)
+        kb, ko, fb = (torch.empty(n, dtype=torch.int32, device=self.device) for _ in range(3))
+        nk, nf = C.c_int64(0), C.c_int64(0)
+        scores = peaks.scores.contiguous()
+        self._check(self.lib.chicdiff_hip_peaks_filter_dev(
+            self.h, peaks.baitID.data_ptr(), peaks.oeID.data_ptr(), peaks.dist.data_ptr(), scores.data_ptr(), n, ns, float(score),
+            cond.ctypes.data_as(C.POINTER(C.c_int32)), ncond, int(bool(replicate_rule)), int(peaks.maxbait), kept.data_ptr(), kb.data_ptr(),
+            ko.data_ptr(), fb.data_ptr(), C.byref(nk), C.byref(nf)))
+        return dict(kept_idx=kept[: nk.value], baitID=kb[: nk.value], oeID=ko[: nk.value], filtered_baits=fb[: nf.value])
 
     # -- a9: results() ---------------------------------------------------------------------------
     def cooks_filter(self, d_counts, group, d_maxCooks, d_cooksArgmax, d_pvalue, cutoff):

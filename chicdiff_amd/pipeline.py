@@ -32,8 +32,118 @@ from .settings import asChicdiffSettings, conditions_per_sample, sample_names
 PEAK_KEY_COLUMNS = ["baitChr", "baitStart", "baitEnd", "baitID", "baitName", "oeChr", "oeStart", "oeEnd", "oeID", "oeName", "dist"]
 
 
-# ---- readAndFilterPeakMatrix, chicdiff.R:218-277 (text I/O; kept on the host as in the reference) -----------------------
-def readAndFilterPeakMatrix(peakFiles, targetColumns, chicagoData, conditions, score, outprefix=""):
+# ---- readAndFilterPeakMatrix, chicdiff.R:218-277 (text I/O; on the host as in the reference unless device=True) ---------
+PEAK_TEXT_FIELDS = (0, 4, 5, 9)                                                    # baitChr, baitName, oeChr, oeName
+
+
+def _peak_text_columns(path, body, sep, line_off, fields=PEAK_TEXT_FIELDS):
+    """The text columns ``fields`` (positions among the 11 key columns) of the rows whose lines start at ``body + line_off`` in the
+    file, cut as strings and never interpreted: {column name: object array}."""
+    import mmap
+    out = {PEAK_KEY_COLUMNS[k]: np.empty(len(line_off), dtype=object) for k in fields}
+    if len(line_off) == 0:
+        return out
+    sepb = bytes([sep])
+    with open(path, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as m:
+        for i, off in enumerate(np.asarray(line_off, dtype=np.int64) + body):
+            e = m.find(b"\n", off)
+            parts = m[off:len(m) if e < 0 else e].split(sepb, max(fields) + 1)
+            for k in fields:
+                out[PEAK_KEY_COLUMNS[k]][i] = parts[k].decode()
+    return out
+
+
+class DevicePeakFile(str):
+    """The path of a peak matrix, marked for the device reader: ``getCandidateInteractions(output, DevicePeakFile(path), ...)`` reads it
+    with HipContext.read_peaks.  (The mirror keeps the reference's argument list plus ``ctx``, so the opt-in travels with the path.)
+    The mark is the type: ``str(path)``, ``os.path.join`` or any other string operation gives a plain ``str`` back and with it the
+    host reader — wrap the final path, at the call."""
+
+
+class PeakMatrix(dict):
+    """readAndFilterPeakMatrix(device=True): the kept rows of the peak matrix as device tensors — ``baitStart, baitEnd, baitID,
+    oeStart, oeEnd, oeID`` (int32), ``dist`` and every score column by its name (float64) — in file order, plus ``line_off`` (int64:
+    where each kept row's line starts in the file's body).  ``to_frame()`` builds the host table of 11 + T columns: the numeric
+    columns from the device, the four text columns cut as strings from the file at the kept rows' lines.  Known differences from
+    the host reader's frame: the text columns are always strings (pandas makes ``baitChr = 19`` an int64); a score column that
+    holds only integer tokens is float64; and ``dist`` and the scores are ``float(token)``, which the pandas reader's are not for
+    tokens of 16 or 17 significant digits (a few units in the last place; tests/test_peaks.py has the measurement) — a row whose score
+    lies that close to the threshold can be kept by one path and not by the other.  Otherwise the values are equal.  ``frame``: set when the host reader served the call (fallback)."""
+
+    path = body = sep = frame = None
+    score_names = ()
+
+    def to_frame(self):
+        import pandas as pd
+        if self.frame is not None:
+            return self.frame
+        host = {k: v.cpu().numpy() for k, v in self.items()}
+        text = _peak_text_columns(self.path, self.body, self.sep, host["line_off"])
+        cols = {k: (text[k] if k in text else host[k]) for k in PEAK_KEY_COLUMNS}
+        cols.update({k: host[k] for k in self.score_names})
+        return pd.DataFrame(cols)
+
+
+def _peak_matrix_from_frame(x, ctx, score_names):
+    torch = ctx.torch
+    pm = PeakMatrix()
+    for k in ("baitStart", "baitEnd", "baitID", "oeStart", "oeEnd", "oeID"):
+        pm[k] = torch.from_numpy(np.ascontiguousarray(x[k].to_numpy(), dtype=np.int32)).to(ctx.device)
+    for k in ["dist"] + list(score_names):
+        pm[k] = torch.from_numpy(np.ascontiguousarray(x[k].to_numpy(np.float64))).to(ctx.device)
+    pm.frame, pm.score_names = x, list(score_names)
+    return pm
+
+
+def _read_peaks_dev(ctx, peakFiles, targetColumns):
+    """One peak file through HipContext.read_peaks -> (Peaks, None), or (None, why the device path does not serve this call)."""
+    from . import hip
+    files = [peakFiles] if isinstance(peakFiles, str) else list(peakFiles)
+    if len(files) != 1:
+        return None, "more than one peak file (.multimerge stays host code)"
+    try:
+        pk = ctx.read_peaks(files[0], targetColumns)
+    except hip.ChicdiffHipError as e:
+        if "All specified targetColumns must be present in the peak file(s)" in str(e):
+            raise ValueError("All specified targetColumns must be present in the peak file(s)") from e
+        raise
+    if pk.status & hip.PEAKS_ST_QUOTE:
+        return None, "the file holds a quoted field"
+    if pk.status:
+        return None, "more decimal tokens than the slow-token list holds need the host's strtod"
+    return pk, None
+
+
+def readAndFilterPeakMatrix(peakFiles, targetColumns, chicagoData, conditions, score, outprefix="", ctx=None, device=False):
+    """``device=True`` (needs ``ctx``): the file is parsed and filtered on the device (HipContext.read_peaks / filter_peaks; the rule
+    stands above chicdiff_hip_peaks_parse_dev in include/chicdiff_hip.h) and a ``PeakMatrix`` comes back; ``_filteredBaits.txt`` is
+    written as below.  More than one peak file, a quoted field, or too many tokens for the slow-token list: one message, and the host
+    reader below serves the call (the PeakMatrix then carries its frame)."""
+    if device:
+        if ctx is None:
+            raise ValueError("readAndFilterPeakMatrix(device=True) needs an open HipContext as ctx")
+        pk, why = _read_peaks_dev(ctx, peakFiles, targetColumns)
+        if pk is None:
+            message("readAndFilterPeakMatrix: ", why, ": reading the peak matrix on the host")
+            x = readAndFilterPeakMatrix(peakFiles, targetColumns, chicagoData, conditions, score, outprefix)
+            return _peak_matrix_from_frame(x, ctx, [c for c in x.columns[11:]])
+        cond = [next((k for k, c in enumerate(conditions) if name in chicagoData[c]), -1) for name in pk.score_names]
+        r = ctx.filter_peaks(pk, score, cond, len(targetColumns) > len(conditions))
+        with open(f"{outprefix}_filteredBaits.txt", "w") as f:
+            f.write("".join(f"{b}\n" for b in r["filtered_baits"].cpu().numpy()))
+        kept = r["kept_idx"]
+        pm = PeakMatrix()
+        ints = pk.ints[:, kept]
+        for k, name in enumerate(("baitStart", "baitEnd", "baitID", "oeStart", "oeEnd", "oeID")):
+            pm[name] = ints[k]
+        pm["baitID"], pm["oeID"] = r["baitID"], r["oeID"]                            # (the filter's own gather: the same values)
+        pm["dist"] = pk.dist[kept]
+        sc = pk.scores[:, kept]
+        for j, name in enumerate(pk.score_names):
+            pm[name] = sc[j]
+        pm["line_off"] = pk.line_off[kept]
+        pm.path, pm.body, pm.sep, pm.score_names = pk.path, pk.info["body"], pk.info["sep"], list(pk.score_names)
+        return pm
     import pandas as pd
 
     read = lambda f: pd.read_csv(f, sep=None, engine="python")
@@ -93,17 +203,21 @@ class RegionUniverse(dict):
 def _expand(ctx, baitID, oeID, RUexpand, rmap):
     ru = RegionUniverse(post.getRegionUniverse(ctx, baitID, oeID, RUexpand, rmap["OEchr"].astype(str).to_numpy(),
                                                rmap["otherEndID"].to_numpy()))
-    ru["peak_baitID"] = np.asarray(baitID, dtype=np.int32)
+    ru["peak_baitID"] = baitID.cpu().numpy() if hasattr(baitID, "cpu") else np.asarray(baitID, dtype=np.int32)
     return ru
 
 
-def getRegionUniverse(chicdiff_settings, ctx, suffix=""):
+def getRegionUniverse(chicdiff_settings, ctx, suffix="", device_peaks=False):
     """chicdiff.R:369-426 (window mode): peaks -> regions; the expansion, the clip to the map and the cis filter run on
-    the device (chicdiff_hip_region_universe_*)."""
+    the device (chicdiff_hip_region_universe_*).  ``device_peaks=True``: the peak matrix is read and filtered on the device too
+    (readAndFilterPeakMatrix(device=True)) and its baitID / oeID reach the expansion as device tensors — the same RU."""
     s = asChicdiffSettings(chicdiff_settings)
     x = readAndFilterPeakMatrix(s["peakfiles"], s["targetColumns"], s["chicagoData"], list(s["chicagoData"]), s["score"],
-                                s["outprefix"])
-    ru = _expand(ctx, x["baitID"].to_numpy(np.int32), x["oeID"].to_numpy(np.int32), s["RUexpand"], _read_rmap(s["rmapfile"]))
+                                s["outprefix"], ctx=ctx, device=device_peaks)
+    if device_peaks:
+        ru = _expand(ctx, x["baitID"], x["oeID"], s["RUexpand"], _read_rmap(s["rmapfile"]))
+    else:
+        ru = _expand(ctx, x["baitID"].to_numpy(np.int32), x["oeID"].to_numpy(np.int32), s["RUexpand"], _read_rmap(s["rmapfile"]))
     if s["saveAuxData"]:
         ru.to_frame().to_csv(f"{s['outprefix']}_RegionUniverse{suffix}.csv", index=False)
     return ru
@@ -537,10 +651,11 @@ def IHWcorrection(chicdiff_settings, DESeqOut, FullRegionData, DESeqOutControl, 
     return out
 
 
-def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, rng=None, assemble=False, control_seed=None):
+def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, rng=None, assemble=False, control_seed=None,
+                     device_peaks=False):
     """chicdiff.R:301-347, same stage order and messages.  ``assemble``: passed to getFullRegionData.  ``control_seed``: the control
     regions are drawn on the device from this seed (getControlRegionUniverse(seed=...)) instead of on the host from ``rng``, which
-    then serves IHWcorrection's columns alone."""
+    then serves IHWcorrection's columns alone.  ``device_peaks``: passed to getRegionUniverse."""
     from . import hip
     from .settings import hipDevice
     own = ctx is None
@@ -549,7 +664,7 @@ def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, r
     try:
         s = asChicdiffSettings(chicdiff_settings)
         message("\n*** Running getRegionUniverse\n")
-        RU = getRegionUniverse(chicdiff_settings, ctx)
+        RU = getRegionUniverse(chicdiff_settings, ctx, device_peaks=device_peaks)
         message("\n*** Running getControlRegionUniverse\n")
         RUcontrol = getControlRegionUniverse(chicdiff_settings, RU, ctx, rng=rng if control_seed is None else None, seed=control_seed)
         message("\n*** Running getFullRegionData\n")
@@ -606,11 +721,21 @@ def getCandidateInteractions(output, peakFiles, chicdiff_settings, pcol="weighte
     merged = not isinstance(raw[conds[0]], dict)                                   # :2118 is.null(names(chicagoData[[1]]))
     s = asChicdiffSettings(chicdiff_settings)
     score, target = s["score"], list(s["targetColumns"])
-    x = pd.read_csv(peakFiles, sep=None, engine="python")                          # fread(peakFiles)
-    x = x[list(x.columns[:11]) + [c for c in x.columns[11:] if c in target]]      # :2080-2081
     names = cnames[0] + cnames[1]
-    if sorted(names) != sorted(c for c in x.columns[11:]) or (merged and len(names) != 2):
-        raise ValueError(f"getCandidateInteractions: the score columns {names} named by chicagoData must be the targetColumns of the peak file")
+    device_peaks = isinstance(peakFiles, DevicePeakFile)
+
+    def read_host():
+        x = pd.read_csv(peakFiles, sep=None, engine="python")                      # fread(peakFiles)
+        return x[list(x.columns[:11]) + [c for c in x.columns[11:] if c in target]]   # :2080-2081
+
+    def check_names(file_names):
+        if sorted(names) != sorted(file_names) or (merged and len(names) != 2):
+            raise ValueError(f"getCandidateInteractions: the score columns {names} named by chicagoData must be the targetColumns of the peak file")
+
+    x = pk = None
+    if not device_peaks:
+        x = read_host()
+        check_names(x.columns[11:])
     if isinstance(output, str):
         output = pd.read_csv(output)
     from . import hip
@@ -621,18 +746,37 @@ def getCandidateInteractions(output, peakFiles, chicdiff_settings, pcol="weighte
     try:
         torch = ctx.torch
         dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(ctx.device)
-        scores = np.ascontiguousarray(x[names].to_numpy(np.float64).T)
+        if device_peaks:
+            pk, why = _read_peaks_dev(ctx, peakFiles, target)
+            if pk is None:
+                message("getCandidateInteractions: ", why, ": reading the peak matrix on the host")
+                x = read_host()
+            file_names = list(pk.score_names) if pk is not None else list(x.columns[11:])
+            check_names(file_names)
+        if pk is not None:
+            d_pb, d_po = pk.baitID, pk.oeID
+            d_scores = pk.scores[dev([file_names.index(c) for c in names], np.int64)].contiguous()   # condition order
+        else:
+            d_pb, d_po = dev(x["baitID"], np.int32), dev(x["oeID"], np.int32)
+            d_scores = dev(np.ascontiguousarray(x[names].to_numpy(np.float64).T), np.float64)
         r = ctx.candidate_interactions(dev(output["baitID"], np.int32), dev(output["minOE"], np.int32), dev(output["maxOE"], np.int32),
-                                       dev(output[pcol], np.float64), dev(x["baitID"], np.int32), dev(x["oeID"], np.int32),
-                                       dev(scores, np.float64), len(cnames[0]), len(cnames[1]), merged, score, pvcut, minDeltaAsinhScore,
-                                       method=method)
+                                       dev(output[pcol], np.float64), d_pb, d_po, d_scores, len(cnames[0]), len(cnames[1]), merged, score,
+                                       pvcut, minDeltaAsinhScore, method=method)
         gp, ptr, rows = r["group_peak"].cpu().numpy(), r["group_ptr"].cpu().numpy(), r["pair_row"].cpu().numpy()
         min_p, delta = r["group_min_p"].cpu().numpy(), r["group_delta"].cpu().numpy()
+        if pk is not None:                                                         # the surviving groups' peaks only
+            d_gp = r["group_peak"].to(torch.int64)
+            px = {"baitID": d_pb[d_gp].cpu().numpy().astype(np.int64), "oeID": d_po[d_gp].cpu().numpy().astype(np.int64)}
+            px.update(_peak_text_columns(pk.path, pk.info["body"], pk.info["sep"], pk.line_off[d_gp].cpu().numpy(), fields=(0, 4)))
+            sc = d_scores[:, d_gp].cpu().numpy()
+            px.update({c: sc[k] for k, c in enumerate(names)})
+            px = pd.DataFrame(px)
+        else:
+            px = x.iloc[gp]
     finally:
         if own:
             ctx.close()
     first = rows[ptr[:-1]] if len(gp) else np.zeros(0, dtype=np.int64)           # baitstart[1], baitend[1]: the group's first region
-    px = x.iloc[gp]
     final = {"baitID": px["baitID"].to_numpy(), "oeID": px["oeID"].to_numpy(), "baitChr": px["baitChr"].to_numpy(),
              "baitstart": output["baitstart"].to_numpy()[first], "baitend": output["baitend"].to_numpy()[first],
              "baitName": px["baitName"].to_numpy()}

@@ -373,6 +373,92 @@ int chicdiff_hip_chinput_parse_dev(chicdiff_hip_ctx *ctx, const uint8_t *d_text,
 int chicdiff_hip_chinput_read_dev(chicdiff_hip_ctx *ctx, const char *path, int64_t *nrows_host);
 int chicdiff_hip_chinput_caps(int32_t *tile_bytes, int32_t *lane_bytes, int32_t *window_bytes);
 
+/* limits and words of the device path of readAndFilterPeakMatrix (below) */
+#define CHICDIFF_PEAKS_KEY_COLUMNS 11    /* baitChr baitStart baitEnd baitID baitName oeChr oeStart oeEnd oeID oeName dist, by position */
+#define CHICDIFF_PEAKS_MAX_SCORES 64     /* score columns one read takes */
+#define CHICDIFF_PEAKS_MAX_SLOW 65536    /* decimal tokens per read that the device may leave to the host's strtod */
+#define CHICDIFF_PEAKS_ST_QUOTE 1        /* status bit: the body holds a '"' — nothing was parsed */
+#define CHICDIFF_PEAKS_ST_SLOW_OVERFLOW 2 /* status bit: more slow tokens than the list holds — the columns are not complete */
+/* info[CHICDIFF_PEAKS_INFO_WORDS] of the calls below (int64 each) */
+#define CHICDIFF_PEAKS_INFO_NROWS 0      /* rows of the body */
+#define CHICDIFF_PEAKS_INFO_STATUS 1     /* CHICDIFF_PEAKS_ST_* bits; non-zero: the caller reads the file some other way */
+#define CHICDIFF_PEAKS_INFO_MAXBAIT 2    /* largest baitID, -1 without rows */
+#define CHICDIFF_PEAKS_INFO_NSLOW 3      /* decimal tokens settled by the host */
+#define CHICDIFF_PEAKS_INFO_BAD 4        /* body offset of the first malformed line, -1 = none */
+#define CHICDIFF_PEAKS_INFO_BODY 5       /* file offset of the body (_read_dev, _selftest_peaks; 0 for _parse_dev) */
+#define CHICDIFF_PEAKS_INFO_SEP 6        /* the separator byte */
+#define CHICDIFF_PEAKS_INFO_NSCORE 7     /* score columns */
+#define CHICDIFF_PEAKS_INFO_NKEPT 8      /* _selftest_peaks: rows the filter keeps */
+#define CHICDIFF_PEAKS_INFO_NFILTERED 9  /* _selftest_peaks: baits without a kept row */
+#define CHICDIFF_PEAKS_INFO_WORDS 10
+/* readAndFilterPeakMatrix (chicdiff.R:218-277) on the device, opt-in: x <- fread(peakFiles); x[, c(1:11, sel)] (:231-244); the four
+ * filters (:246-270); filtered baits (:240, :271).  One peak file; .multimerge (:223-229) stays host code.  The rule, in full:
+ *
+ *   header     read on the HOST.  Leading '#' lines are skipped; the next line is the header, one trailing '\r' dropped.  The separator
+ *              is ONE byte for the whole file: a tab if the header line holds a tab, else a comma if it holds a comma, else a blank.
+ *              Header fields are split at every separator byte; a name may be quoted.  Fields 0 .. 10 must be exactly baitChr,
+ *              baitStart, baitEnd, baitID, baitName, oeChr, oeStart, oeEnd, oeID, oeName, dist in that order (the reference takes them
+ *              by position and uses them by name).  The score columns are the fields from 11 on whose names are targetColumns, in
+ *              FILE order.  Refused with a message (CHICDIFF_E_INVALID): a target that no field from 11 on names ("All specified
+ *              targetColumns must be present in the peak file(s)", the reference's words, :232); a target named twice (in the list or
+ *              in the header); a target that is one of the 11 key names; more than CHICDIFF_PEAKS_MAX_SCORES targets.
+ *   body       the bytes after the header line's '\n'.
+ *   lines      as for chinput, unchanged: a line starts at the body's first byte or after a '\n' and runs to the next '\n' or the
+ *              body's end; ONE trailing '\r' is dropped; a line that is empty after that is skipped.
+ *   fields     split at every single separator byte; two in a row make an empty field, and a separator as the line's last byte is
+ *              followed by an empty field.  A body that holds a '"' ANYWHERE is not parsed: CHICDIFF_PEAKS_ST_QUOTE, no row written.
+ *   integers   fields 1, 2, 3, 6, 7, 8 (baitStart, baitEnd, baitID, oeStart, oeEnd, oeID): chinput's rule — an optional single '+' or
+ *              '-', at least one digit, digits only, magnitude <= 2147483647.  NA is malformed.  baitID and oeID are >= 0.
+ *   decimals   field 10 (dist) and every score column.  Empty, or exactly NA: NaN.  Otherwise the token is
+ *                  [+-]? (d+ (. d*)? | . d+) ([eE] [+-]? d+)?
+ *              and the value is the double nearest to the decimal number it writes, ties to even — what strtod and Python's float()
+ *              return, bit for bit, signed zero included.  Anything else is malformed.
+ *   text       fields 0, 4, 5, 9 and every field that is no score column are skipped byte-wise, never interpreted.
+ *   malformed  nothing behind the last needed field (the last score column; dist without score columns) is looked at.  A line with
+ *              fewer fields than that is malformed.  Any malformed line fails the call with `malformed peak matrix row at byte offset
+ *              K (...)`, K the SMALLEST malformed line start (a 64-bit atomicMin).
+ *   filter     a row is kept when (1) some score column is > score (NaN never is); (2) if replicate_rule != 0 (more target columns than
+ *              conditions, :253), every condition c in 0 .. ncond-1 has >= 2 non-NaN values among the score columns j with
+ *              cond_of_col[j] == c; (3) dist is not NaN; (4) oeID != baitID + 1 and oeID != baitID - 1, compared in 64 bits.
+ *   output     the kept rows' indices in FILE order with their baitID / oeID gathered, and the filtered baits: the baitIDs that occur
+ *              in the file and have no kept row, in order of FIRST APPEARANCE in the file (all_baits <- unique(x$baitID), then %in%).
+ *
+ * Decimal -> double on the device (peaks_decimal.h): the token is (w, q), w its digits up to the last non-zero one without leading
+ * zeros, value = w * 10^q.  For w of at most 19 digits and |q| <= 39 the rounding is decided exactly from integers of at most 192
+ * bits.  Any other non-zero token is a SLOW token: its cell and offset go on a list of CHICDIFF_PEAKS_MAX_SLOW entries (one counter;
+ * every cell is patched on its own, so the slot order cannot show), the host settles it with strtod and a kernel writes the cells
+ * before the call returns; more than the list holds: CHICDIFF_PEAKS_ST_SLOW_OVERFLOW.  A token with at most 17 significant digits
+ * and |q| <= 22 — what shortest-round-trip writers produce for Chicago scores — is never slow.
+ * Row r's place comes from the two scans alone, as for chinput; the kept rows' and filtered baits' places from one scan of packed
+ * flags.  No value passes through an atomic.
+ *
+ * _parse_dev: the device stage alone, for tests.  d_text: the body, 16-byte aligned; sep the separator byte; score_cols[nscore] (host):
+ * the score columns' 0-based fields, ascending, >= 11.  d_ints (6, cap) int32: baitStart, baitEnd, baitID, oeStart, oeEnd, oeID;
+ * d_dist (cap); d_scores (nscore, cap); d_line_off (cap): the body offset of every row's line.  info (host): the words above.  More
+ * rows than cap: CHICDIFF_E_INVALID before anything is written, info[NROWS] set.  A status bit: CHICDIFF_OK, nothing usable written.
+ * Host stops: the row count (with the quote verdict); the verdict (malformed offset, max baitID, slow count).
+ * _read_dev: header on the host (targets[ntargets]: the targetColumns), the body through the bounded pinned area of
+ * chicdiff_hip_chinput_read_dev to the device, then the stage above into grow-only buffers of the context, apart from every
+ * workspace.  score_target[j] (host, room for ntargets): which target score row j is.  Offsets in messages count from the start of
+ * the FILE.  _columns_dev copies the context's columns of the last successful _read_dev into the caller's (shapes as for _parse_dev).
+ * _filter_dev: d_bait, d_oe, d_dist (n), d_scores (nscore, n); cond_of_col[nscore] (host), maxbait = info[MAXBAIT] (any bound on
+ * baitID will do; the bait table has maxbait + 1 words of 8 bytes in the context's grow-only workspace and is cleared by a memset, so ONE
+ * stray large ID costs device memory in proportion: 16 GiB at the largest legal ID, 2^31 - 1; CHICDIFF_E_NOMEM when that fails).  d_kept_idx (int64), d_kept_bait, d_kept_oe, d_filtered (int32): room for n
+ * each; *nkept_host / *nfiltered_host entries are written.  One host stop.
+ * _caps: the tile and window (the chinput constants) and the two limits above, as the library was built; host only. */
+int chicdiff_hip_peaks_parse_dev(chicdiff_hip_ctx *ctx, const uint8_t *d_text, int64_t nbytes, int32_t sep, const int32_t *score_cols,
+                                 int32_t nscore, int32_t *d_ints, double *d_dist, double *d_scores, int64_t *d_line_off, int64_t cap,
+                                 int64_t *info);
+int chicdiff_hip_peaks_read_dev(chicdiff_hip_ctx *ctx, const char *path, const char *const *targets, int32_t ntargets,
+                                int32_t *score_target, int64_t *info);
+int chicdiff_hip_peaks_columns_dev(chicdiff_hip_ctx *ctx, int32_t *d_ints, double *d_dist, double *d_scores, int64_t *d_line_off,
+                                   int64_t cap);
+int chicdiff_hip_peaks_filter_dev(chicdiff_hip_ctx *ctx, const int32_t *d_bait, const int32_t *d_oe, const double *d_dist,
+                                  const double *d_scores, int64_t n, int32_t nscore, double score, const int32_t *cond_of_col,
+                                  int32_t ncond, int32_t replicate_rule, int64_t maxbait, int64_t *d_kept_idx, int32_t *d_kept_bait,
+                                  int32_t *d_kept_oe, int32_t *d_filtered, int64_t *nkept_host, int64_t *nfiltered_host);
+int chicdiff_hip_peaks_caps(int32_t *tile_bytes, int32_t *window_bytes, int32_t *max_scores, int32_t *max_slow);
+
 /* f1/f3 — p.adjust(p, method = "BH") (DESeq2 results() on the independent-filtering survivors; chicdiff.R:2049
  * on the weighted p-values).  NaN = NA: not counted, stays NaN.  n < 2^32. */
 int chicdiff_hip_bh_adjust_dev(chicdiff_hip_ctx *ctx, const double *d_p, int64_t n, double *d_padj);
@@ -701,6 +787,15 @@ int chicdiff_hip_selftest_objective_dev(chicdiff_hip_ctx *ctx, const int32_t *d_
  * the file; on a parse error the message goes to err[errcap]. */
 int chicdiff_hip_selftest_chinput(const char *path, int32_t nthreads, int64_t cap, int32_t *bait, int32_t *oe, int32_t *N,
                                   int64_t *nrows, char *err, int32_t errcap);
+/* _peaks (host only, no context): a single-threaded host statement of the peak-matrix rule above — the same header function, strtod
+ * for the decimals, the same filter — so that the rule can be checked where there is no GPU.  A test entry, not a product path.
+ * targets / cond_of_target[ntargets]: the targetColumns and the condition of each; ints (6, cap), dist (cap), scores (nscore, cap),
+ * line_off (cap), kept_idx (cap), filtered (cap), score_target (ntargets): any may be NULL; info: the words above.  A header or
+ * malformed-row error: CHICDIFF_E_INVALID, the message in err[errcap]. */
+int chicdiff_hip_selftest_peaks(const char *path, const char *const *targets, int32_t ntargets, double score, const int32_t *cond_of_target,
+                                int32_t ncond, int32_t replicate_rule, int64_t cap, int32_t *ints, double *dist, double *scores,
+                                int64_t *line_off, int64_t *kept_idx, int32_t *filtered, int32_t *score_target, int64_t *info, char *err,
+                                int32_t errcap);
 int chicdiff_hip_selftest_r_random(int32_t kind, uint32_t seed, double a, double b, int64_t n, double *out);
 int chicdiff_hip_selftest_prior_mc(int32_t df, const double *hist40, double *dens_out, double *prior_var_out);
 /* _sched_class (host only): the class the gene-wise line search's schedule ("line_search_schedule" = mode, 1 .. 4) puts a row in,
