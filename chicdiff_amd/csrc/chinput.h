@@ -1,4 +1,4 @@
-// chinput.h — the host side of reading a text table (chinput.hip), as api.hip and peaks.hip use it.
+// chinput.h — the host side of reading a text table (chinput.hip), as text_api.hip and peaks.hip use it.
 #pragma once
 #include <stdint.h>
 

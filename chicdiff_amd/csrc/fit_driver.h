@@ -1,5 +1,5 @@
 // fit_driver.h — launch order of the fit's global steps, written once against a small backend
-// interface.  The HIP backend (api.hip) enqueues kernels on a stream and all-reduces device
+// interface.  The HIP backend (fit_api.hip) enqueues kernels on a stream and all-reduces device
 // buffers through the caller's callback; the CPU test backend (tests/harness/shard_harness.cpp)
 // runs plain loops over a row shard and all-reduces host buffers over gloo.  Same driver, same
 // state machines (fit_state.h), so the sharded control flow is exercised without a GPU.

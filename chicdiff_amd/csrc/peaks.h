@@ -1,5 +1,5 @@
 // peaks.h — the peak-matrix reader: what peaks_kernels.hip (device), peaks.hip (host: header, the host statement of the rule, the
-// slow-token patch) and api.hip (entry points) share.  The rule: include/chicdiff_hip.h, above chicdiff_hip_peaks_parse_dev.
+// slow-token patch) and text_api.hip (entry points) share.  The rule: include/chicdiff_hip.h, above chicdiff_hip_peaks_parse_dev.
 #pragma once
 #include <stdint.h>
 

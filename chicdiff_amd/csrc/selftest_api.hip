@@ -1,0 +1,119 @@
+// selftest_api.hip — exports of the parity and self tests: device math, the dispersion objective, host statements of device rules.
+#include "ctx.h"
+
+// small extra export used by the parity tests: p = 2*pnorm(-|stat|) on device (Cody, as R)
+extern "C" int chicdiff_hip_wald_pvalues_dev(chicdiff_hip_ctx *c, const double *d_stat, int64_t n, double *d_p) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (!d_stat || !d_p || n < 0) return fail(c, CHICDIFF_E_INVALID, "wald_pvalues: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n > 0) launch_pvalues(d_stat, n, d_p, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CHICDIFF_OK;
+}
+
+// device-math self test: op 0 flog, 1 tlog (table), 2 rcp, 3 lgamma, 4 digamma, 5 2*pnorm(-|x|), 6 / 7 raw v_rcp_f64 (+ one Newton step), 8 texp (table), 9 qnorm (AS 241)
+extern "C" int chicdiff_hip_selftest_math_dev(chicdiff_hip_ctx *c, int32_t op, const double *d_x, int64_t n, double *d_out) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (!d_x || !d_out || n < 0 || op < 0 || op > 9) return fail(c, CHICDIFF_E_INVALID, "selftest_math: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n > 0) launch_math_selftest(op, d_x, n, d_out, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CHICDIFF_OK;
+}
+
+// landau_tail (devmath.h) as the "hmp" overlap kernel calls it
+extern "C" int chicdiff_hip_selftest_landau_dev(chicdiff_hip_ctx *c, const double *d_z, int64_t n, double *d_out) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (!d_z || !d_out || n < 0) return fail(c, CHICDIFF_E_INVALID, "selftest_landau: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n > 0) launch_landau_selftest(d_z, n, d_out, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CHICDIFF_OK;
+}
+
+// building blocks with a second argument / a second result (header: the op numbers)
+extern "C" int chicdiff_hip_selftest_math3_dev(chicdiff_hip_ctx *c, int32_t op, const double *d_x, const double *d_y, int64_t n, double *d_out,
+                                               double *d_out2) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (!d_x || !d_y || !d_out || !d_out2 || n < 0 || op < 10 || op > 18) return fail(c, CHICDIFF_E_INVALID, "selftest_math3: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n > 0) launch_math3_selftest(op, d_x, d_y, n, c->d_logfact, d_out, d_out2, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CHICDIFF_OK;
+}
+
+// the dispersion objective at chosen points: the fit's own prep, then objective_probe_kernel (disp_kernels.hip)
+extern "C" int chicdiff_hip_selftest_objective_dev(chicdiff_hip_ctx *c, const int32_t *d_counts, const double *d_nf, int64_t n, int32_t S,
+                                                   const int32_t *group, const chicdiff_nbglm_opts *opts, const double *d_log_alpha, int32_t K,
+                                                   const double *d_prior_mean, double prior_var, int32_t live_rows, double *d_lp,
+                                                   double *d_dlp, double *d_alpha, double *d_mu, int32_t *lanes_per_row) {
+    if (!c) return CHICDIFF_E_INVALID;
+    FitDims d;
+    if (!d_counts || !d_nf || !d_log_alpha || !d_lp || !d_dlp || !d_alpha || !d_mu || K < 1 || live_rows < 0 || live_rows > 64 ||
+        (d_prior_mean && !(prior_var > 0)))
+        return fail(c, CHICDIFF_E_INVALID, "selftest_objective: bad arguments");
+    if (int rc = check_counts_group(c, n, S, group, d)) return rc;
+    if (int rc = check_opts(c, opts)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_workspace(c, n, S)) return rc;
+    const Opts o = make_opts(c, opts, S);
+    HIPCHK(c, hipMemsetAsync(c->w.sc, 0, align256(sizeof(FitScalars)) + kQueueBytes + 1024, c->stream));
+    launch_prep(d_counts, const_cast<double *>(d_nf), d, c->w, o, c->stream);  // (not fused: nf is read, never written)
+    ObjectiveProbe pb{d_log_alpha, K, d_prior_mean, d_prior_mean ? 1.0 / prior_var : 0.0, live_rows, d_lp, d_dlp, d_alpha, d_mu};
+    const int lanes = launch_objective_probe(d, c->w, o, pb, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (lanes < 0) return fail(c, CHICDIFF_E_INVALID, "selftest_objective: the line search has no samples-across-lanes layout for %d live rows at S = %d", live_rows, S);
+    HIPCHK(c, hipGetLastError());
+    if (lanes_per_row) *lanes_per_row = lanes;
+    return CHICDIFF_OK;
+}
+
+// host-side self tests of the simulation-matched prior variance (no device involved)
+extern "C" int chicdiff_hip_selftest_r_random(int32_t kind, uint32_t seed, double a, double b, int64_t n, double *out) {
+    if (!out || n < 0 || kind < 0 || kind > 3) return CHICDIFF_E_INVALID;
+    if (kind == 3 && !(a > 0 && b > 0)) return CHICDIFF_E_INVALID;
+    RStream r(seed);
+    for (int64_t i = 0; i < n; i++) out[i] = kind == 0 ? r.unif() : kind == 1 ? r.norm() : kind == 2 ? r.expo() : r.gamma(a, b);
+    return CHICDIFF_OK;
+}
+// the gene-wise schedule's class function (common.h), evaluated on the host: class index of each score, and in `bounds` (7 values) the
+// first class index that is not dealt out statically for 0 .. 6 of the half-decade classes
+extern "C" int chicdiff_hip_selftest_sched_class(int32_t mode, double min_disp, const double *alpha_init, const double *group_mean, int64_t n,
+                                                 int32_t *cls_out, int32_t *bounds) {
+    if (n < 0 || (n > 0 && (!alpha_init || !group_mean || !cls_out)) || mode < 1 || mode > 4) return CHICDIFF_E_INVALID;
+    for (int64_t i = 0; i < n; i++) cls_out[i] = cd::sched_class(alpha_init[i], group_mean[i], min_disp, mode);
+    if (bounds) for (int a = 0; a <= 6; a++) bounds[a] = cd::sched_classes_a(a, mode);
+    return CHICDIFF_OK;
+}
+// the value bins of the direct size-factor select (common.h: sf_bin, sf_sub_bin), evaluated on the host: bins per column for S samples
+// (*nbins_out), the bin of each x, and — sub_out given — its sub-bin inside bin `sub_of`
+extern "C" int chicdiff_hip_selftest_sf_bin(int32_t S, const double *x, int64_t n, int32_t *nbins_out, int32_t *bin_out, int32_t sub_of,
+                                            int32_t *sub_out) {
+    if (S < 1 || S > cd::kSfMaxS || n < 0 || (n > 0 && (!x || !bin_out))) return CHICDIFF_E_INVALID;
+    const int nb = cd::sf_bins(S);
+    if (nbins_out) *nbins_out = nb;
+    for (int64_t i = 0; i < n; i++) {
+        bin_out[i] = cd::sf_bin(x[i], nb);
+        if (sub_out) sub_out[i] = cd::sf_sub_bin(x[i], nb, sub_of);
+    }
+    return CHICDIFF_OK;
+}
+// the claim rule of the gene-wise line search's two-ended queue (common.h: queue_claim, filler_claims, filler_stop_f), evaluated on the host
+extern "C" int chicdiff_hip_selftest_queue_claim(uint64_t old, int32_t back, uint32_t chunks, uint32_t first_back, int32_t stop_percent, int32_t claimed,
+                                                 uint32_t *chunk_out, int32_t *again_out) {
+    uint32_t chunk = 0;
+    const bool valid = cd::queue_claim(old, back != 0, chunks, chunk);
+    if (chunk_out) *chunk_out = chunk;
+    if (again_out) *again_out = cd::filler_claims(claimed != 0, old, chunks, first_back, cd::filler_stop_f(stop_percent, chunks, first_back));
+    return valid ? 1 : 0;
+}
+extern "C" int chicdiff_hip_selftest_prior_mc(int32_t df, const double *hist40, double *dens_out, double *prior_var_out) {
+    if (df < 1 || df > 3) return CHICDIFF_E_INVALID;
+    const PmcTable &t = pmc_table(df);
+    if (dens_out) memcpy(dens_out, t.dens, sizeof t.dens);
+    if (prior_var_out) {
+        if (!hist40) return CHICDIFF_E_INVALID;
+        *prior_var_out = pmc_prior_var(hist40, t);
+    }
+    return CHICDIFF_OK;
+}

@@ -79,7 +79,7 @@ int chicdiff_hip_set_allgather(chicdiff_hip_ctx *ctx, chicdiff_allgather_fn fn, 
 int32_t chicdiff_hip_last_refits(const chicdiff_hip_ctx *ctx);
 
 /* Tuning / test options; results never depend on them, the defaults are what bench.py measures.  (Every option the library
- * accepts, in the order of its table — kOptions in chicdiff_amd/csrc/api.hip; any other name or value is CHICDIFF_E_INVALID.)
+ * accepts, in the order of its table — kOptions in chicdiff_amd/csrc/ctx.hip; any other name or value is CHICDIFF_E_INVALID.)
  *   "line_search_spread"        1 (default) | 0 | 2 | 3: evaluate straggler rows (line searches and IRLS) with their samples spread across
  *                               lanes; 0 = row per lane only; 2 = as 1 without the lean tick of the launch's end, 3 = as 1 without the layouts of
  *                               more than 128 exchange entries (bit-identity tests)

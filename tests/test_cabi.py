@@ -28,11 +28,11 @@ def test_exports_match_header(lib):
 
 def test_header_lists_the_options_of_the_librarys_table():
     """The comment block above chicdiff_hip_set_option in include/chicdiff_hip.h is the only documentation a host has: it names
-    every option of the library's table (kOptions, chicdiff_amd/csrc/api.hip), and no other, in the table's order."""
+    every option of the library's table (kOptions, chicdiff_amd/csrc/ctx.hip), and no other, in the table's order."""
     hdr = open(os.path.join(ROOT, "include", "chicdiff_hip.h")).read()
     block = hdr[hdr.index("/* Tuning / test options"):hdr.index("int chicdiff_hip_set_option(")]
     documented = re.findall(r'^ \*   "([a-z_]+)"', block, re.M)
-    api = open(os.path.join(ROOT, "chicdiff_amd", "csrc", "api.hip")).read()
+    api = open(os.path.join(ROOT, "chicdiff_amd", "csrc", "ctx.hip")).read()
     table = api[api.index("static const OptionDef kOptions[] = {"):]
     table = table[:table.index("\n};")]
     stored = re.findall(r'^    \{"([a-z_]+)",', table, re.M)

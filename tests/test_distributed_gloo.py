@@ -198,7 +198,7 @@ def _gather_worker(rank, world, port, q):
 
 def test_allgather_hook_lays_the_ranks_blocks_out_in_rank_order():
     """chicdiff_allgather_fn as chicdiff_amd.dist implements it (host memory, gloo, world_size 2): rank r's block lands at
-    r * count on every rank — the layout api.hip's gathered_trend / trend_compact_kernel read."""
+    r * count on every rank — the layout fit_api.hip's gathered_trend / trend_compact_kernel read."""
     import socket
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
