@@ -1,0 +1,616 @@
+"""The judge of the dispersion stage, and the CPU oracle before it.
+
+`judge(case, outputs)` holds one fit's dispersion-stage columns (baseMean, baseVar, allZero, dispGeneEst, dispGeneIter, dispFit, dispMAP,
+dispIter, dispOutlier, dispersion) to tests/disp_twin.py (50 digits).
+
+Exact requirements, every row: allZero and the NaN / zero-step pattern of all-zero rows; dispGeneIter equal to the step count of the
+gene-wise search replayed from the double nearest the twin's alpha_init; dispIter equal to that of the MAP search replayed from the
+REPORTED dispGeneEst and dispFit (the MAP stage is judged on its own inputs); dispOutlier equal to the rule applied to the reported
+dispGeneEst, dispFit and varLogDispEsts; dispersion the bits of dispGeneEst where dispOutlier, else those of dispMAP; every estimate in
+[1e-8, max(10, S)].
+
+Near rows: a replay records every decision with its margin; a margin below NEAR_UNITS units of each of the two values compared (the
+objective's unit there: u T_lp; x the oracle's own measured error at that point where that is worse than one unit) may fall either
+way in double arithmetic.  A row that disagrees with the replay must then agree with the replay that takes the other branch at one
+such decision, and is counted as `near` (capped: NEAR_CAP of the judged rows).  Rows whose gene-wise estimate ends below 1e-6 (1 / alpha
+>= 1e6: the lgamma differences have lost six digits or more) are capped apart: with a near decision they need only end below 1e-6.
+
+Measured, in the twin's units, per stratum (quantity, row class): baseMean, baseVar, log dispGeneEst, log dispMAP, dispFit (and
+dispInit where a fit reports it).  Here the judge runs on oracle.nbglm_fit: no violation, near rows within the cap, every stratum below
+SEPARATION units (not an accuracy claim: between "another formula" and "double arithmetic"); the planted classes are present; eleven
+wrong variants are each rejected on rows of counts, the twelfth (the grid's last maximum) on an objective with a plateau.  tests/test_gpu_disp.py applies the same judge to the device, with the oracle as the yardstick.
+"""
+import math
+import time
+
+import mpmath as mp
+import numpy as np
+import pytest
+
+import disp_inputs as di
+import disp_twin as dt
+
+SEPARATION = 64.0      # units: between "another formula" and "double arithmetic" (the Wald judge's)
+NEAR_UNITS = 4.0       # tests/test_gpu_objective.py: ALLOWANCE 4 x FLOOR 1, for each of the two values compared
+NEAR_CAP = 0.01        # share of a case's judged rows that may be near (the Wald judge's)
+SMALL_STRATUM = 20
+CLASSES = ["steps <= 10", "11-29", "30-99", "grid", "reverted", "floor (< 1e-6)", "ceiling", "some mu floored"]
+CHAIN_MAX = 24         # near decisions in a row that a fit may take the other way before it must agree with the replay
+BELOW_ROUNDING_CAP = 2 * di.N_GIANT + di.N_HUGE  # the rows planted with counts of 1e6 and more (giant, huge) and their copies: no other row's T_lp reaches 1e7
+BIG_S, RANDOM_ROWS = 15, 150   # from S = 15 on: the planted rows and 150 seeded random ones
+
+_CLOSED, _REPLAY, _OBJ = {}, {}, {}
+
+
+def _bits(x):
+    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return (_bits(a) == _bits(b)) | (np.isnan(a) & np.isnan(b))
+
+
+def closed_of(case):
+    if case["name"] not in _CLOSED:
+        with mp.workdps(dt.DPS):
+            _CLOSED[case["name"]] = dt.closed_forms(case["counts"], case["nf"], case["group"])
+    return _CLOSED[case["name"]]
+
+
+def replay_of(case, i, start, prior=None, flip=()):
+    """Kept for the session by (case, row, start, prior, flipped decisions); the objective's values are shared among them."""
+    pk = None if prior is None else (float(prior[0]).hex(), float(prior[1]).hex())
+    key = (case["name"], i, float(start).hex(), pk, tuple(flip))
+    if key not in _REPLAY:
+        ok = (case["name"], i, pk)
+        if ok not in _OBJ:
+            pr = None if prior is None else (mp.log(mp.mpf(float(prior[0]))), mp.mpf(float(prior[1])))
+            _OBJ[ok] = dt.Objective(case["counts"][i], closed_of(case)[0][i]["mu"], case["group"], pr)
+        _REPLAY[key] = dt.replay(case["counts"][i], None, case["group"], start, prior=None if prior is None else True, maxit=case["maxit"],
+                                 flip=frozenset(flip), S=case["S"], objective=_OBJ[ok])
+    return _REPLAY[key]
+
+
+def judged_rows(case):
+    """All rows below S = 15; from there on the planted rows and RANDOM_ROWS seeded random ones."""
+    n = len(case["counts"])
+    if case["S"] < BIG_S:
+        return list(range(n))
+    p = case["planted"]
+    planted = np.concatenate([v.ravel() for k, v in p.items()])
+    rng = np.random.default_rng(2701 + case["S"])
+    return sorted(set(int(r) for r in planted) | set(int(r) for r in rng.choice(n, RANDOM_ROWS, replace=False)))
+
+
+def judge(case, outputs, rows=None, oracle=None, device=False):
+    """Every row of `rows` (default: judged_rows) of one fit against the twin.  `oracle` (the module) lets a near decision be measured in
+    the oracle's own error at that point; `device`: floor-class rows use the plain unit (see the module docstring).  Returns
+      errors      {(quantity, class): [(error in units, row), ...]}
+      violations  [(row, what, detail)]
+      near        rows that agree with the replay only after one near decision is taken the other way (capped)
+      floor_near  floor-class rows excused by a near decision (logged, not capped with the others)
+      below_rounding  searches that disagree where dispTol itself is below the objective's rounding (the `giant` rows' MAP search)
+      stats       what the twin saw."""
+    with mp.workdps(dt.DPS):
+        return _judge(case, outputs, judged_rows(case) if rows is None else [int(r) for r in rows], oracle, device)
+
+
+def _near_index(case, i, rp, prior, oracle, plain_unit):
+    """Indices of the decisions of a replay whose margin is inside the combined rounding of the values compared."""
+    out = []
+    cf = closed_of(case)[0][i]
+    for k, d in enumerate(rp["decisions"]):
+        mult = 1.0
+        if abs(d["margin"]) > 1024 * NEAR_UNITS * dt.U * d["T"]:
+            continue  # (no measured error of the oracle's objective comes near a thousand units)
+        if oracle is not None and not plain_unit and d["kind"] in ("armijo", "change", "revert", "grid-coarse", "grid-fine"):
+            mu = np.array([float(m) for m in cf["mu"]])
+            obj = _OBJ[(case["name"], i, None if prior is None else (float(prior[0]).hex(), float(prior[1]).hex()))]
+            for a in d["points"]:
+                kw = {} if prior is None else dict(prior_mean=math.log(prior[0]), prior_sigmasq=float(prior[1]), use_prior=True)
+                got = oracle.log_posterior(float(a), case["counts"][i].astype(float), mu, case["group"], **kw)
+                lp, T = obj.lp(a)
+                mult = max(mult, float(abs(mp.mpf(got) - lp) / (dt.U * T)))
+        if is_near(d, mult):
+            out.append(k)
+    return out
+
+
+def is_near(d, mult=1.0):
+    """A decision inside the combined rounding of the values compared.  Two grid points that are EQUAL in exact arithmetic are no such
+    case: there the rule decides (the first maximum), and a fit that reports the later one is wrong."""
+    if d["kind"].startswith("grid") and d["margin"] == 0:
+        return False
+    return abs(d["margin"]) <= NEAR_UNITS * mult * dt.U * d["T"]
+
+
+def _err_log(got, rp, extra_unit=0):
+    """|log got - log of the replay's result| in units: the search's own unit for a search's end, u |log alpha| (+ extra) for a value
+    that is a bound or the start."""
+    ref = rp["alpha"]
+    plain = rp["clamped"] is not None or rp["reverted"]
+    unit = dt.U * (1 + abs(mp.log(ref))) + extra_unit if plain else rp["unit"]
+    return float(abs(mp.log(mp.mpf(float(got))) - mp.log(ref)) / unit)
+
+
+def _class_of(rp, cf):
+    c = ("grid" if rp["grid"] else "reverted" if rp["reverted"] else "floor (< 1e-6)" if rp["alpha"] < mp.mpf(1e-6) else "ceiling" if rp["clamped"] == "ceiling"
+         else "steps <= 10" if rp["iter"] <= 10 else "11-29" if rp["iter"] <= 29 else "30-99")
+    return [c] + (["some mu floored"] if cf["mufloored"] else [])
+
+
+def _search(case, i, stage, got_alpha, got_iter, start, prior, cf, oracle, device, res, extra_unit=0):
+    """One search of one row against its replay; a mismatch is looked up among the replays that take one near decision the other way."""
+    rp = replay_of(case, i, start, prior)
+    floor = rp["alpha"] < mp.mpf(1e-6)
+    agrees = lambda r: r["iter"] == got_iter and _err_log(got_alpha, r, extra_unit) <= SEPARATION
+    if not agrees(rp):
+        nearby = _near_index(case, i, rp, prior, oracle, plain_unit=device and floor)
+        if floor and nearby:
+            res["floor_near"] += 1
+            if not got_alpha < 1e-6:
+                res["violations"].append((i, f"{stage}: a floor row with a near decision must still end below 1e-6", got_alpha))
+            return None
+        if not floor and dt.DISP_TOL <= 2 * NEAR_UNITS * dt.U * rp["decisions"][0]["T"]:
+            # the stop test (change < 1e-6) lies below the rounding of the objective itself (counts near 1e9: T_lp of 1e10 and more): no
+            # step of such a search is decided in double arithmetic.  A named class: counted, held to the exact requirements that
+            # do not need the path (bounds, outlier rule, the bits of `dispersion`), not to a step count
+            res["below_rounding"] += 1
+            return None
+        # a decision inside rounding seldom comes alone: where the steps have become so small that kappa eps dlp^2 is below the
+        # rounding of lp, every Armijo test from there on is one.  So: the replay that takes ONE near decision the other way, and,
+        # where that does not agree yet, the next near decision after it as well, and so on (a chain, CHAIN_MAX long at the most)
+        found = None
+        for k0 in nearby:
+            flips = (k0,)
+            for _ in range(CHAIN_MAX):
+                alt = replay_of(case, i, start, prior, flip=flips)
+                if agrees(alt):
+                    found = alt
+                    break
+                later = [k for k in _near_index(case, i, alt, prior, oracle, plain_unit=device and floor) if k > flips[-1]]
+                if not later:
+                    break
+                flips += (later[0],)
+            if found is not None:
+                break
+        if found is not None:
+            res["near"] += 1
+            rp = found
+        else:
+            what = "step count" if rp["iter"] != got_iter else "estimate"
+            res["violations"].append((i, f"{stage}: {what}", (got_iter, rp["iter"], float(got_alpha), float(rp["alpha"]),
+                                                            [(rp["decisions"][k]["kind"], rp["decisions"][k]["step"]) for k in nearby])))
+            return None
+    return rp
+
+
+def _judge(case, o, rows, oracle, device):
+    S, group = case["S"], case["group"]
+    p = 2 if case["two_groups"] else 1
+    cfs, xi = closed_of(case)
+    md = dt.max_disp(S)
+    res = dict(errors={}, violations=[], near=0, floor_near=0, below_rounding=0,
+               stats=dict(rows=len(rows), near_decisions=0, long=0, maxit_gene=0, maxit_map=0, reverted=0, one_step=0, floor=0, ceiling=0, clamp_hi=0, clamp_lo=0,
+                          muflo=0, rough=0, moments=0, outlier=0, not_outlier=0, start_gene=0, start_fit=0, grid_gene=0, grid_map=0))
+    st = res["stats"]
+    gs = dt.global_stage(o["baseMean"], o["dispGeneEst"], S, p, coefs=case["opts"]["trendCoef"])
+    v_rep = float(o["varLogDispEsts"])
+    prior_var = float(case["opts"]["dispPriorVar"])
+
+    def add(q, classes, e, i):
+        for c in classes:
+            res["errors"].setdefault((q, c), []).append((e, i))
+
+    add("varLogDispEsts", ["case"], float(abs(mp.mpf(v_rep) - gs["varLogDispEsts"]) / gs["unit"]["varLogDispEsts"]), -1)
+    est_cols = ("dispGeneEst", "dispFit", "dispMAP", "dispersion")
+    for i in rows:
+        cf = cfs[i]
+        if int(o["allZero"][i]) != cf["allZero"]:
+            res["violations"].append((i, "allZero", int(o["allZero"][i])))
+            continue
+        if cf["allZero"]:
+            bad = [k for k in est_cols if not np.isnan(o[k][i])] + [k for k in ("dispGeneIter", "dispIter", "dispOutlier") if o[k][i] != 0] + \
+                  [k for k in ("baseMean", "baseVar") if o[k][i] != 0]
+            if bad:
+                res["violations"].append((i, "all-zero row", bad))
+            continue
+        ge, fit, mapv, fin = (float(o[k][i]) for k in est_cols)
+        if not all(math.isfinite(v) and MIN_OK <= v <= md for v in (ge, mapv, fin)) or not (math.isfinite(fit) and fit > 0):
+            res["violations"].append((i, "an estimate outside [1e-8, max(10, S)] or not finite", (ge, fit, mapv, fin)))
+            continue
+        # gene-wise
+        start = float(cf["init"])
+        u_init = cf["unit"]["init"] / cf["init"] if not cf["clamped"] else 0
+        rp = _search(case, i, "gene-wise", ge, int(o["dispGeneIter"][i]), start, None, cf, oracle, device, res, extra_unit=u_init)
+        base0 = replay_of(case, i, start)
+        st["near_decisions"] += bool(_near_index(case, i, base0, None, None, True)) and not base0["alpha"] < mp.mpf(1e-6)
+        st["long"] += 30 <= base0["iter"] <= 99
+        st["maxit_gene"] += base0["iter"] >= case["maxit"]
+        st["grid_gene"] += base0["grid"]
+        st["reverted"] += base0["reverted"]
+        st["one_step"] += base0["iter"] == 1
+        st["floor"] += base0["clamped"] == "floor"
+        st["ceiling"] += base0["clamped"] == "ceiling"
+        st["clamp_hi"] += any(b == 10 for _, b in base0["proposals_clamped"])
+        st["clamp_lo"] += any(b == -30 for _, b in base0["proposals_clamped"])
+        st["muflo"] += cf["mufloored"] > 0
+        st[cf["branch"]] += 1
+        cls = _class_of(rp or base0, cf)
+        add("baseMean", cls, float(abs(mp.mpf(float(o["baseMean"][i])) - cf["baseMean"]) / cf["unit"]["baseMean"]), i)
+        add("baseVar", cls, float(abs(mp.mpf(float(o["baseVar"][i])) - cf["baseVar"]) / cf["unit"]["baseVar"]), i)
+        if "dispInit" in o and not cf["clamped"]:
+            add("dispInit", cls, float(abs(mp.mpf(float(o["dispInit"][i])) - cf["init"]) / cf["unit"]["init"]), i)
+        elif "dispInit" in o and float(o["dispInit"][i]) != start:
+            res["violations"].append((i, "alpha_init on a bound", (float(o["dispInit"][i]), start)))
+        if rp is not None:
+            add("log dispGeneEst", cls, _err_log(ge, rp, u_init), i)
+        add("dispFit", cls, float(abs(mp.mpf(fit) - gs["dispFit"][i]) / gs["unit"]["dispFit"][i]), i)
+        # MAP, on its own inputs
+        s0, margin, mag = dt.map_start(ge, fit)
+        st["start_gene" if margin > 0 else "start_fit"] += 1
+        rm = _search(case, i, "MAP", mapv, int(o["dispIter"][i]), s0, (fit, prior_var), cf, oracle, device, res)
+        if rm is None and abs(margin) <= NEAR_UNITS * dt.U * mag and res["violations"] and res["violations"][-1][0] == i:
+            last = res["violations"].pop()
+            rm = _search(case, i, "MAP", mapv, int(o["dispIter"][i]), ge if s0 == fit else fit, (fit, prior_var), cf, oracle, device, res)
+            if rm is None:
+                res["violations"][-1] = last
+            else:
+                res["near"] += 1
+        basem = replay_of(case, i, s0, (fit, prior_var))
+        st["maxit_map"] += basem["iter"] >= case["maxit"]
+        st["grid_map"] += basem["grid"]
+        if rm is not None:
+            add("log dispMAP", _class_of(rm, cf), _err_log(mapv, rm), i)
+        # outlier and final value
+        is_out, om, omag = dt.outlier_rule(ge, fit, v_rep)
+        st["outlier" if is_out else "not_outlier"] += 1
+        got_out = int(o["dispOutlier"][i])
+        if got_out != int(is_out):
+            if abs(om) <= NEAR_UNITS * dt.U * omag:
+                res["near"] += 1
+            else:
+                res["violations"].append((i, "dispOutlier", (got_out, int(is_out), float(om))))
+        want = ge if got_out else mapv
+        if not same_bits(fin, want):
+            res["violations"].append((i, "dispersion is not the bits of dispGeneEst (outlier) / dispMAP", (fin, want)))
+    return res
+
+
+MIN_OK = 1e-8
+
+
+def pooled(results, partition=None):
+    """{case: judge result} -> {(case or "pooled", quantity, class): (worst, rows, where)}: a stratum of fewer than SMALL_STRATUM rows
+    joins the same stratum of the other cases.  `partition`, when given, is used instead of the row counts, so that two fits of the
+    same inputs are divided the same way; it is returned as the second value."""
+    own = set(partition) if partition is not None else {(c, q, k) for c, r in results.items() for (q, k), v in r["errors"].items() if len(v) >= SMALL_STRATUM}
+    acc = {}
+    for c, r in results.items():
+        for (q, k), v in r["errors"].items():
+            acc.setdefault((c if (c, q, k) in own else "pooled", q, k), []).extend((e, (c, i)) for e, i in v)
+    return {key: (max(v)[0], len(v), max(v)[1]) for key, v in acc.items()}, own
+
+
+def rejected(res, bound=SEPARATION):
+    """What a wrong implementation must bring about: a violation, or an error beyond the separation."""
+    return bool(res["violations"]) or any(e > bound for v in res["errors"].values() for e, _ in v)
+
+
+def judge_global(fit, columns, scalars, oracle_yard=None):
+    """The global stage of a free fit: trend coefficients, trendOuterIter, dispFit, varLogDispEsts and dispPriorVar (m - p > 3) against
+    the twin on the fit's own baseMean and dispGeneEst.  Returns dict(errors {quantity: error in units}, violations, near)."""
+    with mp.workdps(dt.DPS):
+        S = fit["S"]
+        p = 2 if fit["group"].any() else 1
+        gs = dt.global_stage(columns["baseMean"], columns["dispGeneEst"], S, p)
+        res = dict(errors={}, violations=[], near=0, twin=gs)
+        if gs["failed"]:
+            res["violations"].append((-1, "the twin's trend fails on these estimates", None))
+            return res
+        near = gs["near"] < 1e-9  # a filter bound, the outer stop or a glm stop within 1e-9 (relative): far more than any rounding of it
+        # trendOuterIter counts the rounds AFTER the first (DESeq2's `iter` when its loop breaks)
+        if int(scalars["trendOuterIter"]) != gs["rounds"] - 1:
+            if near and abs(int(scalars["trendOuterIter"]) - (gs["rounds"] - 1)) == 1:
+                res["near"] += 1
+            else:
+                res["violations"].append((-1, "trendOuterIter", (int(scalars["trendOuterIter"]), gs["rounds"] - 1)))
+        for k in (0, 1):
+            res["errors"][f"trendCoef[{k}]"] = float(abs(mp.mpf(float(scalars["trendCoef"][k])) - gs["coefs"][k]) / gs["unit"]["coefs"][k])
+        res["errors"]["varLogDispEsts"] = float(abs(mp.mpf(float(scalars["varLogDispEsts"])) - gs["varLogDispEsts"]) / gs["unit"]["varLogDispEsts"])
+        if gs["dispPriorVar"] is not None:
+            res["errors"]["dispPriorVar"] = float(abs(mp.mpf(float(scalars["dispPriorVar"])) - gs["dispPriorVar"]) / gs["unit"]["dispPriorVar"])
+        # dispFit against the REPORTED coefficients: the row formula on its own inputs
+        c0, c1 = (mp.mpf(float(v)) for v in scalars["trendCoef"])
+        worst = 0.0
+        for i in range(len(columns["baseMean"])):
+            if gs["dispFit"][i] is None:
+                continue
+            bm = mp.mpf(float(columns["baseMean"][i]))
+            ref = c0 + c1 / bm
+            worst = max(worst, float(abs(mp.mpf(float(columns["dispFit"][i])) - ref) / (dt.U * (abs(c0) + abs(c1 / bm)))))
+        res["errors"]["dispFit"] = worst
+        return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the oracle under the judge
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def oracle():
+    from oracle import oracle as o
+    o.build()
+    return o
+
+
+_FITS = {}
+
+
+def oracle_columns(oracle, case):
+    return oracle.nbglm_fit(case["counts"], case["nf"], case["group"], **case["opts"])
+
+
+def oracle_fit(oracle, name):
+    if name not in _FITS:
+        case = di.make_case(name)
+        t0 = time.perf_counter()
+        ref = oracle_columns(oracle, case)
+        res = judge(case, ref, oracle=oracle)
+        print(f"{name}: judged {res['stats']['rows']} rows in {time.perf_counter() - t0:.1f} s; near {res['near']}, floor near {res['floor_near']}, below rounding {res['below_rounding']}; {res['stats']}")
+        _FITS[name] = (case, ref, res)
+    return _FITS[name]
+
+
+@pytest.mark.parametrize("name", list(di.DESIGNS))
+def test_oracle_against_twin(oracle, name):
+    """The oracle's dispersion-stage columns: no violation, near rows (those that agree only with a near decision taken the
+    other way) within the cap — the condition the inputs are chosen to meet — and every stratum below SEPARATION units.  (How many
+    rows above the floor hold a near decision at all is printed with the statistics.)"""
+    case, ref, res = oracle_fit(oracle, name)
+    for (q, k), v in sorted(res["errors"].items()):
+        print(f"  {q} | {k}: n={len(v)} worst {max(v)[0]:.3g} units (row {max(v)[1]})")
+    assert not res["violations"], res["violations"][:10]
+    n = res["stats"]["rows"]
+    assert res["near"] <= NEAR_CAP * n, (res["near"], res["stats"])
+    assert res["below_rounding"] <= BELOW_ROUNDING_CAP
+    worst = {k: max(v) for k, v in res["errors"].items()}
+    assert all(e < SEPARATION for e, _ in worst.values()), {k: w for k, w in worst.items() if not w[0] < SEPARATION}
+
+
+@pytest.mark.parametrize("name", list(di.DESIGNS))
+def test_planted_classes_are_present(oracle, name):
+    """What every case is built to hold, as the twin sees it (the replays of the judged rows)."""
+    case, ref, res = oracle_fit(oracle, name)
+    st, p = res["stats"], case["planted"]
+    assert (st["long"] >= 2 or case["maxit"] < 30) and st["maxit_gene"] >= 2 and st["grid_gene"] >= 2, st  # (2: what the 215-odd judged rows of S >= 15 hold)
+    assert st["reverted"] >= 3 and st["one_step"] >= 3 and st["floor"] >= 10 and st["ceiling"] >= 3, st
+    assert st["clamp_hi"] >= 1 and st["muflo"] >= 10, st
+    # a proposal below -30 needs dlp < -11.6 at the start 1e-8; on a row with less than Poisson variance dlp tends to -(S - p) / 2 as
+    # mu alpha grows and never passes it: only S >= 26 can hold such a row
+    assert st["clamp_lo"] >= (1 if case["S"] >= 26 else 0), st
+    assert st["rough"] >= 10 and st["moments"] >= 10, st
+    assert st["outlier"] >= 5 and st["not_outlier"] >= 5 and st["start_gene"] >= 5 and st["start_fit"] >= 5, st
+    if name == di.MAXIT_CASE:
+        assert st["maxit_map"] >= 20 and st["grid_map"] >= 20, st
+    assert (ref["allZero"][p["zero"]] == 1).all() and ref["allZero"].sum() >= 3
+    cfs, _ = closed_of(case)
+    with mp.workdps(dt.DPS):
+        def rp(i):
+            return replay_of(case, int(i), float(cfs[int(i)]["init"]))
+        assert all(rp(i)["iter"] == 1 and rp(i)["reverted"] and rp(i)["clamped"] == "floor" for i in p["pois"][:1]), [rp(i)["iter"] for i in p["pois"]]
+        assert case["S"] < 26 or any(b == -30 for i in p["giant"] for _, b in rp(i)["proposals_clamped"])
+        # (in the interleaved design the rows' alternating pattern IS the group mask: two constant cells, nothing over-dispersed)
+        assert name == "S6-010101" or sum(float(cfs[int(i)]["init"]) == 1e-8 and rp(i)["alpha"] > 1 for i in p["blow"]) >= 2
+        assert sum(rp(i)["clamped"] == "ceiling" for i in p["spike"]) >= 3
+        assert sum(cfs[int(i)]["mufloored"] > 0 for i in p["wide"]) >= 10 and sum(cfs[int(i)]["mufloored"] < case["S"] for i in p["wide"]) >= 10
+    k = case["counts"][p["huge"]].max(axis=1)
+    assert sorted(k) == [2000 * 2 ** t for t in range(11)]
+    for dst in p["copies"]:
+        assert np.array_equal(case["counts"][dst], case["counts"][p["hard"]]) and np.array_equal(case["nf"][dst], case["nf"][p["hard"]])
+
+
+def test_pooled_strata_of_the_oracle(oracle):
+    """Strata too small to stand alone in a case, pooled over the cases: the same separation; no stratum is empty."""
+    strata, _ = pooled({name: oracle_fit(oracle, name)[2] for name in di.DESIGNS})
+    for k, (w, n, at) in sorted(strata.items()):
+        if k[0] == "pooled":
+            print(f"  {k}: n={n} worst {w:.3g} units at {at}")
+    assert all(w < SEPARATION for w, _, _ in strata.values()), {k: v for k, v in strata.items() if not v[0] < SEPARATION}
+    for q in ("baseMean", "baseVar", "log dispGeneEst", "dispFit"):
+        for c in CLASSES:
+            assert any(k[1] == q and k[2] == c for k in strata), (q, c)
+    for c in ("steps <= 10", "11-29", "grid", "some mu floored"):
+        assert any(k[1] == "log dispMAP" and k[2] == c for k in strata), c
+
+
+def test_global_stage_of_the_oracle(oracle):
+    """The three free fits: the oracle's trend, MAD and prior variance against the twin on the oracle's own estimates."""
+    for name in di.FREE_FITS:
+        fit = di.make_free(name)
+        t0 = time.perf_counter()
+        ref = oracle.nbglm_fit(fit["counts"], fit["nf"], fit["group"])
+        res = judge_global(fit, ref, ref)
+        print(f"{name}: {time.perf_counter() - t0:.1f} s; rounds {res['twin']['rounds']}, closest decision {float(res['twin']['near']):.3g}; {res['errors']}")
+        assert not res["violations"] and res["near"] == 0, res["violations"]
+        assert (fit["S"] - 2 > 3) == ("dispPriorVar" in res["errors"])
+        assert all(e < SEPARATION for e in res["errors"].values()), res["errors"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the judge can fail: twelve wrong variants
+# ---------------------------------------------------------------------------------------------------------------------------
+def _lp_double(a, y, mu, g2, prior, cox_reid=True, deriv=False):
+    from scipy.special import digamma, gammaln
+    al = math.exp(a)
+    r = 1.0 / al
+    w = 1.0 / (1.0 / mu + al)
+    groups = (g2 == 0, g2 == 1) if g2.any() else (np.ones(len(y), bool),)
+    if not deriv:
+        v = float(np.sum(gammaln(y + r) - gammaln(r) - y * np.log(mu + r) - r * np.log1p(mu * al)))
+        if cox_reid:
+            v -= 0.5 * sum(math.log(w[m].sum()) for m in groups)
+        if prior is not None:
+            v -= (a - prior[0]) ** 2 / (2 * prior[1])
+        return v
+    v = float(r * np.sum(digamma(r) + np.log1p(mu * al) - mu * al / (1 + mu * al) - digamma(y + r) + y / (mu + r)))
+    if cox_reid:
+        v -= 0.5 * al * sum(float(-(w[m] ** 2).sum() / w[m].sum()) for m in groups)
+    if prior is not None:
+        v -= (a - prior[0]) / prior[1]
+    return v
+
+
+def _search_double(y, mu, g2, start, prior, S, maxit, f):
+    """fitDisp and what follows, in double arithmetic, with a switch for each wrong variant (f: set of names)."""
+    cr = "no_cox_reid" not in f
+    lp = lambda a: _lp_double(a, y, mu, g2, prior, cr)
+    dlp = lambda a: _lp_double(a, y, mu, g2, prior, cr, True)
+    a = math.log(start)
+    l0 = l = lp(a)
+    d = dlp(a)
+    kappa, it, acc = 1.0, 0, 0
+    prev = a
+    for _ in range(maxit):
+        it += 1
+        prop = a + kappa * d
+        if prop < -30.0:
+            kappa = (-30.0 - a) / d
+        if prop > 10.0:
+            kappa = (10.0 - a) / d
+        new = a + kappa * d
+        ln = lp(new)
+        if -ln <= -l - kappa * 1e-4 * d * d:
+            acc += 1
+            if "stop_before_accept" in f and ln - l < 1e-6:
+                break
+            prev, a = a, new
+            change = ln - l
+            if change < 1e-6:
+                l = ln
+                break
+            if a < math.log(1e-9):
+                break
+            l, d = ln, dlp(a)
+            kappa = min(kappa * 1.1, 1.0)
+            if acc % 5 == 0 and "no_fifth_halving" not in f:
+                kappa /= 2
+        else:
+            kappa /= 2
+    if "one_step_early" in f:
+        a = prev
+    md = float(max(10, S))
+    alpha = math.exp(a)
+    if prior is None:
+        alpha = min(alpha, md)
+        if l < l0 + abs(l0) / 1e6 and "no_revert" not in f:
+            alpha = start
+        grid = (not (it < maxit and it != 1)) and alpha > 1e-7
+    else:
+        grid = it >= maxit
+    if grid:
+        pts = np.linspace(math.log(1e-8), math.log(md), 20)
+        delta = pts[1] - pts[0]
+        for _ in range(2):
+            v = np.array([lp(x) for x in pts])
+            k = int(np.flatnonzero(v == v.max())[-1 if "grid_last_max" in f else 0])
+            best = pts[k]
+            pts = np.linspace(best - delta, best + delta, 20)
+        alpha = math.exp(best)
+    return min(max(alpha, 1e-8), md), it
+
+
+def double_stage(case, ref, rows, flags=()):
+    """The dispersion stage of `rows` in double arithmetic (all switches off: the right formulas, so that only the switch makes the
+    difference), as a copy of the oracle's columns with those rows replaced.  varLogDispEsts stays the reported one."""
+    f = set(flags)
+    S, g = case["S"], case["group"]
+    p = 2 if g.any() else 1
+    o = {k: (np.array(v, copy=True) if isinstance(v, np.ndarray) else v) for k, v in ref.items()}
+    o.pop("dispInit", None)  # a fit reports no alpha_init: a wrong one must show in the search that starts there
+    nz = case["counts"].sum(axis=1) > 0
+    xi = 1.0 if "xi_one" in f else float(np.mean(1.0 / case["nf"][nz].mean(axis=0)))
+    md = float(max(10, S))
+    sd = 1.0 if "outlier_1sd" in f else 2.0
+    for i in rows:
+        y, nf = case["counts"][i].astype(float), case["nf"][i]
+        if y.sum() == 0:
+            continue
+        q = y / nf
+        bm = q.mean()
+        bv = q.var(ddof=0 if "basevar_n" in f else 1)
+        gm = np.where(g == 1, q[g == 1].mean() if p == 2 else 0.0, q[g == 0].mean())
+        mu = np.maximum(nf * gm, 0.5)
+        ml = gm if "rough_no_floor" in f else np.maximum(gm, 1.0)
+        rough = max(float(np.sum(((q - ml) ** 2 - ml) / ml ** 2) / (S - p)), 0.0)
+        init = min(max(min(rough, (bv - xi * bm) / bm ** 2), 1e-8), md)
+        ge, gi = _search_double(y, mu, g, init, None, S, case["maxit"], f)
+        fit = 0.05 + 2.0 / bm
+        start = ge if (ge > 0.1 * fit or "map_start_gene" in f) else fit
+        centre = math.log(ge) if "prior_on_gene" in f else math.log(fit)
+        mv, mi = _search_double(y, mu, g, start, (centre, 1.0), S, case["maxit"], f - {"no_revert"})
+        out = int(math.log(ge) > math.log(fit) + sd * math.sqrt(float(ref["varLogDispEsts"])))
+        for k, v in (("baseMean", bm), ("baseVar", bv), ("dispGeneEst", ge), ("dispGeneIter", gi), ("dispFit", fit), ("dispMAP", mv), ("dispIter", mi),
+                     ("dispOutlier", out), ("dispersion", ge if out else mv)):
+            o[k][i] = v
+    return o
+
+
+VARIANTS = ["no_fifth_halving", "stop_before_accept", "no_cox_reid", "xi_one", "basevar_n", "rough_no_floor", "map_start_gene", "prior_on_gene", "outlier_1sd",
+            "no_revert", "one_step_early"]
+
+
+def _flagged(res):
+    return {i for i, _, _ in res["violations"]} | {i for v in res["errors"].values() for e, i in v if e > SEPARATION}
+
+
+@pytest.mark.parametrize("name", ["S4-0011", "S8-4v4", "S3-intercept"])
+def test_judge_rejects_wrong_variants(oracle, name):
+    """One wrong thing at a time, on the planted rows and 60 more: first the right formulas in the same double arithmetic pass on most
+    rows (plain lgamma differences do not carry every floor row); then every variant is rejected on rows that the right formulas
+    pass.  (The twelfth, the grid's LAST maximum instead of the first, cannot show on a row of counts: the objective is analytic in
+    log alpha, so no two grid points tie in exact arithmetic, and a tie in double arithmetic is a near decision like any other —
+    test_first_maximum_of_the_grid holds the rule itself on an objective with a plateau.)"""
+    case, ref, _ = oracle_fit(oracle, name)
+    p = case["planted"]
+    rows = np.unique(np.concatenate([p[k] for k in ("pois", "giant", "blow", "huge", "spike", "wide", "zero")] + [np.arange(80, 140)]))
+    right = judge(case, double_stage(case, ref, rows), rows, oracle=oracle)
+    good = np.array([r for r in rows if r not in _flagged(right)])
+    print(f"{name}: the right formulas pass on {len(good)} of {len(rows)} rows")
+    assert len(good) >= 0.8 * len(rows), (len(good), len(rows), right["violations"][:5])
+    missed = []
+    for v in VARIANTS:
+        res = judge(case, double_stage(case, ref, good, [v]), good, oracle=oracle)
+        hit = _flagged(res) & set(int(r) for r in good)
+        print(f"  {v}: flagged {len(hit)} of {len(good)} rows")
+        # (design ~1: rough = (baseVar - baseMean S / (S - 1)) / baseMean^2 lies below the moments estimate for every xi < S / (S - 1), so
+        # xi starts no search there but through the rough estimate's floor of mu at 1)
+        if not hit and not (v == "xi_one" and not case["two_groups"]):
+            missed.append(v)
+    assert not missed, missed
+
+
+class _Plateau:
+    """An objective with two grid points exactly equal on top: steps of height 1 and width 1.5 coarse grid steps around log(0.3)."""
+    prior = None
+
+    def lp(self, a, cox_reid=True):
+        h = mp.mpf("1.5") * (mp.log(mp.mpf(10)) - mp.log(mp.mpf(1e-8))) / 19
+        return -mp.floor(abs(a - mp.log(mp.mpf("0.3"))) / h) - 5, mp.mpf(10)
+
+    def dlp(self, a, cox_reid=True):
+        return mp.mpf(0), mp.mpf(1)
+
+
+def test_first_maximum_of_the_grid():
+    """(l) of the wrong variants.  On a plateau the twin takes the FIRST of the equal grid values, records the later one as a decision of
+    margin exactly 0, and does not count that as near: a fit that reports the later point has no replay to agree with."""
+    with mp.workdps(dt.DPS):
+        rp = dt.replay(None, None, np.zeros(8, dtype=np.int32), 1.0, S=8, objective=_Plateau())
+        assert rp["iter"] == 1 and rp["reverted"] and rp["grid"]
+        ties = [(k, d) for k, d in enumerate(rp["decisions"]) if d["kind"].startswith("grid") and d["margin"] == 0]
+        assert ties and all(d["points"][1] > d["points"][0] for _, d in ties)  # (winner, the later equal point)
+        assert not any(is_near(d) for _, d in ties)
+        k, d = [t for t in ties if t[1]["kind"] == "grid-coarse"][0]
+        last = dt.replay(None, None, np.zeros(8, dtype=np.int32), 1.0, S=8, objective=_Plateau(), flip=frozenset([k]))
+        assert last["alpha"] > rp["alpha"] and abs(mp.log(last["alpha"]) - mp.log(rp["alpha"])) > SEPARATION * rp["unit"]

@@ -8,6 +8,9 @@ stratum (quantity, row class), the device's worst error must stay within ALLOWAN
 same run, 1 unit) — 4, as for the dispersion objective (tests/test_gpu_objective.py) and for the same reasons: table-driven 1-ulp
 texp / tlog and rcp against libm and IEEE division, sums folded in another order.  Nothing else is fixed in advance.
 
+The dispersion-stage columns that COLUMNS leaves out (baseMean, baseVar, dispGeneEst, dispFit, dispMAP, dispGeneIter, dispIter,
+dispOutlier) have a judge of their own: tests/disp_twin.py, tests/test_disp_twin.py and tests/test_gpu_disp.py.
+
 Every comparison goes to test_gpu_parity.PARITY_LOG (profiles/r23_wald_accuracy.json holds the records of one run).
 """
 import numpy as np
