@@ -89,6 +89,9 @@ struct chicdiff_hip_ctx {
     size_t pk_buf_bytes = 0;
     int64_t pk_stride = 0, pk_rows = -1;    // pk_rows >= 0: a successful read of this many rows
     int pk_nscore = 0;
+    // while chin_text still holds the body of that read (chicdiff_hip_peaks_textkeys_dev walks it): its length and separator
+    int64_t pk_text_bytes = -1;
+    int pk_sep = 0;
     // host-buffer entry point: columns that are final once the MAP dispersions exist leave for the host on a second
     // stream while the Wald stage runs (set for the duration of one chicdiff_hip_nbglm_fit call)
     struct EarlyCopy {

@@ -44,6 +44,39 @@ int launch_peaks_filter(const int32_t *bait, const int32_t *oe, const double *di
                         double score, const int32_t *cond_of_col_host, int ncond, int replicate_rule, int64_t maxbait, int64_t *kept_idx,
                         int32_t *kept_bait, int32_t *kept_oe, int32_t *filtered, char *ws, hipStream_t st, const int64_t **totals_out);
 
+// ---- device (peaks_merge_kernels.hip): .multimerge ----
+// the F files of one merge, rows concatenated file-major: file f holds the rows off[f] .. off[f + 1] - 1 and the score rows
+// score_off[f] .. score_off[f + 1] - 1 of the result; its matrices are contiguous with n_f = off[f + 1] - off[f] columns
+struct PeaksMergeFiles {
+    int nfiles;
+    int64_t off[CHICDIFF_PEAKS_MERGE_MAX_FILES + 1];
+    int32_t score_off[CHICDIFF_PEAKS_MERGE_MAX_FILES + 1];
+    const int32_t *ints[CHICDIFF_PEAKS_MERGE_MAX_FILES];  // (6, n_f)
+    const double *dist[CHICDIFF_PEAKS_MERGE_MAX_FILES];   // (n_f)
+    const double *scores[CHICDIFF_PEAKS_MERGE_MAX_FILES]; // (T_f, n_f)
+    const int64_t *chr[CHICDIFF_PEAKS_MERGE_MAX_FILES];   // (2, n_f): chr(baitChr), chr(oeChr)
+    const int64_t *name[CHICDIFF_PEAKS_MERGE_MAX_FILES];  // (2, n_f): the hashes of baitName, oeName
+};
+struct PeaksMergeWork {
+    int *status;         // CHICDIFF_PEAKS_ST_MERGE_* bits
+    uint64_t *w, *ka, *kb;
+    uint32_t *pa, *pb;   // pa: the permutation once sorted
+    int32_t *flags;      // (N + 1): head flags, then their exclusive scan; flags[N] = n_out
+    void *tmp;
+    size_t tmp_bytes;
+};
+size_t peaks_textkeys_workspace_bytes(int64_t stride);
+int *peaks_textkeys_flags(char *ws);
+int64_t *peaks_textkeys_bytes(char *ws);
+int launch_peaks_textkeys(const unsigned char *text, int64_t nbytes, int sep, const int64_t *line_off, int64_t n, int64_t stride,
+                          int64_t *d_chr, int64_t *d_name, char *ws, hipStream_t st);
+size_t peaks_merge_workspace_bytes(int64_t N);
+PeaksMergeWork peaks_merge_work(char *ws, int64_t N);
+int launch_peaks_merge_sort(const PeaksMergeFiles &F, PeaksMergeWork &k, hipStream_t st);
+int launch_peaks_merge_heads(const PeaksMergeFiles &F, const PeaksMergeWork &k, hipStream_t st);
+void launch_peaks_merge_write(const PeaksMergeFiles &F, const PeaksMergeWork &k, int64_t cap, int32_t *o_ints, double *o_dist, double *o_scores,
+                              int32_t *o_file, int64_t *o_row, hipStream_t st);
+
 // ---- host (peaks.hip) ----
 // The file mapped and its header read: file.body = the offset of the body; sep = the one separator byte; score_col[j] = the 0-based
 // field of score column j (ascending), score_target[j] = which entry of `targets` names it.
@@ -56,6 +89,8 @@ struct PeaksFile {
     std::string error;
 };
 int peaks_open(const char *path, const char *const *targets, int ntargets, PeaksFile &f);  // 0, or -1 with f.error set (nothing stays mapped)
+// the same header rule without targets: the file mapped as above (nscore = 0) and every column name in file order
+int peaks_open_names(const char *path, PeaksFile &f, std::vector<std::string> &names);
 void peaks_close(PeaksFile &f);
 std::string peaks_malformed(long long offset);
 // one decimal field [p, e): empty or NA -> NaN, else the token of the rule through strtod; false = malformed
@@ -70,5 +105,9 @@ int64_t peaks_parse_host(const char *body, size_t nbytes, int sep, const int32_t
 void peaks_filter_host(const int32_t *bait, const int32_t *oe, const double *dist, const double *scores, int64_t stride, int64_t n, int nscore,
                        double score, const int32_t *cond_of_col, int ncond, int replicate_rule, std::vector<int64_t> &kept,
                        std::vector<int32_t> &filtered);
+
+// the host statement of the text keys (peaks_textkey.h) for the rows whose lines start at body + line_off[r]: chr (2, n) in the form of
+// each column's class, name (2, n); returns the status bits (CHICDIFF_PEAKS_ST_CHR_*), cls[2] = the columns' classes
+int peaks_textkeys_host(const char *body, size_t nbytes, int sep, const int64_t *line_off, int64_t n, int64_t *chr, int64_t *name, int cls[2]);
 
 }  // namespace cd

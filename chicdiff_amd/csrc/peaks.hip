@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "peaks.h"
+#include "peaks_textkey.h"
 
 namespace cd {
 
@@ -28,7 +29,8 @@ std::string peaks_malformed(long long offset) {
            " (the first 11 fields and the score columns must be present; coordinates and IDs integers, IDs not negative; dist and scores decimal, NA or empty)";
 }
 
-int peaks_open(const char *path, const char *const *targets, int ntargets, PeaksFile &f) {
+// the file mapped and its header read; names: every column name in file order
+static int peaks_open_impl(const char *path, const char *const *targets, int ntargets, PeaksFile &f, std::vector<std::string> &names) {
     const int fd = open(path, O_RDONLY);
     if (fd < 0) { f.error = std::string("cannot open ") + path; return -1; }
     struct stat stt;
@@ -44,7 +46,7 @@ int peaks_open(const char *path, const char *const *targets, int ntargets, Peaks
         const char *e = line_end(p);
         p = e < end ? e + 1 : end;
     }
-    std::vector<std::string> names;
+    names.clear();
     int sep = ' ';
     if (p < end) {
         const char *e = line_end(p), *he = e;
@@ -95,6 +97,13 @@ int peaks_open(const char *path, const char *const *targets, int ntargets, Peaks
     f.file.base = base; f.file.size = size; f.file.body = (size_t)(p - base);
     return 0;
 }
+
+int peaks_open(const char *path, const char *const *targets, int ntargets, PeaksFile &f) {
+    std::vector<std::string> names;
+    return peaks_open_impl(path, targets, ntargets, f, names);
+}
+
+int peaks_open_names(const char *path, PeaksFile &f, std::vector<std::string> &names) { return peaks_open_impl(path, nullptr, 0, f, names); }
 
 const char *peaks_field_end(const char *p, const char *body_end, int sep) {
     const char *q = p;
@@ -200,6 +209,38 @@ int64_t peaks_parse_host(const char *body, size_t nbytes, int sep, const int32_t
         s = le + 1;
     }
     return row;
+}
+
+int peaks_textkeys_host(const char *body, size_t nbytes, int sep, const int64_t *line_off, int64_t n, int64_t *chr, int64_t *name, int cls[2]) {
+    int flags[2] = {0, 0};
+    std::vector<int64_t> as_int(2 * (size_t)n), as_text(2 * (size_t)n);
+    const char *end = body + nbytes;
+    for (int64_t r = 0; r < n; r++) {
+        const char *p = body + line_off[r];
+        for (int field = 0; field < 10; field++) {
+            const char *e = peaks_field_end(p, end, sep);
+            if (field == 0 || field == 5) {
+                PkChrToken tok;
+                for (const char *q = p; q < e; q++) tok.feed((unsigned char)*q);
+                const size_t at = (field == 5 ? (size_t)n : 0) + (size_t)r;
+                flags[field == 5] |= pk_col_flags(tok);
+                as_int[at] = tok.value;
+                as_text[at] = pk_text_key(tok.packed);
+            } else if (field == 4 || field == 9) {
+                uint64_t h = kPkFnvBasis;
+                for (const char *q = p; q < e; q++) h = pk_fnv_step(h, (unsigned char)*q);
+                name[(field == 9 ? (size_t)n : 0) + (size_t)r] = (int64_t)h;
+            }
+            p = e < end && *e == (char)sep ? e + 1 : e;
+        }
+    }
+    int status = 0;
+    for (int k = 0; k < 2; k++) {
+        cls[k] = pk_col_class(flags[k], &status);
+        const std::vector<int64_t> &from = cls[k] == CHICDIFF_PEAKS_KEY_INT ? as_int : as_text;
+        for (int64_t r = 0; r < n; r++) chr[(size_t)k * (size_t)n + (size_t)r] = from[(size_t)k * (size_t)n + (size_t)r];
+    }
+    return status;
 }
 
 void peaks_filter_host(const int32_t *bait, const int32_t *oe, const double *dist, const double *scores, int64_t stride, int64_t n, int nscore,

@@ -2,6 +2,7 @@
 // peaks_kernels.hip).
 #include "ctx.h"
 #include "peaks.h"
+#include "peaks_textkey.h"
 
 // host-side self test of the .chinput parser (no device, no context): the three columns of up to `cap` rows
 extern "C" int chicdiff_hip_selftest_chinput(const char *path, int32_t nthreads, int64_t cap, int32_t *bait, int32_t *oe, int32_t *N,
@@ -143,6 +144,7 @@ extern "C" int chicdiff_hip_chinput_read_dev(chicdiff_hip_ctx *c, const char *pa
     const size_t body = f.size - f.body;
     HIPCHK(c, hipSetDevice(c->device));
     c->chin_dev_rows = -1;  // nothing to serve until this read has succeeded: an earlier read's columns are given up
+    c->pk_text_bytes = -1;  // (and the text buffer no longer holds a peak matrix)
     delete c->chin;
     c->chin = nullptr;
     timing_reset(c);
@@ -339,6 +341,7 @@ extern "C" int chicdiff_hip_peaks_read_dev(chicdiff_hip_ctx *c, const char *path
     if (!c) return CHICDIFF_E_INVALID;
     if (!path || !info || ntargets < 0 || (ntargets > 0 && (!targets || !score_target))) return fail(c, CHICDIFF_E_INVALID, "peaks_read: bad arguments");
     c->pk_rows = -1;  // nothing to serve until this read has succeeded
+    c->pk_text_bytes = -1;
     PeaksFile f;
     if (peaks_open(path, targets, ntargets, f) != 0) return fail(c, CHICDIFF_E_INVALID, "peaks_read: %s", f.error.c_str());
     struct Closer { PeaksFile &f; ~Closer() { peaks_close(f); } } closer{f};
@@ -356,6 +359,8 @@ extern "C" int chicdiff_hip_peaks_read_dev(chicdiff_hip_ctx *c, const char *path
     if (info[CHICDIFF_PEAKS_INFO_STATUS] == 0) {
         c->pk_rows = info[CHICDIFF_PEAKS_INFO_NROWS];
         c->pk_nscore = f.nscore;
+        c->pk_text_bytes = (int64_t)body;
+        c->pk_sep = f.sep;
     }
     return CHICDIFF_OK;
 }
@@ -411,6 +416,169 @@ extern "C" int chicdiff_hip_peaks_filter_dev(chicdiff_hip_ctx *c, const int32_t 
     timing_collect(c);
     *nkept_host = totals & 0xffffffffll;
     *nfiltered_host = totals >> 32;
+    return CHICDIFF_OK;
+}
+
+// ---- .multimerge on the device (chicdiff.R:218-228, 234-236; peaks_merge_kernels.hip, peaks_textkey.h) ------------------------------------
+extern "C" int chicdiff_hip_peaks_textkeys_dev(chicdiff_hip_ctx *c, int64_t *d_chr, int64_t *d_name, int64_t cap, int64_t *info) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (!info || cap < 0) return fail(c, CHICDIFF_E_INVALID, "peaks_textkeys: bad arguments");
+    if (c->pk_rows < 0 || c->pk_text_bytes < 0)
+        return fail(c, CHICDIFF_E_INVALID, "peaks_textkeys: the text buffer holds no peak matrix (call chicdiff_hip_peaks_read_dev first, and nothing else in between)");
+    const int64_t n = c->pk_rows;
+    if (cap < n || (n > 0 && (!d_chr || !d_name)))
+        return fail(c, CHICDIFF_E_INVALID, "peaks_textkeys: the read holds %lld rows, the caller's columns have room for %lld", (long long)n, (long long)cap);
+    for (int k = 0; k < CHICDIFF_PEAKS_TEXTKEYS_WORDS; k++) info[k] = 0;
+    info[CHICDIFF_PEAKS_TEXTKEYS_NROWS] = n;
+    if (n == 0) return CHICDIFF_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_aux(c, peaks_textkeys_workspace_bytes(cap))) return rc;
+    timing_reset(c);
+    const PeaksOut o = peaks_ctx_out(c, n, c->pk_nscore);
+    {
+        Scope t(c, "peaks_textkeys");
+        if (launch_peaks_textkeys((const unsigned char *)c->chin_text, c->pk_text_bytes, c->pk_sep, o.line_off, n, cap, d_chr, d_name, c->aux, c->stream))
+            return fail(c, CHICDIFF_E_HIP, "peaks_textkeys: memset failed");
+    }
+    int flags[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(flags, peaks_textkeys_flags(c->aux), sizeof flags, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    int status = 0;
+    for (int k = 0; k < 2; k++) {
+        const int cls = pk_col_class(flags[k], &status);
+        info[CHICDIFF_PEAKS_TEXTKEYS_CLASS_BAIT + k] = cls;
+        if (cls != CHICDIFF_PEAKS_KEY_INT)  // this column's keys are its bytes
+            HIPCHK(c, hipMemcpyAsync(d_chr + (size_t)k * (size_t)cap, peaks_textkeys_bytes(c->aux) + (size_t)k * (size_t)cap, sizeof(int64_t) * (size_t)n,
+                                     hipMemcpyDeviceToDevice, c->stream));
+    }
+    info[CHICDIFF_PEAKS_TEXTKEYS_STATUS] = status;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    timing_collect(c);
+    return CHICDIFF_OK;
+}
+
+extern "C" int chicdiff_hip_peaks_merge_dev(chicdiff_hip_ctx *c, int32_t nfiles, const int32_t *const *d_ints, const double *const *d_dist,
+                                            const double *const *d_scores, const int64_t *const *d_chr, const int64_t *const *d_name,
+                                            const int64_t *nrows, const int32_t *nscores, int64_t cap, int32_t *d_out_ints, double *d_out_dist,
+                                            double *d_out_scores, int32_t *d_src_file, int64_t *d_src_row, int64_t *info) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (!info || !d_ints || !d_dist || !d_scores || !d_chr || !d_name || !nrows || !nscores || cap < 0)
+        return fail(c, CHICDIFF_E_INVALID, "peaks_merge: bad arguments");
+    if (nfiles < 2 || nfiles > CHICDIFF_PEAKS_MERGE_MAX_FILES)
+        return fail(c, CHICDIFF_E_INVALID, "peaks_merge: 2 .. %d files", CHICDIFF_PEAKS_MERGE_MAX_FILES);
+    PeaksMergeFiles F;
+    memset(&F, 0, sizeof F);
+    F.nfiles = nfiles;
+    for (int f = 0; f < nfiles; f++) {
+        if (nrows[f] < 0 || nscores[f] < 0 || (nrows[f] > 0 && (!d_ints[f] || !d_dist[f] || !d_chr[f] || !d_name[f] || (nscores[f] > 0 && !d_scores[f]))))
+            return fail(c, CHICDIFF_E_INVALID, "peaks_merge: bad arguments for file %d", f);
+        F.off[f + 1] = F.off[f] + nrows[f];
+        F.score_off[f + 1] = F.score_off[f] + nscores[f];
+        if (F.off[f + 1] >= ((int64_t)1 << 31)) return fail(c, CHICDIFF_E_INVALID, "peaks_merge: the files hold 2^31 rows or more");
+        if (F.score_off[f + 1] > CHICDIFF_PEAKS_MAX_SCORES)
+            return fail(c, CHICDIFF_E_INVALID, "peaks_merge: more than %d score columns", CHICDIFF_PEAKS_MAX_SCORES);
+        F.ints[f] = d_ints[f]; F.dist[f] = d_dist[f]; F.scores[f] = d_scores[f]; F.chr[f] = d_chr[f]; F.name[f] = d_name[f];
+    }
+    const int64_t N = F.off[nfiles];
+    const int T = F.score_off[nfiles];
+    info[CHICDIFF_PEAKS_MERGE_NOUT] = info[CHICDIFF_PEAKS_MERGE_STATUS] = 0;
+    if (N == 0) return CHICDIFF_OK;
+    if (cap < N || !d_out_ints || !d_out_dist || (T > 0 && !d_out_scores) || !d_src_file || !d_src_row)
+        return fail(c, CHICDIFF_E_INVALID, "peaks_merge: the files hold %lld rows, the caller's columns have room for %lld", (long long)N, (long long)cap);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_aux(c, peaks_merge_workspace_bytes(N))) return rc;
+    timing_reset(c);
+    PeaksMergeWork k = peaks_merge_work(c->aux, N);
+    int rc = 0;
+    {
+        Scope t(c, "peaks_merge_sort");
+        rc = launch_peaks_merge_sort(F, k, c->stream);
+    }
+    if (!rc) {
+        Scope t(c, "peaks_merge_heads");
+        rc = launch_peaks_merge_heads(F, k, c->stream);
+    }
+    if (!rc) {
+        Scope t(c, "peaks_merge_write");
+        launch_peaks_merge_write(F, k, cap, d_out_ints, d_out_dist, d_out_scores, d_src_file, d_src_row, c->stream);
+    }
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);
+        return fail(c, CHICDIFF_E_HIP, "peaks_merge: %s", hipGetErrorString(hipGetLastError()));
+    }
+    int status = 0;
+    int32_t nout = 0;
+    HIPCHK(c, hipMemcpyAsync(&status, k.status, sizeof status, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&nout, k.flags + N, sizeof nout, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    timing_collect(c);
+    info[CHICDIFF_PEAKS_MERGE_NOUT] = nout;
+    info[CHICDIFF_PEAKS_MERGE_STATUS] = status;
+    return CHICDIFF_OK;
+}
+
+extern "C" int chicdiff_hip_peaks_header(const char *path, char *names, int32_t namecap, int32_t *ncols, int32_t *sep, char *err, int32_t errcap) {
+    if (!path || !names || namecap <= 0 || !ncols) return CHICDIFF_E_INVALID;
+    PeaksFile f;
+    std::vector<std::string> cols;
+    if (peaks_open_names(path, f, cols) != 0) {
+        if (err && errcap > 0) snprintf(err, (size_t)errcap, "%s", f.error.c_str());
+        return CHICDIFF_E_INVALID;
+    }
+    peaks_close(f);
+    std::string joined;
+    for (size_t k = 0; k < cols.size(); k++) joined += (k ? "\n" : "") + cols[k];
+    *ncols = (int32_t)cols.size();
+    if (sep) *sep = f.sep;
+    if (joined.size() + 1 > (size_t)namecap) {
+        if (err && errcap > 0) snprintf(err, (size_t)errcap, "peaks_header: the names take %zu bytes", joined.size() + 1);
+        return CHICDIFF_E_INVALID;
+    }
+    memcpy(names, joined.c_str(), joined.size() + 1);
+    return CHICDIFF_OK;
+}
+
+// the host statement of the text-key rule (peaks.hip, peaks_textkey.h): no device, no context
+extern "C" int chicdiff_hip_selftest_peaks_textkeys(const char *path, int64_t cap, int64_t *chr, int64_t *name, int64_t *info, char *err,
+                                                    int32_t errcap) {
+    if (!path || !info || cap < 0 || (cap > 0 && (!chr || !name))) return CHICDIFF_E_INVALID;
+    auto refuse = [&](const std::string &msg) {
+        if (err && errcap > 0) snprintf(err, (size_t)errcap, "%s", msg.c_str());
+        return CHICDIFF_E_INVALID;
+    };
+    PeaksFile f;
+    std::vector<std::string> cols;
+    if (peaks_open_names(path, f, cols) != 0) return refuse(f.error);
+    struct Closer { PeaksFile &f; ~Closer() { peaks_close(f); } } closer{f};
+    for (int k = 0; k < CHICDIFF_PEAKS_TEXTKEYS_WORDS; k++) info[k] = 0;
+    const char *body = f.file.base + f.file.body;
+    const size_t nbytes = f.file.size - f.file.body;
+    long long bad = -1;
+    int quote = 0, maxbait = -1;
+    const int64_t nrows = peaks_parse_host(body, nbytes, f.sep, f.score_col, 0, PeaksOut{nullptr, nullptr, nullptr, nullptr, 0, 0}, &bad, &quote, &maxbait);
+    info[CHICDIFF_PEAKS_TEXTKEYS_NROWS] = nrows;
+    if (quote) {
+        info[CHICDIFF_PEAKS_TEXTKEYS_STATUS] = CHICDIFF_PEAKS_ST_QUOTE;
+        return CHICDIFF_OK;
+    }
+    if (bad >= 0) return refuse(peaks_malformed(bad + (long long)f.file.body));
+    if (cap == 0 || nrows == 0) return CHICDIFF_OK;
+    const size_t n = (size_t)nrows;
+    std::vector<int32_t> vi(6 * n);
+    std::vector<double> vd(n);
+    std::vector<int64_t> vo(n), vc(2 * n), vn(2 * n);
+    (void)peaks_parse_host(body, nbytes, f.sep, f.score_col, 0, PeaksOut{vi.data(), vd.data(), nullptr, vo.data(), nrows, nrows}, &bad, &quote, &maxbait);
+    int cls[2];
+    info[CHICDIFF_PEAKS_TEXTKEYS_STATUS] = peaks_textkeys_host(body, nbytes, f.sep, vo.data(), nrows, vc.data(), vn.data(), cls);
+    info[CHICDIFF_PEAKS_TEXTKEYS_CLASS_BAIT] = cls[0];
+    info[CHICDIFF_PEAKS_TEXTKEYS_CLASS_OE] = cls[1];
+    const size_t m = (size_t)(nrows < cap ? nrows : cap);
+    for (int k = 0; k < 2; k++) {
+        memcpy(chr + (size_t)k * (size_t)cap, vc.data() + (size_t)k * n, 8 * m);
+        memcpy(name + (size_t)k * (size_t)cap, vn.data() + (size_t)k * n, 8 * m);
+    }
     return CHICDIFF_OK;
 }
 

@@ -33,6 +33,7 @@ EXPORTS = [
     "chicdiff_hip_chinput_parse_dev", "chicdiff_hip_chinput_read_dev", "chicdiff_hip_chinput_caps",
     "chicdiff_hip_peaks_parse_dev", "chicdiff_hip_peaks_read_dev", "chicdiff_hip_peaks_columns_dev", "chicdiff_hip_peaks_filter_dev",
     "chicdiff_hip_peaks_caps", "chicdiff_hip_selftest_peaks",
+    "chicdiff_hip_peaks_textkeys_dev", "chicdiff_hip_peaks_merge_dev", "chicdiff_hip_peaks_header", "chicdiff_hip_selftest_peaks_textkeys",
     "chicdiff_hip_count_join_inner_dev", "chicdiff_hip_count_join_multi_dev", "chicdiff_hip_region_assemble_dev",
     "chicdiff_hip_malloc", "chicdiff_hip_free", "chicdiff_hip_outstanding_allocations", "chicdiff_hip_memcpy_h2d", "chicdiff_hip_memcpy_d2h",
     "chicdiff_hip_rccl_unique_id", "chicdiff_hip_rccl_init", "chicdiff_hip_cooks_filter_dev",
@@ -144,6 +145,10 @@ def load_library() -> C.CDLL:
     L.chicdiff_hip_peaks_caps.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.chicdiff_hip_selftest_peaks.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), i32, dbl, C.POINTER(i32), i32, i32, i64, vp, vp, vp, vp, vp, vp,
                                               C.POINTER(i32), C.POINTER(i64), C.c_char_p, i32]
+    L.chicdiff_hip_peaks_textkeys_dev.argtypes = [vp, vp, vp, i64, C.POINTER(i64)]
+    L.chicdiff_hip_peaks_merge_dev.argtypes = [vp, i32] + [C.POINTER(vp)] * 5 + [C.POINTER(i64), C.POINTER(i32), i64, vp, vp, vp, vp, vp, C.POINTER(i64)]
+    L.chicdiff_hip_peaks_header.argtypes = [C.c_char_p, C.c_char_p, i32, C.POINTER(i32), C.POINTER(i32), C.c_char_p, i32]
+    L.chicdiff_hip_selftest_peaks_textkeys.argtypes = [C.c_char_p, i64, vp, vp, C.POINTER(i64), C.c_char_p, i32]
     L.chicdiff_hip_bh_adjust_dev.argtypes = [vp, vp, i64, vp]
     L.chicdiff_hip_region_avdist_dev.argtypes = [vp, vp, vp, i64, vp, i64, i32, i32, vp, vp, vp]
     L.chicdiff_hip_count_join_inner_dev.argtypes = [vp, vp, vp, i64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp]
@@ -283,11 +288,59 @@ def selftest_peaks(path, targetColumns, score=5.0, cond_of_target=None, replicat
                 filtered=filt[:d["nfiltered"]])
 
 
+# .multimerge on the device (include/chicdiff_hip.h, above chicdiff_hip_peaks_textkeys_dev)
+PEAKS_MERGE_MAX_FILES = 16
+PEAKS_ST_CHR_LONG, PEAKS_ST_CHR_AMBIGUOUS, PEAKS_ST_MERGE_DUPLICATE, PEAKS_ST_MERGE_NAME, PEAKS_ST_MERGE_DIST = 4, 8, 16, 32, 64
+PEAKS_KEY_INT, PEAKS_KEY_TEXT, PEAKS_KEY_MIXED = 0, 1, 2
+
+
+def peaks_header(path):
+    """The column names of a peak matrix and its separator byte, through the header rule of ``HipContext.read_peaks``
+    (chicdiff_hip_peaks_header: host only).  A header the rule refuses raises ValueError with the library's message."""
+    lib = load_library()
+    cap = 1 << 16
+    while True:
+        names, err = C.create_string_buffer(cap), C.create_string_buffer(512)
+        ncols, sep = C.c_int32(0), C.c_int32(0)
+        rc = lib.chicdiff_hip_peaks_header(os.fsencode(path), names, cap, C.byref(ncols), C.byref(sep), err, 512)
+        if rc and err.value.startswith(b"peaks_header: the names take") and cap < (1 << 28):
+            cap *= 16
+            continue
+        if rc:
+            raise ValueError(err.value.decode() or f"peaks_header: error {rc}")
+        return names.value.decode().split("\n"), sep.value
+
+
+def selftest_peaks_textkeys(path):
+    """The library's HOST statement of the text-key rule (chicdiff_hip_selftest_peaks_textkeys: no device, no context) on a file: a dict
+    with ``status`` (PEAKS_ST_CHR_* bits), ``key_class`` (baitChr, oeChr), ``chr_keys`` (2, n) and ``name_hash`` (2, n) int64."""
+    lib = load_library()
+    info, err = (C.c_int64 * 4)(), C.create_string_buffer(512)
+
+    def call(cap, chr_, name):
+        rc = lib.chicdiff_hip_selftest_peaks_textkeys(os.fsencode(path), cap, chr_.ctypes.data if chr_ is not None else None,
+                                                      name.ctypes.data if name is not None else None, info, err, 512)
+        if rc:
+            raise ValueError(err.value.decode() or f"selftest_peaks_textkeys: error {rc}")
+    call(0, None, None)
+    n = info[3]
+    chr_, name = np.zeros((2, n), dtype=np.int64), np.zeros((2, n), dtype=np.int64)
+    if n and not info[0]:
+        call(n, chr_, name)
+    return dict(status=info[0], key_class=(info[1], info[2]), chr_keys=chr_, name_hash=name, nrows=n)
+
+
 class Peaks:
     """A peak matrix on the device (``HipContext.read_peaks`` / ``parse_peaks_text``): ``ints`` (6, n) int32 — PEAKS_INT_COLUMNS, also
     as attributes —, ``dist`` (n) and ``scores`` (nscore, n) float64, ``line_off`` (n) int64: the offset of every row's line in the body;
     ``info``: the words of PEAKS_INFO; ``score_names``: the score rows' column names (file order).  ``status`` != 0 (PEAKS_ST_*): the
-    device did not parse this body and no column is held."""
+    device did not parse this body and no column is held.  After ``read_peaks(text_keys=True)`` also ``chr_keys`` (2, n) int64 — the
+    sort keys of baitChr and oeChr —, ``name_hash`` (2, n) int64 — baitName, oeName —, ``key_class`` (PEAKS_KEY_* of the two
+    chromosome columns) and ``key_status`` (PEAKS_ST_CHR_* bits).  After ``merge_peaks`` also ``src_file`` (int32) and ``src_row``
+    (int64): the file (an index into ``paths``) and the row there that every merged row's key columns come from; ``line_off`` is then
+    that row's offset in ITS file's body; ``bodies`` / ``seps``: per file."""
+
+    chr_keys = name_hash = key_class = key_status = src_file = src_row = paths = bodies = seps = None
 
     def __init__(self, info, ints=None, dist=None, scores=None, line_off=None, score_names=None, path=None):
         self.info, self.ints, self.dist, self.scores, self.line_off = info, ints, dist, scores, line_off
@@ -686,10 +739,11 @@ class HipContext:
         d = dict(zip(PEAKS_INFO, info))
         return Peaks(d) if d["status"] else Peaks(d, ints, dist, scores, line_off)
 
-    def read_peaks(self, path, targetColumns):
+    def read_peaks(self, path, targetColumns, text_keys=False):
         """fread(peakFile)[, c(1:11, sel)] on the device (chicdiff_hip_peaks_read_dev): header on the host, the body uploaded as bytes
         and parsed there -> ``Peaks`` (its tensors are copies of the context's columns).  ``status`` != 0: the caller reads the file
-        some other way.  A header the rule refuses or a malformed row raises."""
+        some other way.  A header the rule refuses or a malformed row raises.  ``text_keys=True``: the sort keys of the four text
+        columns are taken from the body while it is still on the device (chicdiff_hip_peaks_textkeys_dev), for ``merge_peaks``."""
         targets = list(targetColumns)
         info = (C.c_int64 * len(PEAKS_INFO))()
         st = (C.c_int32 * max(len(targets), 1))()
@@ -702,7 +756,63 @@ class HipContext:
         if d["nrows"]:
             self._check(self.lib.chicdiff_hip_peaks_columns_dev(self.h, ints.data_ptr(), dist.data_ptr(), scores.data_ptr(), line_off.data_ptr(),
                                                                 d["nrows"]))
-        return Peaks(d, ints, dist, scores, line_off, score_names=names, path=path)
+        pk = Peaks(d, ints, dist, scores, line_off, score_names=names, path=path)
+        if text_keys:
+            self.peaks_text_keys(pk)
+        return pk
+
+    def peaks_text_keys(self, pk):
+        """The sort keys of the four text columns of ``pk``, the ``Peaks`` of the ``read_peaks`` that came LAST on this context, taken
+        from its body while that is still on the device (chicdiff_hip_peaks_textkeys_dev): sets ``chr_keys``, ``name_hash``,
+        ``key_class``, ``key_status``."""
+        torch = self.torch
+        pk.chr_keys, pk.name_hash = (torch.empty((2, pk.n), dtype=torch.int64, device=self.device) for _ in range(2))
+        ki = (C.c_int64 * 4)()
+        self._check(self.lib.chicdiff_hip_peaks_textkeys_dev(self.h, pk.chr_keys.data_ptr(), pk.name_hash.data_ptr(), pk.n, ki))
+        if ki[3] != pk.n:
+            raise ChicdiffHipError("peaks_text_keys: another file was read on this context since")
+        pk.key_status, pk.key_class = ki[0], (ki[1], ki[2])
+        return pk
+
+    def merge_peaks(self, peaks):
+        """.multimerge (chicdiff.R:218-228, 234-236) of the ``Peaks`` of ``read_peaks(text_keys=True)``, one per file, in the files'
+        order (chicdiff_hip_peaks_merge_dev; the rule stands above chicdiff_hip_peaks_textkeys_dev in include/chicdiff_hip.h) -> one
+        ``Peaks`` in the pandas twin's row order, its score rows file after file, plus ``src_file`` / ``src_row`` / ``paths``.
+        ``status`` != 0 (PEAKS_ST_MERGE_*): the device declined and no column is held.  The caller has checked that the files'
+        chromosome columns have one class."""
+        torch = self.torch
+        peaks = list(peaks)
+        F = len(peaks)
+        if not 2 <= F <= PEAKS_MERGE_MAX_FILES:
+            raise ValueError(f"merge_peaks: 2 .. {PEAKS_MERGE_MAX_FILES} files")
+        if any(p.status or p.ints is None or p.chr_keys is None for p in peaks):
+            raise ValueError("merge_peaks: every file comes from read_peaks(text_keys=True) with status 0")
+        keep = [(p.ints.contiguous(), p.dist.contiguous(), p.scores.contiguous(), p.chr_keys.contiguous(), p.name_hash.contiguous()) for p in peaks]
+        arr = lambda k: (C.c_void_p * F)(*[t[k].data_ptr() if t[k].numel() else None for t in keep])
+        nrows, nsc = (C.c_int64 * F)(*[p.n for p in peaks]), (C.c_int32 * F)(*[p.nscore for p in peaks])
+        N, T = sum(p.n for p in peaks), sum(p.nscore for p in peaks)
+        ints, dist, scores, _ = self._peaks_empty(N, T)
+        src_file, src_row = torch.empty(N, dtype=torch.int32, device=self.device), torch.empty(N, dtype=torch.int64, device=self.device)
+        info = (C.c_int64 * 2)()
+        self._check(self.lib.chicdiff_hip_peaks_merge_dev(self.h, F, arr(0), arr(1), arr(2), arr(3), arr(4), nrows, nsc, N, ints.data_ptr(),
+                                                          dist.data_ptr(), scores.data_ptr(), src_file.data_ptr(), src_row.data_ptr(), info))
+        n = info[0]
+        d = dict(zip(PEAKS_INFO, [0] * len(PEAKS_INFO)))
+        d.update(nrows=n, status=info[1], maxbait=max(p.maxbait for p in peaks), nscore=T, bad=-1)
+        names = [c for p in peaks for c in p.score_names]
+        if d["status"]:
+            out = Peaks(d, score_names=names)
+        else:
+            src_file, src_row = src_file[:n], src_row[:n]
+            line_off = torch.empty(n, dtype=torch.int64, device=self.device)
+            for f, p in enumerate(peaks):                                      # every merged row's line in its own file's body
+                m = src_file == f
+                line_off[m] = p.line_off[src_row[m]]
+            out = Peaks(d, ints[:, :n], dist[:n], scores[:, :n], line_off, score_names=names)
+            out.src_file, out.src_row = src_file, src_row
+        out.paths = [p.path for p in peaks]
+        out.bodies, out.seps = [p.info["body"] for p in peaks], [p.info["sep"] for p in peaks]
+        return out
 
     def filter_peaks(self, peaks, score, cond_of_col, replicate_rule):
         """The four filters of readAndFilterPeakMatrix (chicdiff.R:246-270) on a ``Peaks``: ``cond_of_col[j]`` = the condition (0-based,

@@ -68,9 +68,11 @@ class PeakMatrix(dict):
     the host reader's frame: the text columns are always strings (pandas makes ``baitChr = 19`` an int64); a score column that
     holds only integer tokens is float64; and ``dist`` and the scores are ``float(token)``, which the pandas reader's are not for
     tokens of 16 or 17 significant digits (a few units in the last place; tests/test_peaks.py has the measurement) — a row whose score
-    lies that close to the threshold can be kept by one path and not by the other.  Otherwise the values are equal.  ``frame``: set when the host reader served the call (fallback)."""
+    lies that close to the threshold can be kept by one path and not by the other.  Otherwise the values are equal.  ``frame``: set when the host reader served the call (fallback).
+    Several files merged on the device (``device_merge=True``): ``src_file`` (int32) names, per kept row, the entry of ``paths`` /
+    ``bodies`` / ``seps`` whose file the text columns are cut from, and ``line_off`` counts in that file's body."""
 
-    path = body = sep = frame = None
+    path = body = sep = frame = paths = bodies = seps = None
     score_names = ()
 
     def to_frame(self):
@@ -78,7 +80,14 @@ class PeakMatrix(dict):
         if self.frame is not None:
             return self.frame
         host = {k: v.cpu().numpy() for k, v in self.items()}
-        text = _peak_text_columns(self.path, self.body, self.sep, host["line_off"])
+        if self.paths is not None:
+            text = {PEAK_KEY_COLUMNS[k]: np.empty(len(host["line_off"]), dtype=object) for k in PEAK_TEXT_FIELDS}
+            for f, path in enumerate(self.paths):
+                m = host["src_file"] == f
+                for k, v in _peak_text_columns(path, self.bodies[f], self.seps[f], host["line_off"][m]).items():
+                    text[k][m] = v
+        else:
+            text = _peak_text_columns(self.path, self.body, self.sep, host["line_off"])
         cols = {k: (text[k] if k in text else host[k]) for k in PEAK_KEY_COLUMNS}
         cols.update({k: host[k] for k in self.score_names})
         return pd.DataFrame(cols)
@@ -114,15 +123,69 @@ def _read_peaks_dev(ctx, peakFiles, targetColumns):
     return pk, None
 
 
-def readAndFilterPeakMatrix(peakFiles, targetColumns, chicagoData, conditions, score, outprefix="", ctx=None, device=False):
+def _merge_peaks_dev(ctx, files, targetColumns):
+    """Several peak files through HipContext.read_peaks(text_keys=True) and merge_peaks -> (Peaks, None), or (None, why the device
+    path does not serve this call).  The conditions stand above chicdiff_hip_peaks_textkeys_dev in include/chicdiff_hip.h."""
+    from . import hip
+    targets = list(targetColumns)
+    if len(files) > hip.PEAKS_MERGE_MAX_FILES:
+        return None, f"more than {hip.PEAKS_MERGE_MAX_FILES} peak files"
+    has = []
+    for f in files:
+        try:
+            names, _ = hip.peaks_header(f)
+        except ValueError as e:
+            return None, str(e)
+        has.append([t for t in targets if t in names[11:]])
+    if not all(any(t in h for h in has) for t in targets):
+        raise ValueError("All specified targetColumns must be present in the peak file(s)")
+    if any(sum(t in h for h in has) > 1 for t in targets):
+        return None, "a target column appears in two peak files"
+    if sum(len(h) for h in has) > hip.peaks_caps()["max_scores"]:
+        return None, "more score columns than the device reader takes"
+    pks = []
+    for f, h in zip(files, has):
+        pk = ctx.read_peaks(f, h, text_keys=True)                                # the keys before the next read overwrites the text
+        if pk.status & hip.PEAKS_ST_QUOTE:
+            return None, "a file holds a quoted field"
+        if pk.status:
+            return None, "more decimal tokens than the slow-token list holds need the host's strtod"
+        if pk.n == 0:
+            return None, "a peak file without rows"
+        if pk.key_status & hip.PEAKS_ST_CHR_LONG:
+            return None, "a chromosome name of more than 8 bytes"
+        if pk.key_status:
+            return None, "a chromosome token that is neither a plain integer nor text"
+        pks.append(pk)
+    is_int = [tuple(c == hip.PEAKS_KEY_INT for c in pk.key_class) for pk in pks]
+    if any(c != is_int[0] for c in is_int):
+        return None, "a chromosome column is integer in one file and text in another"
+    m = ctx.merge_peaks(pks)
+    if m.status & hip.PEAKS_ST_MERGE_DUPLICATE:
+        return None, "a key occurs twice in one peak file"
+    if m.status & hip.PEAKS_ST_MERGE_NAME:
+        return None, "rows that share a key differ in baitName or oeName"
+    if m.status:
+        return None, "rows that share a key differ in dist"
+    return m, None
+
+
+def readAndFilterPeakMatrix(peakFiles, targetColumns, chicagoData, conditions, score, outprefix="", ctx=None, device=False,
+                            device_merge=False):
     """``device=True`` (needs ``ctx``): the file is parsed and filtered on the device (HipContext.read_peaks / filter_peaks; the rule
     stands above chicdiff_hip_peaks_parse_dev in include/chicdiff_hip.h) and a ``PeakMatrix`` comes back; ``_filteredBaits.txt`` is
     written as below.  More than one peak file, a quoted field, or too many tokens for the slow-token list: one message, and the host
-    reader below serves the call (the PeakMatrix then carries its frame)."""
+    reader below serves the call (the PeakMatrix then carries its frame).  ``device_merge=True`` (with ``device=True``): more than
+    one peak file is read, merged (.multimerge, chicdiff.R:218-228, 234-236) and filtered on the device (HipContext.merge_peaks); where
+    the device declines (_merge_peaks_dev has the list), one message and the host reader, as above."""
     if device:
         if ctx is None:
             raise ValueError("readAndFilterPeakMatrix(device=True) needs an open HipContext as ctx")
-        pk, why = _read_peaks_dev(ctx, peakFiles, targetColumns)
+        files = [peakFiles] if isinstance(peakFiles, str) else list(peakFiles)
+        if device_merge and len(files) > 1:
+            pk, why = _merge_peaks_dev(ctx, files, targetColumns)
+        else:
+            pk, why = _read_peaks_dev(ctx, peakFiles, targetColumns)
         if pk is None:
             message("readAndFilterPeakMatrix: ", why, ": reading the peak matrix on the host")
             x = readAndFilterPeakMatrix(peakFiles, targetColumns, chicagoData, conditions, score, outprefix)
@@ -143,6 +206,9 @@ def readAndFilterPeakMatrix(peakFiles, targetColumns, chicagoData, conditions, s
             pm[name] = sc[j]
         pm["line_off"] = pk.line_off[kept]
         pm.path, pm.body, pm.sep, pm.score_names = pk.path, pk.info["body"], pk.info["sep"], list(pk.score_names)
+        if pk.src_file is not None:                                              # merged: the text columns come from several files
+            pm["src_file"] = pk.src_file[kept]
+            pm.paths, pm.bodies, pm.seps = list(pk.paths), list(pk.bodies), list(pk.seps)
         return pm
     import pandas as pd
 
@@ -207,13 +273,14 @@ def _expand(ctx, baitID, oeID, RUexpand, rmap):
     return ru
 
 
-def getRegionUniverse(chicdiff_settings, ctx, suffix="", device_peaks=False):
+def getRegionUniverse(chicdiff_settings, ctx, suffix="", device_peaks=False, device_merge=False):
     """chicdiff.R:369-426 (window mode): peaks -> regions; the expansion, the clip to the map and the cis filter run on
     the device (chicdiff_hip_region_universe_*).  ``device_peaks=True``: the peak matrix is read and filtered on the device too
-    (readAndFilterPeakMatrix(device=True)) and its baitID / oeID reach the expansion as device tensors — the same RU."""
+    (readAndFilterPeakMatrix(device=True)) and its baitID / oeID reach the expansion as device tensors — the same RU.
+    ``device_merge``: passed to readAndFilterPeakMatrix (several peak files merged on the device)."""
     s = asChicdiffSettings(chicdiff_settings)
     x = readAndFilterPeakMatrix(s["peakfiles"], s["targetColumns"], s["chicagoData"], list(s["chicagoData"]), s["score"],
-                                s["outprefix"], ctx=ctx, device=device_peaks)
+                                s["outprefix"], ctx=ctx, device=device_peaks, device_merge=device_merge)
     if device_peaks:
         ru = _expand(ctx, x["baitID"], x["oeID"], s["RUexpand"], _read_rmap(s["rmapfile"]))
     else:
@@ -652,10 +719,10 @@ def IHWcorrection(chicdiff_settings, DESeqOut, FullRegionData, DESeqOutControl, 
 
 
 def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, rng=None, assemble=False, control_seed=None,
-                     device_peaks=False):
+                     device_peaks=False, device_merge=False):
     """chicdiff.R:301-347, same stage order and messages.  ``assemble``: passed to getFullRegionData.  ``control_seed``: the control
     regions are drawn on the device from this seed (getControlRegionUniverse(seed=...)) instead of on the host from ``rng``, which
-    then serves IHWcorrection's columns alone.  ``device_peaks``: passed to getRegionUniverse."""
+    then serves IHWcorrection's columns alone.  ``device_peaks``, ``device_merge``: passed to getRegionUniverse."""
     from . import hip
     from .settings import hipDevice
     own = ctx is None
@@ -664,7 +731,7 @@ def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, r
     try:
         s = asChicdiffSettings(chicdiff_settings)
         message("\n*** Running getRegionUniverse\n")
-        RU = getRegionUniverse(chicdiff_settings, ctx, device_peaks=device_peaks)
+        RU = getRegionUniverse(chicdiff_settings, ctx, device_peaks=device_peaks, device_merge=device_merge)
         message("\n*** Running getControlRegionUniverse\n")
         RUcontrol = getControlRegionUniverse(chicdiff_settings, RU, ctx, rng=rng if control_seed is None else None, seed=control_seed)
         message("\n*** Running getFullRegionData\n")

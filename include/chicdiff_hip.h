@@ -392,7 +392,8 @@ int chicdiff_hip_chinput_caps(int32_t *tile_bytes, int32_t *lane_bytes, int32_t 
 #define CHICDIFF_PEAKS_INFO_NFILTERED 9  /* _selftest_peaks: baits without a kept row */
 #define CHICDIFF_PEAKS_INFO_WORDS 10
 /* readAndFilterPeakMatrix (chicdiff.R:218-277) on the device, opt-in: x <- fread(peakFiles); x[, c(1:11, sel)] (:231-244); the four
- * filters (:246-270); filtered baits (:240, :271).  One peak file; .multimerge (:223-229) stays host code.  The rule, in full:
+ * filters (:246-270); filtered baits (:240, :271).  One peak file per read; .multimerge (:223-229) is
+ * chicdiff_hip_peaks_merge_dev, further down.  The rule, in full:
  *
  *   header     read on the HOST.  Leading '#' lines are skipped; the next line is the header, one trailing '\r' dropped.  The separator
  *              is ONE byte for the whole file: a tab if the header line holds a tab, else a comma if it holds a comma, else a blank.
@@ -458,6 +459,81 @@ int chicdiff_hip_peaks_filter_dev(chicdiff_hip_ctx *ctx, const int32_t *d_bait, 
                                   int32_t ncond, int32_t replicate_rule, int64_t maxbait, int64_t *d_kept_idx, int32_t *d_kept_bait,
                                   int32_t *d_kept_oe, int32_t *d_filtered, int64_t *nkept_host, int64_t *nfiltered_host);
 int chicdiff_hip_peaks_caps(int32_t *tile_bytes, int32_t *window_bytes, int32_t *max_scores, int32_t *max_slow);
+
+/* .multimerge on the device, opt-in (chicdiff.R:218-228, 234-236): peakfiles names F >= 2 files and the reference joins them with
+ * Reduce(merge(..., all = TRUE)) on the eleven key columns.  The twin is pandas' x.merge(y, on = the 11 keys, how = "outer"), left to
+ * right.  Words and limits: */
+#define CHICDIFF_PEAKS_MERGE_MAX_FILES 16
+#define CHICDIFF_PEAKS_ST_CHR_LONG 4          /* status bit: a text chromosome token over 8 bytes (or a 9-digit number in a text column) */
+#define CHICDIFF_PEAKS_ST_CHR_AMBIGUOUS 8     /* status bit: a chromosome token that is neither a plain integer nor text */
+#define CHICDIFF_PEAKS_ST_MERGE_DUPLICATE 16  /* status bit: two rows of one file share their eight words */
+#define CHICDIFF_PEAKS_ST_MERGE_NAME 32       /* status bit: rows that share a bait (a key) differ in baitName (oeName) */
+#define CHICDIFF_PEAKS_ST_MERGE_DIST 64       /* status bit: rows that share their eight words differ in dist */
+#define CHICDIFF_PEAKS_KEY_INT 0              /* a chromosome column's class: every row a plain integer (pandas: int64) */
+#define CHICDIFF_PEAKS_KEY_TEXT 1             /* every row text (pandas: object) */
+#define CHICDIFF_PEAKS_KEY_MIXED 2            /* plain integers and text: object for pandas too, ordered as strings like TEXT */
+#define CHICDIFF_PEAKS_TEXTKEYS_STATUS 0      /* info[] of _textkeys_dev / _selftest_peaks_textkeys: CHICDIFF_PEAKS_ST_CHR_* bits */
+#define CHICDIFF_PEAKS_TEXTKEYS_CLASS_BAIT 1  /* class of baitChr */
+#define CHICDIFF_PEAKS_TEXTKEYS_CLASS_OE 2    /* class of oeChr */
+#define CHICDIFF_PEAKS_TEXTKEYS_NROWS 3
+#define CHICDIFF_PEAKS_TEXTKEYS_WORDS 4
+#define CHICDIFF_PEAKS_MERGE_NOUT 0           /* info[] of _merge_dev: rows of the merged table */
+#define CHICDIFF_PEAKS_MERGE_STATUS 1         /* CHICDIFF_PEAKS_ST_MERGE_* bits; non-zero: the merged table must not be used */
+#define CHICDIFF_PEAKS_MERGE_WORDS 2
+/* The rule, in full.
+ *
+ *   twin's order   pandas returns the outer join ordered lexicographically by the eleven key columns; regionID is the row number of
+ *                  the filtered table (:393), so the order is part of the result.  A baitChr / oeChr column that pandas types object
+ *                  orders as strings ("10" < "2" < "X"), one it types int64 numerically; int64 in one file against object in another
+ *                  raises.  NA dist keys (trans rows) match each other.  Two rows of one file with one key give a Cartesian product.
+ *   eight words    (chr(baitChr), baitStart, baitEnd, baitID, chr(oeChr), oeStart, oeEnd, oeID).  If no two rows that agree in them
+ *                  differ in baitName, oeName or dist, and no two rows that agree in the first four differ in baitName, the twin's
+ *                  order is the order of these words.  The device sorts on exactly them, checks the condition, and reports a status
+ *                  bit where it fails: the caller then reads the files some other way.
+ *   chr()          a chromosome token is one of
+ *                    plain integer  0|[1-9][0-9]{0,8}; the key is its value.
+ *                    text           1 .. 8 bytes, every byte ASCII, at least one byte outside 0-9 + - . e E and blank, not one of
+ *                                   pandas' NA spellings ('' #N/A '#N/A N/A' #NA -1.#IND -1.#QNAN -NaN -nan 1.#IND 1.#QNAN <NA> N/A NA
+ *                                   NULL NaN None n/a nan null), not [+-]?(inf|infinity) in any letter case; the key is the bytes
+ *                                   packed big-endian, zero-padded, the top bit flipped: signed int64 order is byte order.
+ *                    anything else  CHICDIFF_PEAKS_ST_CHR_LONG for a token over 8 bytes that is text otherwise,
+ *                                   CHICDIFF_PEAKS_ST_CHR_AMBIGUOUS for the rest (01, +1, 1.0, 1e5, inf, an NA spelling, a non-ASCII
+ *                                   byte, ten or more digits).
+ *                  A column's class follows its rows: all plain integers INT; else TEXT or MIXED, and then EVERY row's key is its
+ *                  bytes (['1', '2L'] is object for pandas), which a 9-digit number does not fit: CHR_LONG.
+ *   names          baitName and oeName enter as 64-bit FNV-1a hashes of the field's bytes.  Equal bytes give equal hashes; unequal
+ *                  bytes give equal hashes with probability 2^-64 per pair, and such a pair would pass as one name.
+ *   groups         rows are concatenated file-major and a permutation is sorted by the eight words with stable radix passes, so a
+ *                  group's members stand in file order.  A sorted row opens a group when any word differs from its predecessor's.
+ *                  Inside a group: two rows of one file DUPLICATE, unequal oeName hashes NAME, unequal dist DIST (NaN equals NaN,
+ *                  +0 equals -0).  Along a run of equal (chr(baitChr), baitStart, baitEnd, baitID): unequal baitName hashes NAME.
+ *   output         one row per group, in sorted order: the six ints and dist of the group's first member, src_file / src_row of that
+ *                  member (the text columns are cut from that file), and the (sum T_f, n_out) score matrix: file f's score rows at
+ *                  sum_{g < f} T_g, NaN where file f has no such key — the twin's column order.
+ *
+ * _textkeys_dev works on the body of the last successful _read_dev of this context, still in the context's text buffer (any other
+ * read through the context in between: CHICDIFF_E_INVALID).  One lane per row walks fields 0 .. 9 from the row's line offset.
+ * d_chr (2, cap) int64: chr(baitChr), chr(oeChr) in the form of each column's class; d_name (2, cap): the hashes of baitName, oeName;
+ * cap >= the rows of that read.  info (host): the words above.  One host stop (the flag words).
+ * _merge_dev: nfiles in 2 .. CHICDIFF_PEAKS_MERGE_MAX_FILES; per file (host arrays of device pointers) d_ints (6, n_f) int32, d_dist
+ * (n_f), d_scores (T_f, n_f), d_chr and d_name (2, n_f) as above, all contiguous; nrows[f] = n_f >= 0, nscores[f] = T_f >= 0, sum T_f <=
+ * CHICDIFF_PEAKS_MAX_SCORES, sum n_f < 2^31.  The caller has made sure that every file's columns have one class (INT everywhere, or
+ * TEXT / MIXED everywhere).  Outputs (device, cap >= sum n_f columns each): d_out_ints (6, cap), d_out_dist (cap), d_out_scores (sum
+ * T_f, cap), d_src_file (cap) int32, d_src_row (cap) int64; the first info[NOUT] columns are written.  One host stop.  The result
+ * does not depend on the launch shape: no value passes through an atomic, only status bits do.
+ * _header (host only, no context): the header of a file through the same function as _read_dev's, without targets: the column names
+ * joined by '\n' into names (namecap bytes, NUL-terminated), *ncols their number, *sep the separator byte.  A file whose first 11
+ * columns are not the key columns is refused with that function's message in err. */
+int chicdiff_hip_peaks_textkeys_dev(chicdiff_hip_ctx *ctx, int64_t *d_chr, int64_t *d_name, int64_t cap, int64_t *info);
+int chicdiff_hip_peaks_merge_dev(chicdiff_hip_ctx *ctx, int32_t nfiles, const int32_t *const *d_ints, const double *const *d_dist,
+                                 const double *const *d_scores, const int64_t *const *d_chr, const int64_t *const *d_name,
+                                 const int64_t *nrows, const int32_t *nscores, int64_t cap, int32_t *d_out_ints, double *d_out_dist,
+                                 double *d_out_scores, int32_t *d_src_file, int64_t *d_src_row, int64_t *info);
+int chicdiff_hip_peaks_header(const char *path, char *names, int32_t namecap, int32_t *ncols, int32_t *sep, char *err, int32_t errcap);
+/* _selftest_peaks_textkeys (host only, no context): the host statement of the text-key rule on a file — header as above, the body
+ * parsed by the host statement of the parse rule (no targets), then chr (2, cap) and name (2, cap) as _textkeys_dev gives them, for the
+ * first min(nrows, cap) rows; info as for _textkeys_dev.  cap = 0: the row count alone. */
+int chicdiff_hip_selftest_peaks_textkeys(const char *path, int64_t cap, int64_t *chr, int64_t *name, int64_t *info, char *err, int32_t errcap);
 
 /* f1/f3 — p.adjust(p, method = "BH") (DESeq2 results() on the independent-filtering survivors; chicdiff.R:2049
  * on the weighted p-values).  NaN = NA: not counted, stays NaN.  n < 2^32. */
