@@ -435,5 +435,31 @@ struct ObjectiveProbe {
 };
 int launch_objective_probe(FitDims d, FitWork w, Opts o, const ObjectiveProbe &pb, hipStream_t st);
 void launch_pvalues(const double *stat, int64_t n, double *p, hipStream_t st);
+// table_text_kernels.hip — a table of device columns as text (the rule: include/chicdiff_hip.h, above chicdiff_hip_table_text_dev).
+// The descriptors travel as a kernel argument (2 KiB): every lane reads the same one, through the scalar cache.
+struct TtCol {
+    const void *data;           // device: n values of the column's kind; CHICDIFF_COL_DICT: n int32 codes, or NULL = entry 0 for every row
+    const int32_t *dict_off;    // device: ndict + 1 offsets into dict_bytes
+    const uint8_t *dict_bytes;  // device
+    int32_t kind, ndict;
+};
+struct TtCols {
+    int32_t ncol, sep;
+    TtCol col[CHICDIFF_TABLE_MAX_COLUMNS];
+};
+// what the host reads back after the length pass and the scan
+struct TtResult {
+    int64_t nbytes;    // bytes of the whole text (written by the scan: the last tile's end)
+    int32_t bad_code;  // != 0: a dictionary code >= the number of entries was met (it is written as an empty cell)
+    int32_t _pad;
+};
+size_t table_text_workspace_bytes(int64_t n);
+// _len: the length pass, _scan: the scan of the tile totals (n >= 1), enqueued on st; *res_out (inside ws) is valid once st has been
+// synchronised after both.
+// _write: the write pass; `out` has room for the nbytes the length pass found.
+int launch_table_text_len(const TtCols &t, int64_t n, char *ws, hipStream_t st, const TtResult **res_out);
+int launch_table_text_scan(int64_t n, char *ws, hipStream_t st);
+void launch_table_text_write(const TtCols &t, int64_t n, uint8_t *out, char *ws, hipStream_t st);
+void launch_format_double_selftest(const double *x, int64_t n, uint8_t *text, int32_t *len, hipStream_t st);
 
 }  // namespace cd

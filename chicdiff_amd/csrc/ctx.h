@@ -1,4 +1,4 @@
-// ctx.h — what the host sources of include/chicdiff_hip.h share (ctx.hip, fit_api.hip, stage_api.hip, text_api.hip, selftest_api.hip):
+// ctx.h — what the host sources of include/chicdiff_hip.h share (ctx.hip, fit_api.hip, stage_api.hip, text_api.hip, table_api.hip, selftest_api.hip):
 // the context, its options and timers, and the helpers that more than one of them calls.  Host translation units only: no
 // *_kernels.hip file and no header that one of them includes may include it.
 #pragma once
@@ -47,6 +47,7 @@ struct HostOpts {
     // overflow.  Each verdict is all-reduced, so every rank of a sharded fit must re-enter together.
     int fault_inject = 0;
     int region_assemble_generic = 0;  // test option: every tile of region_assemble takes the generic path
+    int table_write_half_kib = 0;  // test handle: bytes (KiB) of one half of the pinned area in chicdiff_hip_table_write_dev (0: up to 64 MiB)
     int chicago_tables_run_merge = 1;  // chicago_tables: runs of rows with one slot are merged inside the wave before the global atomic
 };
 
@@ -92,6 +93,9 @@ struct chicdiff_hip_ctx {
     // while chin_text still holds the body of that read (chicdiff_hip_peaks_textkeys_dev walks it): its length and separator
     int64_t pk_text_bytes = -1;
     int pk_sep = 0;
+    // chicdiff_hip_table_write_dev: the table's text on the device (grow-only); it leaves through chin_pin / chin_ev
+    char *tt_text = nullptr;
+    size_t tt_text_bytes = 0;
     // host-buffer entry point: columns that are final once the MAP dispersions exist leave for the host on a second
     // stream while the Wald stage runs (set for the duration of one chicdiff_hip_nbglm_fit call)
     struct EarlyCopy {

@@ -81,6 +81,7 @@ static const OptionDef kOptions[] = {
     {"prep_blocks", nullptr, &HostOpts::prep_blocks, 0, kRedBlocks, 1, 0},
     {"region_assemble_generic", nullptr, &HostOpts::region_assemble_generic, 0, 1, 1, 0},
     {"chicago_tables_run_merge", nullptr, &HostOpts::chicago_tables_run_merge, 0, 1, 1, 0},
+    {"table_write_half_kib", nullptr, &HostOpts::table_write_half_kib, 0, 65536, 1, 3},  // 0 (64 MiB at most) or 4 .. 65536
     {"fault_inject", nullptr, &HostOpts::fault_inject, 0, 7, 1, 0},
     {"bench_fake_world", nullptr, &HostOpts::bench_fake_world, 0, kGatherMaxWorld, 1, 0},
     {"local_trend_substitute", nullptr, &HostOpts::local_trend_substitute, 0, 1, 1, 0},
@@ -150,6 +151,7 @@ void chicdiff_hip_destroy(chicdiff_hip_ctx *c) {
     if (c->chin_text) (void)hipFree(c->chin_text);
     if (c->chin_cols) (void)hipFree(c->chin_cols);
     if (c->pk_buf) (void)hipFree(c->pk_buf);
+    if (c->tt_text) (void)hipFree(c->tt_text);
     if (c->chin_pin) (void)hipHostFree(c->chin_pin);
     for (hipEvent_t e : c->chin_ev)
         if (e) (void)hipEventDestroy(e);

@@ -29,6 +29,8 @@ EXPORTS = [
     "chicdiff_hip_region_universe_count_dev", "chicdiff_hip_region_universe_fill_dev", "chicdiff_hip_region_universe_dev", "chicdiff_hip_count_table_dev",
     "chicdiff_hip_candidate_interactions_dev", "chicdiff_hip_candidate_interactions_method_dev", "chicdiff_hip_selftest_landau_dev", "chicdiff_hip_chicago_tables_dev", "chicdiff_hip_chicago_tables_caps",
     "chicdiff_hip_control_draws_dev", "chicdiff_hip_countput_dev", "chicdiff_hip_countput_caps",
+    "chicdiff_hip_table_check", "chicdiff_hip_table_text_dev", "chicdiff_hip_table_write_dev", "chicdiff_hip_table_text_caps",
+    "chicdiff_hip_selftest_format_double_dev", "chicdiff_hip_selftest_format_double",
     "chicdiff_hip_chinput_read", "chicdiff_hip_chinput_table_dev", "chicdiff_hip_region_avdist_dev",
     "chicdiff_hip_chinput_parse_dev", "chicdiff_hip_chinput_read_dev", "chicdiff_hip_chinput_caps",
     "chicdiff_hip_peaks_parse_dev", "chicdiff_hip_peaks_read_dev", "chicdiff_hip_peaks_columns_dev", "chicdiff_hip_peaks_filter_dev",
@@ -69,6 +71,11 @@ class Scalars(C.Structure):
 class ResultsInfo(C.Structure):
     _fields_ = [("filterThreshold", C.c_double), ("filterTheta", C.c_double), ("alpha", C.c_double), ("index", C.c_int32),
                 ("_pad", C.c_int32), ("theta", C.c_double * 50), ("numRej", C.c_double * 50), ("lowess", C.c_double * 50)]
+
+
+class TableColumn(C.Structure):
+    """chicdiff_table_column (include/chicdiff_hip.h)."""
+    _fields_ = [("kind", C.c_int32), ("ndict", C.c_int32), ("d_data", C.c_void_p), ("dict_off", C.c_void_p), ("dict_bytes", C.c_void_p)]
 
 
 class KernelTime(C.Structure):
@@ -171,6 +178,12 @@ def load_library() -> C.CDLL:
                                                  vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
     L.chicdiff_hip_countput_dev.argtypes = [vp, i32] + [C.POINTER(vp)] * 6 + [C.POINTER(i64), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
     L.chicdiff_hip_countput_caps.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.chicdiff_hip_table_check.argtypes = [C.POINTER(TableColumn), i32, i64, i32, C.c_char_p, i32]
+    L.chicdiff_hip_table_text_dev.argtypes = [vp, C.POINTER(TableColumn), i32, i64, i32, vp, i64, C.POINTER(i64)]
+    L.chicdiff_hip_table_write_dev.argtypes = [vp, C.c_char_p, i32, C.c_char_p, i64, C.POINTER(TableColumn), i32, i64, i32, C.POINTER(i64)]
+    L.chicdiff_hip_table_text_caps.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.chicdiff_hip_selftest_format_double_dev.argtypes = [vp, vp, i64, vp, vp]
+    L.chicdiff_hip_selftest_format_double.argtypes = [vp, i64, vp, vp]
     L.chicdiff_hip_nbglm_fit_dev.argtypes = [vp, vp, vp, i64, i32, C.POINTER(i32), C.POINTER(Opts), C.POINTER(Out),
                                              C.POINTER(Scalars)]
     L.chicdiff_hip_nbglm_fit.argtypes = L.chicdiff_hip_nbglm_fit_dev.argtypes
@@ -215,6 +228,102 @@ def countput_caps() -> dict:
     m, k, r = C.c_int32(0), C.c_int32(0), C.c_int32(0)
     load_library().chicdiff_hip_countput_caps(C.byref(m), C.byref(k), C.byref(r))
     return dict(max_rep=m.value, key_rows_per_workgroup=k.value, reduce_rows_per_workgroup=r.value)
+
+
+# include/chicdiff_hip.h, CHICDIFF_COL_* / CHICDIFF_TABLE_*
+COL_INT32, COL_INT64, COL_FLOAT64, COL_DICT = 0, 1, 2, 3
+TABLE_MAX_CELL_BYTES = 24
+
+
+def table_text_caps() -> dict:
+    """The limits of ``HipContext.table_text`` / ``write_table`` as the library was built (include/chicdiff_hip.h, CHICDIFF_TABLE_*): the
+    rows a workgroup takes, the bytes of text it stages in LDS at a time, the most columns and the most entries of a dictionary."""
+    r, b, c, d = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    load_library().chicdiff_hip_table_text_caps(C.byref(r), C.byref(b), C.byref(c), C.byref(d))
+    return dict(rows_per_tile=r.value, lds_bytes=b.value, max_columns=c.value, max_dict=d.value)
+
+
+def _format_double_cells(text, length):
+    return [text[i, :k].tobytes() for i, k in enumerate(length.tolist())]
+
+
+def selftest_format_double(x):
+    """The library's double -> text function compiled for the HOST (chicdiff_hip_selftest_format_double: no device, no context) on
+    an array of float64: the list of the cells as bytes — repr(float), nothing for NaN."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    text, length = np.zeros((len(x), TABLE_MAX_CELL_BYTES), dtype=np.uint8), np.zeros(len(x), dtype=np.int32)
+    rc = load_library().chicdiff_hip_selftest_format_double(x.ctypes.data, len(x), text.ctypes.data, length.ctypes.data)
+    if rc:
+        raise ValueError(f"selftest_format_double: error {rc}")
+    return _format_double_cells(text, length)
+
+
+def table_columns(columns, n=None, device=None):
+    """The column descriptors of ``HipContext.table_text`` / ``write_table`` from ``columns``: a one-dimensional contiguous int32,
+    int64 or float64 tensor is a column of that kind; a pair ``(codes, entries)`` is a dictionary column — ``codes`` an int32 tensor
+    or None (entry 0 for every row), ``entries`` a sequence of bytes or str.  ``n``: the number of rows, needed where no column is a
+    tensor.  ``device``: where every tensor must live (None: not checked).  Returns (array of TableColumn, n, what the array points
+    into — to be kept alive for the call).  Anything else raises ValueError; the rule's own refusals are the library's."""
+    import torch
+    kinds = {torch.int32: COL_INT32, torch.int64: COL_INT64, torch.float64: COL_FLOAT64}
+    columns = list(columns)
+    arr = (TableColumn * max(len(columns), 1))()
+    keep = []
+
+    def tensor(name, t, dtypes):
+        nonlocal n
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: a torch tensor is required, got {type(t).__name__}")
+        if t.dtype not in dtypes:
+            raise ValueError(f"{name}: dtype {' / '.join(str(d) for d in dtypes)} is required, got {t.dtype}")
+        if device is not None and t.device != device:
+            raise ValueError(f"{name}: must be on {device}, is on {t.device}")
+        if t.dim() != 1:
+            raise ValueError(f"{name}: a one-dimensional tensor is required, got shape {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: must be contiguous")
+        if n is None:
+            n = t.numel()
+        if t.numel() != n:
+            raise ValueError(f"{name}: {n} rows are required, got {t.numel()}")
+        keep.append(t)
+        return t.data_ptr() if t.numel() else None
+
+    for j, col in enumerate(columns):
+        if isinstance(col, (tuple, list)):
+            if len(col) != 2:
+                raise ValueError(f"columns[{j}]: a dictionary column is (codes, entries)")
+            codes, entries = col
+            ent = [e.encode() if isinstance(e, str) else bytes(e) for e in entries]
+            off = np.zeros(len(ent) + 1, dtype=np.int32)
+            off[1:] = np.cumsum([len(e) for e in ent], dtype=np.int64).astype(np.int32) if ent else 0
+            blob = np.frombuffer(b"".join(ent) + b"\0", dtype=np.uint8).copy()
+            keep += [off, blob]
+            arr[j].kind, arr[j].ndict = COL_DICT, len(ent)
+            arr[j].d_data = None if codes is None else tensor(f"columns[{j}] codes", codes, (torch.int32,))
+            arr[j].dict_off, arr[j].dict_bytes = off.ctypes.data, blob.ctypes.data
+        else:
+            ptr = tensor(f"columns[{j}]", col, tuple(kinds))
+            arr[j].kind, arr[j].d_data = kinds[col.dtype], ptr
+    if n is None:
+        raise ValueError("table: the number of rows is required where no column is a tensor")
+    return arr, int(n), keep
+
+
+def _sep_byte(sep):
+    b = sep.encode() if isinstance(sep, str) else bytes(sep)
+    if len(b) != 1:
+        raise ValueError(f"table: the separator is one byte, got {sep!r}")
+    return b[0]
+
+
+def table_check(columns, sep=",", n=None):
+    """The refusals of the table rule on their own (chicdiff_hip_table_check: host only, no context, the tensors are not read): raises
+    ValueError with the library's message."""
+    arr, n, keep = table_columns(columns, n=n)
+    err = C.create_string_buffer(512)
+    if load_library().chicdiff_hip_table_check(arr, len(list(columns)), n, _sep_byte(sep), err, 512):
+        raise ValueError(err.value.decode())
 
 
 def chinput_caps() -> dict:
@@ -1092,6 +1201,48 @@ class HipContext:
         if 2 * k < n:   # (a view would pin the whole n-entry allocation)
             out = {name: t.clone() for name, t in out.items()}
         return out
+
+    # -- tables as text ---------------------------------------------------------------------------
+    def table_text(self, columns, sep=",", n=None):
+        """A table of device columns as text, what ``DataFrame.to_csv(index=False)`` writes below its header, byte for byte
+        (chicdiff_hip_table_text_dev; the rule stands above it in include/chicdiff_hip.h): a uint8 device tensor.  ``columns`` as for
+        ``table_columns``; 2 .. 64 of them."""
+        torch = self.torch
+        columns = list(columns)
+        arr, n, keep = table_columns(columns, n=n, device=self.device)
+        sepb, size = _sep_byte(sep), C.c_int64(0)
+        self._check(self.lib.chicdiff_hip_table_text_dev(self.h, arr, len(columns), n, sepb, None, 0, C.byref(size)))
+        out = torch.empty(size.value, dtype=torch.uint8, device=self.device)
+        if size.value:
+            self._check(self.lib.chicdiff_hip_table_text_dev(self.h, arr, len(columns), n, sepb, out.data_ptr(), size.value, C.byref(size)))
+        return out
+
+    def write_table(self, path, columns, header, append=False, sep=",", n=None):
+        """The same text into the file ``path`` (chicdiff_hip_table_write_dev): the line of the column names ``header`` first, unless
+        ``append`` — then the rows go behind what the file holds.  Returns the bytes written.  ``last_table_write_ms``: the call's
+        timers (len, scan, write, download) when timing is enabled."""
+        columns = list(columns)
+        arr, n, keep = table_columns(columns, n=n, device=self.device)
+        names = [str(h) for h in header]
+        if len(names) != len(columns):
+            raise ValueError(f"write_table: {len(columns)} column names are required, got {len(names)}")
+        head = (sep.join(names) + "\n").encode()
+        written = C.c_int64(0)
+        self._check(self.lib.chicdiff_hip_table_write_dev(self.h, os.fsencode(path), int(bool(append)), head, len(head), arr, len(columns), n,
+                                                          _sep_byte(sep), C.byref(written)))
+        kt = self.kernel_times()
+        self.last_table_write_ms = {k[len("table_"):]: v[0] for k, v in kt.items() if k.startswith("table_")}
+        return written.value
+
+    def selftest_format_double_dev(self, d_x):
+        """The library's double -> text function on the device (chicdiff_hip_selftest_format_double_dev): the cells as a list of bytes."""
+        torch = self.torch
+        self._check_tensor("d_x", d_x, torch.float64, (-1,))
+        n = d_x.numel()
+        text = torch.empty((n, TABLE_MAX_CELL_BYTES), dtype=torch.uint8, device=self.device)
+        length = torch.empty(n, dtype=torch.int32, device=self.device)
+        self._check(self.lib.chicdiff_hip_selftest_format_double_dev(self.h, d_x.data_ptr(), n, text.data_ptr(), length.data_ptr()))
+        return _format_double_cells(text.cpu().numpy(), length.cpu().numpy())
 
     # -- a6 + a7 ----------------------------------------------------------------------------
     def nbglm_fit(self, d_counts, d_nf, group, want=None, opts: Opts | None = None, outputs: dict | None = None):

@@ -519,12 +519,13 @@ def _countput(xs, conditions, rmap):
     return pd.concat(out, ignore_index=True)
 
 
-def countput_dev(xs, conditions, ctx, id_min, midsum, chr_codes, id_columns=None):
+def countput_dev(xs, conditions, ctx, id_min, midsum, chr_codes, id_columns=None, keep=None):
     """``_countput`` on the device (HipContext.countput, one call per condition in ``dict.fromkeys(conditions)`` order): the same
     DataFrame — columns, dtypes, row order, ``condition`` — with Nav, Bav, score and oeID_mid equal bit for bit.  ``midsum`` /
     ``chr_codes``: ``_rmap_tables``' dense per-ID tables (host arrays or device tensors); ``id_columns``: [(baitID, otherEndID)] per
     replicate as int32 device tensors, when the caller has uploaded them already.  The rule (rows kept, Kahan means in row order,
-    strict maximum, groups in order of first appearance) is above chicdiff_hip_countput_dev in include/chicdiff_hip.h."""
+    strict maximum, groups in order of first appearance) is above chicdiff_hip_countput_dev in include/chicdiff_hip.h.
+    ``keep``: a list that receives (condition, the condition's device columns) — what ``write_countput_dev`` writes."""
     import pandas as pd
     torch = ctx.torch
     dev = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, dtype=t)).to(ctx.device)
@@ -542,6 +543,8 @@ def countput_dev(xs, conditions, ctx, id_min, midsum, chr_codes, id_columns=None
                          dev(x[sc].to_numpy(np.float64), np.float64), dev(x["distSign"].to_numpy(np.float64), np.float64)))
             id_dtypes.append((x["baitID"].dtype, x["otherEndID"].dtype))
         r = ctx.countput(reps, id_min, d_midsum, d_chr)
+        if keep is not None:
+            keep.append((cond, r))
         host = {k: v.cpu().numpy() for k, v in r.items()}
         # the twin's ID dtypes: as the replicates carry them (the inner merge with the map keeps the left key column's)
         z = pd.DataFrame({"baitID": host["baitID"].astype(np.result_type(*[b for b, _ in id_dtypes])),
@@ -552,8 +555,64 @@ def countput_dev(xs, conditions, ctx, id_min, midsum, chr_codes, id_columns=None
     return pd.concat(out, ignore_index=True)
 
 
+TABLE_COLUMN_DTYPES = (np.dtype(np.int32), np.dtype(np.int64), np.dtype(np.float64))   # what HipContext.write_table takes as it stands
+
+
+def _needs_quoting(text, sep=","):
+    return any(ch in text for ch in (sep, '"', "\r", "\n"))
+
+
+def write_countput_dev(ctx, path, kept, columns):
+    """``countput.to_csv(path, index=False)`` from the device columns ``countput_dev`` kept: one ``write_table`` per condition, the
+    first with the header, the others appending; ``condition`` is a one-entry dictionary column.  Returns None, or the reason why the
+    device writer does not take this table (nothing has been written then)."""
+    if not kept:
+        return "no condition"
+    bad = [str(c) for c, _ in kept if _needs_quoting(str(c))] + [str(c) for c in columns if _needs_quoting(str(c))]
+    if bad:
+        return f"{bad[0]!r} needs quoting"
+    for k, (cond, r) in enumerate(kept):
+        cols = [r[name] for name in ("baitID", "otherEndID", "Nav", "Bav", "score", "oeID_mid")] + [(None, [str(cond)])]
+        ctx.write_table(path, cols, columns, append=k > 0, n=r["baitID"].numel())
+    return None
+
+
+def frame_columns_dev(df, ctx):
+    """The columns of a DataFrame as ``HipContext.write_table`` takes them: int32, int64 and float64 columns uploaded as they stand,
+    object columns of strings (None / NaN allowed) as dictionary columns — codes by ``pd.factorize``.  Returns (columns, None), or
+    (None, reason) where the device writer would not write what ``to_csv`` writes: another dtype, an entry or a column name that needs
+    quoting, more distinct strings than a dictionary holds, a one-column frame."""
+    import pandas as pd
+    from . import hip
+    torch = ctx.torch
+    if df.shape[1] < 2:
+        return None, "a frame of fewer than two columns"
+    caps = hip.table_text_caps()
+    if df.shape[1] > caps["max_columns"]:
+        return None, f"more than {caps['max_columns']} columns"
+    cols = []
+    for j, name in enumerate(df.columns):
+        col = df.iloc[:, j]
+        if _needs_quoting(str(name)):
+            return None, f"column name {name!r} needs quoting"
+        if col.dtype in TABLE_COLUMN_DTYPES:
+            cols.append(torch.from_numpy(np.ascontiguousarray(col.to_numpy())).to(ctx.device))
+        elif col.dtype == object:
+            codes, uniques = pd.factorize(col)
+            if not all(isinstance(u, str) for u in uniques):
+                return None, f"column {name!r} holds objects that are not strings"
+            if len(uniques) > caps["max_dict"]:
+                return None, f"column {name!r} holds more than {caps['max_dict']} distinct strings"
+            if any(_needs_quoting(u) for u in uniques):
+                return None, f"column {name!r} holds an entry that needs quoting"
+            cols.append((torch.from_numpy(codes.astype(np.int32)).to(ctx.device), list(uniques) or [""]))
+        else:
+            return None, f"column {name!r} has dtype {col.dtype}"
+    return cols, None
+
+
 def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, read_chicago=None, assemble=False, device_tables=False,
-                      device_countput=False, device_chinput=False):
+                      device_countput=False, device_chinput=False, device_write=False):
     """chicdiff.R:1460-1478 with the device path behind it: list(test block, control block, countput).  Every Chicago
     data set and every chinput file is read ONCE for both universes (what ``parallel = TRUE`` -> getFullRegionData2,
     :948-1456, does in the reference; the result does not depend on it).  The long "recast" table (one row per region,
@@ -566,7 +625,12 @@ def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, rea
     ``device_countput=True``: countput is aggregated on the device (``countput_dev``) instead of by the pandas groupby — the same frame,
     bit for bit and in the same row order.
     ``device_chinput=True``: the text of every chinput file is parsed on the device (``ctx.read_chinput(..., device=True)``) instead of
-    by host threads — the same key tables; without countData no chinput file is read and it has no effect."""
+    by host threads — the same key tables; without countData no chinput file is read and it has no effect.
+    ``device_write=True`` (with ``device_countput=True`` only): ``_countput.csv`` is formatted on the device from the aggregation's own
+    columns (``write_countput_dev``) instead of by ``to_csv`` — the same file, byte for byte; the returned frame is built as before."""
+    if device_write and not device_countput:
+        raise ValueError("getFullRegionData(device_write=True) writes the device columns of the countput aggregation: it needs "
+                         "device_countput=True")
     s = asChicdiffSettings(chicdiff_settings)
     if assemble and s["countData"] is None:
         raise ValueError("getFullRegionData(assemble=True) covers the chinput branch only: without countData the counts are "
@@ -597,11 +661,17 @@ def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, rea
         bg = background_tables(xs, id_min, nid)
     bg.update(id_min=id_min, midsum=midsum)
     message("Saving counts\n")
+    kept = [] if device_write else None
     if device_countput:
-        countput = countput_dev(xs, conditions, ctx, id_min, midsum, chr_codes, id_columns=d_ids)
+        countput = countput_dev(xs, conditions, ctx, id_min, midsum, chr_codes, id_columns=d_ids, keep=kept)
     else:
         countput = _countput(xs, conditions, rmap)
-    countput.to_csv(f"{s['outprefix']}_countput.csv", index=False)                 # the reference: saveRDS(_countput.Rds), :769
+    why = write_countput_dev(ctx, f"{s['outprefix']}_countput.csv", kept, list(countput.columns)) if device_write else ""
+    if why is not None:
+        if why:
+            message("getFullRegionData: ", why, ": writing countput on the host")
+        countput.to_csv(f"{s['outprefix']}_countput.csv", index=False)             # the reference: saveRDS(_countput.Rds), :769
+    del kept
 
     universes = [RU, RUcontrol]
     baits = np.unique(np.concatenate([u["csr_baitID"].cpu().numpy() for u in universes]))   # sort(unique(RU$baitID)), :775
@@ -677,11 +747,13 @@ def dist_lookup(ihw_df, ihw_weights):
 
 
 def IHWcorrection(chicdiff_settings, DESeqOut, FullRegionData, DESeqOutControl, FullControlRegionData, countput=None,
-                  DiagPlot=True, diffbaitPlot=True, suffix="", ctx=None, ihw=None, rng=None):
+                  DiagPlot=True, diffbaitPlot=True, suffix="", ctx=None, ihw=None, rng=None, device_write=False):
     """chicdiff.R:1956-2065.  ``ihw(pvalue, covariate, alpha)`` stands for IHW::ihw(pvalue ~ abs(avDist), data =
     out.control, alpha = 0.05) (:1994; an R package the reference calls — SURVEY.md §2 row 10) and returns
     ``(df, weights)`` = (ihwRes@df with columns covariate and group, ihwRes@weights).  The covariate comes from the
-    device blocks, the application side (:2038-2049) runs on the device; the diagnostic plots stay R."""
+    device blocks, the application side (:2038-2049) runs on the device; the diagnostic plots stay R.
+    ``device_write=True``: ``_results.csv`` is formatted on the device (``HipContext.write_table``) — the file ``to_csv`` writes, byte
+    for byte; a frame the device writer does not take (``frame_columns_dev``) gets one message and the host's ``to_csv``."""
     import pandas as pd
     s = asChicdiffSettings(chicdiff_settings)
     if ihw is None:
@@ -714,15 +786,22 @@ def IHWcorrection(chicdiff_settings, DESeqOut, FullRegionData, DESeqOutControl, 
     attrs = dict(out.attrs)
     out = out.sort_values("group", kind="stable").reset_index(drop=True)           # merge(out, distLookup, by = "group") re-sorts
     out.attrs.update(attrs)
-    out.to_csv(f"{s['outprefix']}_results{suffix}.csv", index=False)               # the reference: saveRDS(_results.Rds), :2062
+    cols, why = frame_columns_dev(out, ctx) if device_write else (None, "")
+    if cols is not None:
+        ctx.write_table(f"{s['outprefix']}_results{suffix}.csv", cols, [str(c) for c in out.columns], n=len(out))
+    else:
+        if why:
+            message("IHWcorrection: ", why, ": writing the results table on the host")
+        out.to_csv(f"{s['outprefix']}_results{suffix}.csv", index=False)           # the reference: saveRDS(_results.Rds), :2062
     return out
 
 
 def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, rng=None, assemble=False, control_seed=None,
-                     device_peaks=False, device_merge=False):
+                     device_peaks=False, device_merge=False, device_countput=False, device_write=False):
     """chicdiff.R:301-347, same stage order and messages.  ``assemble``: passed to getFullRegionData.  ``control_seed``: the control
     regions are drawn on the device from this seed (getControlRegionUniverse(seed=...)) instead of on the host from ``rng``, which
-    then serves IHWcorrection's columns alone.  ``device_peaks``, ``device_merge``: passed to getRegionUniverse."""
+    then serves IHWcorrection's columns alone.  ``device_peaks``, ``device_merge``: passed to getRegionUniverse.  ``device_countput``:
+    passed to getFullRegionData; ``device_write``: passed to getFullRegionData and IHWcorrection."""
     from . import hip
     from .settings import hipDevice
     own = ctx is None
@@ -736,7 +815,7 @@ def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, r
         RUcontrol = getControlRegionUniverse(chicdiff_settings, RU, ctx, rng=rng if control_seed is None else None, seed=control_seed)
         message("\n*** Running getFullRegionData\n")
         FullRegionData = getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=ctx, read_chicago=read_chicago,
-                                           assemble=assemble)
+                                           assemble=assemble, device_countput=device_countput, device_write=device_write)
         message("\n*** Running DESeq2Wrap for FullRegion\n")
         DESeqOut = DESeq2Wrap(chicdiff_settings, RU, FullRegionData[0], ctx=ctx)
         message("\n*** Running DESeq2Wrap for FullControlRegion\n")
@@ -747,7 +826,7 @@ def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, r
                                      theta=DESeqOut.attrs.get("theta"), ctx=ctx)
         message("\n*** Running IHWcorrection\n")
         output = IHWcorrection(chicdiff_settings, DESeqOut, FullRegionData[0], DESeqOutControl, FullRegionData[1],
-                               countput=FullRegionData[2], ctx=ctx, ihw=ihw, rng=rng)
+                               countput=FullRegionData[2], ctx=ctx, ihw=ihw, rng=rng, device_write=device_write)
         print({k: v for k, v in s.items()}, file=sys.stderr)
         return output
     finally:

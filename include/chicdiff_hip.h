@@ -129,6 +129,8 @@ int32_t chicdiff_hip_last_refits(const chicdiff_hip_ctx *ctx);
  *   "region_assemble_generic"   0 (default) | 1: test option of chicdiff_hip_region_assemble_dev (see there): same bits
  *   "chicago_tables_run_merge"  1 (default) | 0: chicdiff_hip_chicago_tables_dev merges runs of rows that aim at one fragment's slot inside the
  *                               wave before the global atomic (tables keyed by bait); 0 = one atomic per row: same bits
+ *   "table_write_half_kib"      0 (default: 64 MiB at most) | 4 .. 65536: test handle, KiB of one half of the pinned area that
+ *                               chicdiff_hip_table_write_dev moves the text through (small values make a small table take many halves)
  *   "fault_inject"              0 (default) .. 7; test hook, one-shot bits consumed by the next call: 1 = this rank reports a select
  *                               overflow in its next fit, 2 = a grid-barrier timeout of its trend kernel, 4 = an overflow of its
  *                               next size-factor select — to prove that all ranks of a sharded fit refit together
@@ -795,6 +797,72 @@ int chicdiff_hip_countput_dev(chicdiff_hip_ctx *ctx, int32_t nrep, const int32_t
                               const int64_t *d_midsum, const int32_t *d_chr, int32_t *d_out_bait, int32_t *d_out_oe, double *d_Nav,
                               double *d_Bav, double *d_out_score, double *d_mid, int64_t *ngroups_host);
 int chicdiff_hip_countput_caps(int32_t *max_rep, int32_t *key_rows_per_workgroup, int32_t *reduce_rows_per_workgroup);
+
+/* limits of chicdiff_hip_table_text_dev / chicdiff_hip_table_write_dev (below) */
+#define CHICDIFF_TABLE_MAX_COLUMNS 64          /* columns of a table: their descriptors travel as one kernel argument */
+#define CHICDIFF_TABLE_MAX_DICT 4096           /* entries of one dictionary column */
+#define CHICDIFF_TABLE_MAX_ENTRY_BYTES 4096    /* bytes of one dictionary entry */
+#define CHICDIFF_TABLE_ROWS_PER_TILE 256       /* consecutive rows a workgroup takes in both passes: one row per lane */
+#define CHICDIFF_TABLE_LDS_BYTES 65536         /* text of a tile staged in LDS at a time; a tile with more goes through it in chunks */
+#define CHICDIFF_TABLE_MAX_CELL_BYTES 24       /* the longest number: -2.2250738585072014e-308 */
+#define CHICDIFF_COL_INT32 0
+#define CHICDIFF_COL_INT64 1
+#define CHICDIFF_COL_FLOAT64 2
+#define CHICDIFF_COL_DICT 3
+/* A table of device columns written as text: what pandas' DataFrame.to_csv(index = False) writes for the same frame (pandas 2.x, no
+ * float_format, no quoting needed), byte for byte — the writing of _countput.csv and _results.csv (chicdiff_amd.pipeline; the
+ * reference saves .Rds, chicdiff.R:769, :2062).  The rule, stated in full (tests/table_text_twin.py is the same in plain Python):
+ *   - a table is ncol >= 2 columns of n rows and one separator byte (a tab, a comma or a blank); row r is its cells joined by the
+ *     separator, followed by '\n'.  One-column tables are not offered: pandas writes a NaN of a one-column frame as "".
+ *   - CHICDIFF_COL_INT32 / _INT64: the decimal digits, '-' in front of a negative value.
+ *   - CHICDIFF_COL_FLOAT64: NaN of any sign or payload gives no byte; +inf gives inf, -inf gives -inf; every other value gives Python's
+ *     repr(float): digits d1 .. dk (k <= 17), the shortest string that reads back to the value and among the shortest the one closest
+ *     to it; with decpt the position of the decimal point (value = 0.d1 .. dk * 10^decpt), -4 < decpt <= 16 gives the positional
+ *     form, which always has a fractional part (5.0, -0.0, 0.0001, 9999999999999998.0); any other decpt gives d[.ddd]e+XX / e-XX
+ *     with at least two exponent digits (1e+16, 1e-05, 5e-324).  A cell is at most CHICDIFF_TABLE_MAX_CELL_BYTES bytes.
+ *     (chicdiff_amd/csrc/table_text.h decides this with integers alone: 64 x 128-bit products against pow10_table.h.)
+ *   - CHICDIFF_COL_DICT: each row carries an int32 code into a table of at most CHICDIFF_TABLE_MAX_DICT byte strings (dict_off[ndict
+ *     + 1] ascending from 0, dict_bytes: HOST memory, copied by the call); a negative code gives no byte, as pandas writes None / NaN
+ *     in an object column; d_data = NULL means entry 0 for every row (a constant column).  An entry that holds the separator, '"',
+ *     '\r' or '\n' is refused: pandas would quote it.  A code >= ndict is refused once met (nothing is read out of bounds).
+ * Two passes (table_text_kernels.hip): a length pass, one lane per row, leaves every row's byte count and every tile's total; one scan
+ * of the tile totals places the tiles and gives the size (the first host stop); the write pass scans the row lengths inside the
+ * workgroup, formats every row into LDS at its offset and stores the tile's bytes as one contiguous run.  Placement comes from the two
+ * scans alone and no value passes through an atomic: the bytes are a function of the inputs, not of launch shape or arrival order.
+ * Limits, each refused by name with CHICDIFF_E_INVALID: ncol < 2 or > CHICDIFF_TABLE_MAX_COLUMNS; n < 0 or >= 2^31; an unknown
+ * kind; a NULL column with n > 0 (other than a dictionary's codes); a dictionary with no or too many entries, with offsets that do
+ * not ascend from 0, with an entry over CHICDIFF_TABLE_MAX_ENTRY_BYTES or one that needs quoting; a text of 2^40 bytes or more.
+ *
+ * chicdiff_hip_table_check: the refusals above on their own (host only, no context; d_data is compared with NULL, never read); the
+ * message goes to err[errcap].
+ * chicdiff_hip_table_text_dev: the device stage alone.  d_out[cap] is the caller's device buffer; *nbytes_host = the size of the text.
+ * cap < that size: nothing is written and the call returns CHICDIFF_OK — call again with room (cap = 0, d_out = NULL asks for the size).
+ * chicdiff_hip_table_write_dev: the text into a file.  The header bytes (header_bytes >= 0, written as they are — the caller ends
+ * them with '\n') go first unless `append` is set; append = 1 adds the rows behind what the file holds (created if missing).  The text
+ * is formed in a grow-only buffer of the context and leaves through the two halves of the bounded pinned area of
+ * chicdiff_hip_chinput_read_dev (2 x 64 MiB at most, never file-sized): host_copy_threads threads pwrite one half while the DMA of
+ * the other runs.  A failed open, write or close fails the call with CHICDIFF_E_INVALID, the message naming the path and the system's
+ * reason; the file is then removed if this call created it.  *written_host (may be NULL) = bytes written, header included.
+ * Timers (chicdiff_hip_kernel_times): table_len, table_scan, table_write, table_download (the DMAs and the file writes between them).
+ * chicdiff_hip_table_text_caps: rows per tile, LDS bytes, most columns, most dictionary entries (any pointer may be NULL). */
+typedef struct {
+    int32_t kind;              /* CHICDIFF_COL_* */
+    int32_t ndict;             /* CHICDIFF_COL_DICT: entries, 1 .. CHICDIFF_TABLE_MAX_DICT; otherwise ignored */
+    const void *d_data;        /* DEVICE: n values (int32 / int64 / float64), or n int32 codes, or NULL (dictionary: entry 0 throughout) */
+    const int32_t *dict_off;   /* HOST: ndict + 1 offsets */
+    const uint8_t *dict_bytes; /* HOST: the entries' bytes */
+} chicdiff_table_column;
+int chicdiff_hip_table_check(const chicdiff_table_column *cols, int32_t ncol, int64_t n, int32_t sep, char *err, int32_t errcap);
+int chicdiff_hip_table_text_dev(chicdiff_hip_ctx *ctx, const chicdiff_table_column *cols, int32_t ncol, int64_t n, int32_t sep,
+                                uint8_t *d_out, int64_t cap, int64_t *nbytes_host);
+int chicdiff_hip_table_write_dev(chicdiff_hip_ctx *ctx, const char *path, int32_t append, const uint8_t *header, int64_t header_bytes,
+                                 const chicdiff_table_column *cols, int32_t ncol, int64_t n, int32_t sep, int64_t *written_host);
+int chicdiff_hip_table_text_caps(int32_t *rows_per_tile, int32_t *lds_bytes, int32_t *max_columns, int32_t *max_dict);
+/* The double -> text function of the rule on its own: text (24 n bytes, slot i = bytes 24 i .., zero-filled behind the cell) and len
+ * (n).  _dev: through the device function, d_x / d_text / d_len device memory; the other: the same function compiled for the host, no
+ * device and no context (machines without a GPU check the rule with it). */
+int chicdiff_hip_selftest_format_double_dev(chicdiff_hip_ctx *ctx, const double *d_x, int64_t n, uint8_t *d_text, int32_t *d_len);
+int chicdiff_hip_selftest_format_double(const double *x, int64_t n, uint8_t *text, int32_t *len);
 
 /* a6 + a7 — estimateDispersions + nbinomWaldTest (chicdiff.R:1573-1574, 1602-1603, 1643-1644,
  * 1673-1674) for design ~condition (group[j] in {0,1}, both present) or ~1 (all group[j]==0).
