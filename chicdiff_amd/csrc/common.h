@@ -224,7 +224,8 @@ void launch_resid_hist(FitDims d, FitWork w, double *out40, hipStream_t st);  //
 void launch_prior_mc(FitDims d, FitWork w, const double *hist40, const void *table, hipStream_t st);  // simulation-matched prior variance
 void launch_wald_prep(const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o, hipStream_t st);
 void launch_wald_irls(const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o, hipStream_t st);
-void launch_wald_final(const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o,
+// row_constant: sum_j y_j log(alpha mu_j) of a row the IRLS converged on from wald_prep's row constant (option "wald_final_row_constant")
+void launch_wald_final(const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o, int row_constant,
                        const chicdiff_nbglm_out &out, hipStream_t st);
 void launch_wald_intercept(const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o,
                            const chicdiff_nbglm_out &out, hipStream_t st);
@@ -281,8 +282,9 @@ __host__ __device__ inline int sf_sub_bin(double x, int nb, int b) {
 }
 // hist: kSfWorkWords words, the histograms all zero (the pick leaves them so); lists: n x S words, column j's keys from j * n (free: the offsets buffer)
 // cus: compute units of the device (both passes run one workgroup on each)
+// log_table: both passes take log k of a count k < kSfLogK from a table the workgroup fills in LDS (option "sf_log_table")
 void launch_sf_direct(const int32_t *counts, int64_t n, int S, SelArgs a, FitWork w, unsigned int *hist, uint64_t *lists,
-                      int32_t *clear_flag, int cus, hipStream_t st);
+                      int32_t *clear_flag, int cus, int log_table, hipStream_t st);
 void launch_offsets(const double *fullMean, const double *sf_dev, int64_t n, int S, double theta, int mix,
                     double *out, hipStream_t st);
 void launch_window_sums(const int32_t *fragN, const double *fragFM, int64_t nfrag, int S, const int64_t *rptr,

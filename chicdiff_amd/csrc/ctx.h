@@ -49,6 +49,8 @@ struct HostOpts {
     int region_assemble_generic = 0;  // test option: every tile of region_assemble takes the generic path
     int table_write_half_kib = 0;  // test handle: bytes (KiB) of one half of the pinned area in chicdiff_hip_table_write_dev (0: up to 64 MiB)
     int chicago_tables_run_merge = 1;  // chicago_tables: runs of rows with one slot are merged inside the wave before the global atomic
+    int sf_log_table = 1;  // size factors, direct route: log k of a count below kSfLogK from a table in LDS (0: a table logarithm per count)
+    int wald_final_row_constant = 1;  // wald_final: sum_j y_j log(alpha mu_j) of a row the IRLS converged on from wald_prep's row constant (0: a table logarithm per sample)
 };
 
 struct chicdiff_hip_ctx {

@@ -84,6 +84,8 @@ static const OptionDef kOptions[] = {
     {"table_write_half_kib", nullptr, &HostOpts::table_write_half_kib, 0, 65536, 1, 3},  // 0 (64 MiB at most) or 4 .. 65536
     {"fault_inject", nullptr, &HostOpts::fault_inject, 0, 7, 1, 0},
     {"bench_fake_world", nullptr, &HostOpts::bench_fake_world, 0, kGatherMaxWorld, 1, 0},
+    {"sf_log_table", nullptr, &HostOpts::sf_log_table, 0, 1, 1, 0},
+    {"wald_final_row_constant", nullptr, &HostOpts::wald_final_row_constant, 0, 1, 1, 0},
     {"local_trend_substitute", nullptr, &HostOpts::local_trend_substitute, 0, 1, 1, 0},
 };
 

@@ -562,7 +562,7 @@ static int fit_pass(chicdiff_hip_ctx *c, const int32_t *d_counts, const double *
             launch_wald_irls(d_counts, d_nf, d, w, o, st);
         }
         Scope t(c, "wald_final");
-        launch_wald_final(d_counts, d_nf, d, w, o, out, st);
+        launch_wald_final(d_counts, d_nf, d, w, o, c->host.wald_final_row_constant, out, st);
     } else {
         Scope t(c, "wald_intercept");
         launch_wald_intercept(d_counts, d_nf, d, w, o, out, st);
@@ -828,7 +828,7 @@ static int size_factors_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, int64
         if (c->sfhist_dirty) HIPCHK(c, hipMemsetAsync(c->d_sfhist, 0, sizeof(unsigned int) * kSfWorkWords, c->stream));
         c->sfhist_dirty = true;
         launch_sf_direct(d_counts, n, S, sa, c->w, c->d_sfhist, reinterpret_cast<uint64_t *>(c->d_nf_tmp), c->d_carry,
-                         c->cu_count, c->stream);
+                         c->cu_count, c->host.sf_log_table, c->stream);
         HIPCHK(c, hipGetLastError());
         c->sfhist_dirty = false;  // every launch went out: the pick leaves the histograms zero
     } else {

@@ -1623,13 +1623,30 @@ void launch_row_ratio(const int32_t *counts, int64_t n, int S, double *ratio, in
 
 // The keys of one row, by row_ratio16_kernel's expressions (-ffp-contract=off: the same bits wherever this is inlined — the two
 // passes must agree on every key).  false = the row is not used (a zero or negative count).
-template <int SM>
-__device__ __forceinline__ bool sf_row_keys(const int32_t (&kc)[SM], int S, const LogEntry *lt, double (&x)[SM]) {
+// TAB (option "sf_log_table"): log k of a count 0 <= k < kSfLogK is read from logk[] — the table sf_logk_to_lds fills with this very
+// expression, so the key has the same bits either way —, a larger or negative count goes through it under a branch (99.94 % of the
+// benchmark matrix's counts are below 2048: a wave trip of 64 rows takes the branch for 4 % of its samples).  A count is an integer,
+// and the row-per-thread passes are issue-bound: the ~25 VALU instructions of tlog per key were about half of both.
+#ifndef CHICDIFF_SF_LOGK
+#define CHICDIFF_SF_LOGK 2048
+#endif
+constexpr int kSfLogK = CHICDIFF_SF_LOGK;  // 16 KB of LDS; DESIGN.md section 5 has 1024 against 2048
+__device__ __forceinline__ double sf_log_count(int32_t k, const LogEntry *lt) {
+    return k > 0 ? tlog((double)k, lt) : (k == 0 ? -INFINITY : NAN);  // log(0) = -Inf drops the row, as in R
+}
+// (call behind log_table_to_lds; ends with a barrier)
+__device__ __forceinline__ void sf_logk_to_lds(double *logk, const LogEntry *lt) {
+    for (int k = threadIdx.x; k < kSfLogK; k += blockDim.x) logk[k] = sf_log_count(k, lt);
+    __syncthreads();
+}
+template <int SM, bool TAB>
+__device__ __forceinline__ bool sf_row_keys(const int32_t (&kc)[SM], int S, const LogEntry *lt, const double *logk, double (&x)[SM]) {
     double l[SM];
 #pragma unroll
     for (int j = 0; j < SM; j++) {
         const int32_t k = kc[j];
-        l[j] = k > 0 ? tlog((double)k, lt) : (k == 0 ? -INFINITY : NAN);  // log(0) = -Inf drops the row, as in R
+        if (TAB && (uint32_t)k < (uint32_t)kSfLogK) l[j] = logk[k];
+        else l[j] = sf_log_count(k, lt);
     }
     double s = 0;
 #pragma unroll
@@ -1724,15 +1741,17 @@ __device__ __forceinline__ void sf_wg_pick(const unsigned int *h, int nb, int nr
     __syncthreads();  // (the shared words belong to the next call from here on)
 }
 
-template <int SM>
+template <int SM, bool TAB>
 __global__ __launch_bounds__(kSfThreads) void sf_hist_kernel(const int32_t *__restrict__ counts, int64_t n, int S, int nb,
                                                             unsigned int *__restrict__ ghist, int32_t *clear_flag) {
     if (clear_flag && blockIdx.x == 0 && threadIdx.x == 0) *clear_flag = 0;  // (nothing on this route sets it: as row_ratio16_kernel)
     __shared__ LogEntry s_lt[64];
     __shared__ unsigned int s_h[kSfHistWords];
+    __shared__ double s_logk[TAB ? kSfLogK : 1];
     const int words = S * nb;
     for (int k = threadIdx.x; k < words; k += kSfThreads) s_h[k] = 0;
     log_table_to_lds(s_lt);
+    if (TAB) sf_logk_to_lds(s_logk, s_lt);
     const int64_t step = (int64_t)gridDim.x * kSfThreads;
     int32_t kn[SM];  // the next row's counts are loaded before the current row is worked on
     int64_t i = (int64_t)blockIdx.x * kSfThreads + threadIdx.x;
@@ -1747,7 +1766,7 @@ __global__ __launch_bounds__(kSfThreads) void sf_hist_kernel(const int32_t *__re
 #pragma unroll
             for (int j = 0; j < SM; j++) kn[j] = j < S ? counts[(int64_t)j * n + i + step] : 1;
         }
-        const bool use = sf_row_keys<SM>(kc, S, s_lt, x);
+        const bool use = sf_row_keys<SM, TAB>(kc, S, s_lt, s_logk, x);
 #pragma unroll
         for (int j = 0; j < SM; j++)
             if (j < S) sf_hist_add(s_h + j * nb, use, (unsigned int)sf_bin(x[j], nb));
@@ -1784,10 +1803,11 @@ __global__ __launch_bounds__(kSfThreads) void sf_pick_kernel(FitWork w, unsigned
 // One atomic per wave and list straight into the lists' lengths made this launch 312 us at 2 M x 8: about every wave trip holds a
 // wanted key, the returning atomics of 256 CUs queue on the one cache line the sixteen lengths shared.  So a workgroup keeps what it
 // finds in LDS and reserves room once per list at its end; only keys beyond kSfStage (massive ties) go out at once, wave by wave.
-template <int SM>
+template <int SM, bool TAB>
 __global__ __launch_bounds__(kSfThreads) void sf_list_kernel(const int32_t *__restrict__ counts, int64_t n, int S, int nb, FitWork w,
                                                             unsigned int *__restrict__ gcnt, uint64_t *__restrict__ lists) {
     __shared__ LogEntry s_lt[64];
+    __shared__ double s_logk[TAB ? kSfLogK : 1];
     __shared__ int s_b[2][kSfMaxS];
     __shared__ uint64_t s_key[kSfStage];
     __shared__ unsigned char s_tag[kSfStage];  // 2 x column + slot
@@ -1797,6 +1817,7 @@ __global__ __launch_bounds__(kSfThreads) void sf_list_kernel(const int32_t *__re
     if (threadIdx.x < 2 * kSfMaxS) s_lc[threadIdx.x] = 0;
     if (threadIdx.x == 0) s_n = 0;
     log_table_to_lds(s_lt);
+    if (TAB) sf_logk_to_lds(s_logk, s_lt);
     const int lane = threadIdx.x & 63;
     const int64_t step = (int64_t)gridDim.x * kSfThreads;
     int32_t kn[SM];
@@ -1812,7 +1833,7 @@ __global__ __launch_bounds__(kSfThreads) void sf_list_kernel(const int32_t *__re
 #pragma unroll
             for (int j = 0; j < SM; j++) kn[j] = j < S ? counts[(int64_t)j * n + i + step] : 1;
         }
-        const bool use = sf_row_keys<SM>(kc, S, s_lt, x);
+        const bool use = sf_row_keys<SM, TAB>(kc, S, s_lt, s_logk, x);
         unsigned int hit = 0;  // bit j: column j's key lies in the bin of slot 0; bit 16 + j: in that of slot 1, another bin
 #pragma unroll
         for (int j = 0; j < SM; j++)
@@ -1980,22 +2001,28 @@ __global__ __launch_bounds__(kSfThreads) void sf_finish_kernel(SelArgs a, FitWor
     }
 }
 
+template <bool TAB>
+static void launch_sf_passes(const int32_t *counts, int64_t n, int S, int nb, unsigned int hb, FitWork w, unsigned int *hist, unsigned int *gcnt,
+                             uint64_t *lists, int32_t *clear_flag, hipStream_t st) {
+    if (S <= 4) sf_hist_kernel<4, TAB><<<hb, kSfThreads, 0, st>>>(counts, n, S, nb, hist, clear_flag);
+    else if (S <= 8) sf_hist_kernel<8, TAB><<<hb, kSfThreads, 0, st>>>(counts, n, S, nb, hist, clear_flag);
+    else sf_hist_kernel<16, TAB><<<hb, kSfThreads, 0, st>>>(counts, n, S, nb, hist, clear_flag);
+    sf_pick_kernel<<<S, kSfThreads, 0, st>>>(w, hist, gcnt, nb);
+    if (S <= 4) sf_list_kernel<4, TAB><<<hb, kSfThreads, 0, st>>>(counts, n, S, nb, w, gcnt, lists);
+    else if (S <= 8) sf_list_kernel<8, TAB><<<hb, kSfThreads, 0, st>>>(counts, n, S, nb, w, gcnt, lists);
+    else sf_list_kernel<16, TAB><<<hb, kSfThreads, 0, st>>>(counts, n, S, nb, w, gcnt, lists);
+}
 void launch_sf_direct(const int32_t *counts, int64_t n, int S, SelArgs a, FitWork w, unsigned int *hist, uint64_t *lists,
-                      int32_t *clear_flag, int cus, hipStream_t st) {
+                      int32_t *clear_flag, int cus, int log_table, hipStream_t st) {
     const int nb = sf_bins(S);
-    // both passes: one 16-wave workgroup per CU and a grid-stride loop.  LDS (62 KB) would let a second one in, registers do not (65 at
+    // both passes: one 16-wave workgroup per CU and a grid-stride loop.  LDS (62 KB, 78 with the table of log k) would let a second one in, registers do not (65 at
     // S = 8: a SIMD holds seven such waves, two workgroups need eight); and every workgroup of pass 1 ends by adding its S x nb
     // counters to the global histogram, so more of them is more of that
     int64_t hb = (n + kSfThreads - 1) / kSfThreads;
     if (hb > (cus > 0 ? cus : 256)) hb = cus > 0 ? cus : 256;
     unsigned int *gcnt = hist + kSfHistWords;
-    if (S <= 4) sf_hist_kernel<4><<<(unsigned)hb, kSfThreads, 0, st>>>(counts, n, S, nb, hist, clear_flag);
-    else if (S <= 8) sf_hist_kernel<8><<<(unsigned)hb, kSfThreads, 0, st>>>(counts, n, S, nb, hist, clear_flag);
-    else sf_hist_kernel<16><<<(unsigned)hb, kSfThreads, 0, st>>>(counts, n, S, nb, hist, clear_flag);
-    sf_pick_kernel<<<S, kSfThreads, 0, st>>>(w, hist, gcnt, nb);
-    if (S <= 4) sf_list_kernel<4><<<(unsigned)hb, kSfThreads, 0, st>>>(counts, n, S, nb, w, gcnt, lists);
-    else if (S <= 8) sf_list_kernel<8><<<(unsigned)hb, kSfThreads, 0, st>>>(counts, n, S, nb, w, gcnt, lists);
-    else sf_list_kernel<16><<<(unsigned)hb, kSfThreads, 0, st>>>(counts, n, S, nb, w, gcnt, lists);
+    if (log_table) launch_sf_passes<true>(counts, n, S, nb, (unsigned)hb, w, hist, gcnt, lists, clear_flag, st);
+    else launch_sf_passes<false>(counts, n, S, nb, (unsigned)hb, w, hist, gcnt, lists, clear_flag, st);
     sf_finish_kernel<<<S, kSfThreads, 0, st>>>(a, w, nb, gcnt, lists);
 }
 

@@ -561,8 +561,13 @@ __device__ __forceinline__ double cell_trimmed_mean(const double *s_q, int T, in
     return sum / (nc - 2 * lo);
 }
 
+// row_const (option "wald_final_row_constant"): for a row the IRLS converged on (oc < 0: mu_j = nf_j e^eta, unfloored, in the likelihood)
+// sum_j y_j (log alpha + log mu_j) = cst + eta_A sum_A y + eta_B sum_B y, with cst = sum_j y_j (log alpha + log nf_j) — the identity the
+// IRLS's own deviance uses, and wald_prep left crow + cst in the start record: no logarithm of mu per sample (26 of the loop's 176
+// instructions).  Another association of the same 2 S + O(1) terms: deviance within 2^-45 of its magnitude, every other output the same
+// bits.  Rows of the optim fallback (oc >= 0, floored mu: a handful per million) keep the per-sample sum.
 __global__ __launch_bounds__(256) void wald_final_kernel(const int32_t *__restrict__ counts,
-                                                         const double *__restrict__ nf, FitDims d, FitWork w, Opts o,
+                                                         const double *__restrict__ nf, FitDims d, FitWork w, Opts o, int row_const,
                                                          chicdiff_nbglm_out out) {
     extern __shared__ double s_q[];  // [S][blockDim.x] normalised counts of this thread's row
     __shared__ LogEntry s_lt[64];
@@ -589,13 +594,16 @@ __global__ __launch_bounds__(256) void wald_final_kernel(const int32_t *__restri
             // (round 4: table-driven exp / log as in the IRLS, reciprocals where a quotient is not part of a decision — the kernel was
             // 2 400 instructions per row, a third of them IEEE divisions and polynomial logarithms)
             const double E0 = texp(b0, s_et), E1 = texp(b0 + b1, s_et);
-            const double la = tlog(alpha, s_lt);
-            double wA = 0, wB = 0, ll = w.crow[i], m = 0;
+            const bool rc = row_const && oc < 0;
+            const double la = rc ? 0.0 : tlog(alpha, s_lt);
+            double wA = 0, wB = 0, ll = rc ? w.start[4 * i + 1] : w.crow[i], m = 0;
+            int64_t syA = 0, syB = 0;  // (64 bits: S counts of up to 2^31 - 1)
             int y_next = counts[i];
             double nf_next = nf[i];
             for (int j = 0; j < S; j++) {
                 const bool g = (d.gmask >> j) & 1;
-                const double y = (double)y_next;
+                const int yi = y_next;
+                const double y = (double)yi;
                 const double nfj = nf_next;
                 if (j + 1 < S) {  // the next sample's loads are in flight while this one is worked on
                     y_next = counts[(int64_t)(j + 1) * n + i];
@@ -610,13 +618,16 @@ __global__ __launch_bounds__(256) void wald_final_kernel(const int32_t *__restri
                 const double mul = oc >= 0 ? mu : muf;
                 const double ma = alpha * mul, t = 1.0 + ma;
                 ll -= (size + y) * tlog1p_from(ma, t, rcp(t), s_lt);
-                if (y > 0) ll += y * (la + tlog(mul, s_lt));
+                if (rc) {
+                    if (g) syB += yi; else syA += yi;
+                } else if (y > 0) ll += y * (la + tlog(mul, s_lt));
                 if (want_cooks) {
                     const double q = y / nfj;
                     s_q[j * T + tid] = q;
                     m += q;
                 }
             }
+            if (rc) ll += fma(b0, (double)syA, (b0 + b1) * (double)syB);  // eta_A sum_A y + eta_B sum_B y, as the IRLS's D
             const double m00 = wA + wB + lambda, m01 = wB, m11 = wB + lambda, det = m00 * m11 - m01 * m01;
             const double idet = rcp_or_div(det);
             const double i00 = m11 * idet, i01 = -m01 * idet, i11 = m00 * idet;
@@ -882,10 +893,10 @@ void launch_wald_irls(const int32_t *counts, const double *nf, FitDims d, FitWor
     }
 #endif
 }
-void launch_wald_final(const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o,
+void launch_wald_final(const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o, int row_constant,
                        const chicdiff_nbglm_out &out, hipStream_t st) {
     const int threads = d.S <= 16 ? 256 : 64;
-    wald_final_kernel<<<kRedBlocks, threads, (size_t)d.S * threads * sizeof(double), st>>>(counts, nf, d, w, o, out);
+    wald_final_kernel<<<kRedBlocks, threads, (size_t)d.S * threads * sizeof(double), st>>>(counts, nf, d, w, o, row_constant, out);
 }
 void launch_wald_intercept(const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts,
                            const chicdiff_nbglm_out &out, hipStream_t st) {

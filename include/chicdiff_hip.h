@@ -137,6 +137,13 @@ int32_t chicdiff_hip_last_refits(const chicdiff_hip_ctx *ctx);
  *   "bench_fake_world"          0 (default) | 1 .. 64: rehearsal hook of bench.py, refused above 1 unless CHICDIFF_BENCH_FAKE_WORLD is set
  *                               in the environment: on a 1-rank communicator the trend's rows are gathered as if this many ranks had
  *                               each sent this rank's block (a rank's step of an N-GPU fit at its share of the rows)
+ *   "sf_log_table"              1 (default) | 0: the two passes of the single-rank size-factor route (S <= 16) take the logarithm of a
+ *                               count below 2048 from a table each workgroup fills in LDS with the very function it replaces;
+ *                               0 = a table-driven logarithm per count: same bits
+ *   "wald_final_row_constant"   1 (default) | 0: the Wald stage's last kernel takes sum_j y_j log(alpha mu_j) of a row the IRLS
+ *                               converged on from the row constant and the group sums of the counts instead of a logarithm per
+ *                               sample: `deviance` and `sumDeviance` differ in summation order only (1e-13), every other output
+ *                               has the same bits
  * and one that does change the outcome of a fit whose parametric trend fails (DESeq2 offers the same choice through fitType):
  *   "local_trend_substitute"    1 (default) | 0: report CHICDIFF_ST_TREND_FAILED instead of substituting the local regression */
 int chicdiff_hip_set_option(chicdiff_hip_ctx *ctx, const char *name, int64_t value);
