@@ -480,6 +480,7 @@ constexpr int kIfBlock = 1024;
 // ranks inside that one p-order.  The host looks once in between, for the 50-point lowess that picks the filter.
 struct IfState {
     unsigned long long nzero, count;  // rows with baseMean == 0; rows with a p-value
+    unsigned long long nnan;          // rows whose baseMean is NaN: quantile() stops on them in R, the host refuses them
     unsigned int total[kIfN];         // rows passing filter f (and holding a p-value)
     unsigned int numRej[kIfN];        // BH rejections at level alpha among them
     double cut[kIfN];                 // quantile(baseMean, theta[f])
@@ -487,13 +488,15 @@ struct IfState {
 };
 
 __global__ __launch_bounds__(256) void if_keys_kernel(const double *__restrict__ bm, int64_t n, uint64_t *keys, IfState *st) {
-    unsigned int mine = 0;
+    unsigned int mine = 0, nan = 0;
     for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double x = bm[i];
         keys[i] = x != x ? ~0ull : key_of(x);
         mine += x == 0.0 ? 1u : 0u;
+        nan += x != x ? 1u : 0u;
     }
     if (mine) atomicAdd(&st->nzero, (unsigned long long)mine);
+    if (nan) atomicAdd(&st->nnan, (unsigned long long)nan);
 }
 // lower = mean(baseMean == 0); theta = seq(lower, upper, length = 50); cutoffs = quantile(baseMean, theta), type 7
 __global__ void if_cuts_kernel(const uint64_t *__restrict__ sorted, int64_t n, double alpha, IfState *st) {
@@ -714,7 +717,7 @@ size_t if_workspace_bytes(int64_t n) {
     return bh_workspace_bytes(n) + 2 * al(8 * (size_t)n) + al((size_t)n) + al(4 * (size_t)kIfN * nblocks) + al(sort_tmp) + al(sizeof(IfState)) + 256;
 }
 
-// returns 0 ok.  info: filterThreshold, filterTheta, index (1-based), theta[50], numRej[50], lowess[50]
+// returns 0 ok, 2 when a baseMean is NaN (nothing is written to d_padj then).  info: filterThreshold, filterTheta, index (1-based), theta[50], numRej[50], lowess[50]
 // st2 / fork / join: a second stream and two events of the caller's, so that the two independent sorts (baseMean keys
 // for the cutoffs, p-values for everything else — each a chain of ~20 small launches that does not fill the GPU at
 // 2 M rows) run side by side
@@ -762,6 +765,7 @@ int run_independent_filtering(const double *d_bm, const double *d_p, int64_t n, 
     //    one place the host looks at the device's numbers before the end
     IfState h;
     if (hipMemcpyAsync(&h, state, sizeof(IfState), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return 1;
+    if (h.nnan) return 2;
     double maxRej = 0;
     for (int k = 0; k < kIfN; k++) {
         info->theta[k] = h.info.theta[k];

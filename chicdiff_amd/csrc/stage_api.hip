@@ -621,8 +621,9 @@ extern "C" int chicdiff_hip_independent_filtering_dev(chicdiff_hip_ctx *c, const
     timing_reset(c);
     {
         Scope t(c, "independent_filtering");
-        if (run_independent_filtering(d_baseMean, d_pvalue, n, alpha, d_padj, c->aux, c->stream, c->copy_stream, c->ev_fork, c->ev_join, info))
-            return fail(c, CHICDIFF_E_HIP, "independent_filtering: %s", hipGetErrorString(hipGetLastError()));
+        const int rf = run_independent_filtering(d_baseMean, d_pvalue, n, alpha, d_padj, c->aux, c->stream, c->copy_stream, c->ev_fork, c->ev_join, info);
+        if (rf == 2) return fail(c, CHICDIFF_E_INVALID, "independent_filtering: NaN baseMean (quantile() stops on missing values)");
+        if (rf) return fail(c, CHICDIFF_E_HIP, "independent_filtering: %s", hipGetErrorString(hipGetLastError()));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     timing_collect(c);

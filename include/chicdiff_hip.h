@@ -568,6 +568,7 @@ typedef struct {
     int32_t _pad;
     double theta[50], numRej[50], lowess[50];
 } chicdiff_results_info;
+/* A NaN baseMean is refused (CHICDIFF_E_INVALID): R's quantile() stops on missing values. */
 int chicdiff_hip_independent_filtering_dev(chicdiff_hip_ctx *ctx, const double *d_baseMean, const double *d_pvalue, int64_t n,
                                            double alpha, double *d_padj, chicdiff_results_info *info);
 
