@@ -177,6 +177,14 @@ int do_allgather(chicdiff_hip_ctx *c, const double *send, double *recv, int64_t 
 int check_counts_group(chicdiff_hip_ctx *c, int64_t n, int32_t S, const int32_t *group, FitDims &d);
 int check_opts(chicdiff_hip_ctx *c, const chicdiff_nbglm_opts *opts);
 Opts make_opts(const chicdiff_hip_ctx *c, const chicdiff_nbglm_opts *in, int S);
+struct LfTree {  // the local trend's vertices as the host grows them (local_trend_fit)
+    int nv = 0;
+    double x[kLfMaxV], h[kLfMaxV], f[kLfMaxV], d[kLfMaxV];
+};
+int global_stage(chicdiff_hip_ctx *c, FitDims d, const Opts &o, bool all_rounds, LfTree *tree);
+bool substitute_local_trend(const chicdiff_hip_ctx *c, const Opts &o);  // the verdict of fit_dev_impl on a failed parametric trend
+bool prior_by_simulation(const FitDims &d, const Opts &o);
+double *resid_hist_of(const FitWork &w);  // the 40 device doubles prior_mc counts the residuals into
 
 }  // namespace cd
 

@@ -8,6 +8,7 @@
 #include "ctx.h"
 
 static double *sums_of(const FitWork &w) { return w.partials + (size_t)kRedBlocks * 72; }
+double *cd::resid_hist_of(const FitWork &w) { return sums_of(w) + 32; }
 
 // ---- HIP backend of fit_driver.h -----------------------------------------------------------
 struct HipBackend {
@@ -206,16 +207,23 @@ static int lf_vertex(chicdiff_hip_ctx *c, FitDims d, const Opts &o, double nfit,
     long double A[3][4] = {{s[0], s[1], (long double)s[2] / 2, s[5]},
                            {s[1], s[2], (long double)s[3] / 2, s[6]},
                            {(long double)s[2] / 2, (long double)s[3] / 2, (long double)s[4] / 4, (long double)s[7] / 2}};
+    // B: the sum of the absolute values of the terms an entry was formed from.  With fewer than three distinct x inside the bandwidth
+    // the exact system is singular, but the moments are rounded sums: elimination leaves a residue instead of a zero, and a test for
+    // zero would take it for a pivot and fit through noise.  A pivot within kLfSingular of its terms' sum is such a residue.
+    constexpr long double kLfSingular = 0x1p-40L;  // far above the moments' rounding (double sums), far below a pivot that leaves a digit
+    long double B[3][4];
+    for (int r = 0; r < 3; r++)
+        for (int q = 0; q < 4; q++) B[r][q] = fabsl(A[r][q]);
     for (int col = 0; col < 3; col++) {
         int piv = col;
         for (int r = col + 1; r < 3; r++)
             if (fabsl(A[r][col]) > fabsl(A[piv][col])) piv = r;
-        if (!(fabsl(A[piv][col]) > 0)) return CHICDIFF_E_NUMERIC;
+        if (!(fabsl(A[piv][col]) > kLfSingular * B[piv][col])) return CHICDIFF_E_NUMERIC;
         if (piv != col)
-            for (int q = 0; q < 4; q++) std::swap(A[col][q], A[piv][q]);
+            for (int q = 0; q < 4; q++) { std::swap(A[col][q], A[piv][q]); std::swap(B[col][q], B[piv][q]); }
         for (int r = col + 1; r < 3; r++) {
             const long double m = A[r][col] / A[col][col];
-            for (int q = col; q < 4; q++) A[r][q] -= m * A[col][q];
+            for (int q = col; q < 4; q++) { A[r][q] -= m * A[col][q]; B[r][q] += fabsl(m) * B[col][q]; }
         }
     }
     long double b[3];
@@ -228,10 +236,6 @@ static int lf_vertex(chicdiff_hip_ctx *c, FitDims d, const Opts &o, double nfit,
     *df = (double)b[1];
     return CHICDIFF_OK;
 }
-struct LfTree {
-    int nv = 0;
-    double x[kLfMaxV], h[kLfMaxV], f[kLfMaxV], d[kLfMaxV];
-};
 // a new vertex at xv: its index, or -1 with *rc set (CHICDIFF_E_NUMERIC: no fit possible there / too many vertices)
 static int lf_add(chicdiff_hip_ctx *c, FitDims d, const Opts &o, double nfit, LfTree &t, double xv, int *rc) {
     if (t.nv >= kLfMaxV) { *rc = CHICDIFF_E_NUMERIC; return -1; }
@@ -253,7 +257,8 @@ static int lf_grow(chicdiff_hip_ctx *c, FitDims d, const Opts &o, double nfit, L
     return lf_grow(c, d, o, nfit, t, im, ir, range);
 }
 // returns CHICDIFF_OK with dispFit[] filled and the trend marked local, or CHICDIFF_E_NUMERIC when no fit is possible
-static int local_trend_fit(chicdiff_hip_ctx *c, FitDims d, const Opts &o) {
+// (tree_out, may be NULL: the vertices as the evaluation gets them, with their bandwidths)
+static int local_trend_fit(chicdiff_hip_ctx *c, FitDims d, const Opts &o, LfTree *tree_out) {
     double lo, hi, nfit = 0, dummy;
     int rc = lf_order_stat(c, d, o, 0, 0.0, 0.0, &lo, &nfit);  // min(x) and the number of rows in the fit
     if (rc) return rc;
@@ -270,6 +275,10 @@ static int local_trend_fit(chicdiff_hip_ctx *c, FitDims d, const Opts &o) {
     std::sort(order.begin(), order.end(), [&](int p, int q) { return t.x[p] < t.x[q]; });
     v.nv = t.nv;
     for (int i = 0; i < t.nv; i++) { v.x[i] = t.x[order[i]]; v.f[i] = t.f[order[i]]; v.d[i] = t.d[order[i]]; }
+    if (tree_out) {
+        tree_out->nv = t.nv;
+        for (int i = 0; i < t.nv; i++) { tree_out->x[i] = v.x[i]; tree_out->h[i] = t.h[order[i]]; tree_out->f[i] = v.f[i]; tree_out->d[i] = v.d[i]; }
+    }
     launch_lf_eval(d, c->w, v, c->stream);
     return CHICDIFF_OK;
 }
@@ -379,13 +388,13 @@ struct WorkRedirect {
 };
 
 // the prior variance is matched by simulation (prior_mc.h) instead of taken in closed form
-static bool prior_by_simulation(const FitDims &d, const Opts &o) { return !(o.dispPriorVarIn == o.dispPriorVarIn) && d.S - d.p <= 3 && d.S > d.p; }
+bool cd::prior_by_simulation(const FitDims &d, const Opts &o) { return !(o.dispPriorVarIn == o.dispPriorVarIn) && d.S - d.p <= 3 && d.S > d.p; }
 
 // residual d.f. <= 3: DESeq2 matches the prior variance by simulation (prior_mc.h).  The 200 x 40 simulated densities are
 // constants (built once per process and d.f.); the matching itself runs on the device, on the histogram of the residuals in wm.resid
 static int prior_mc(chicdiff_hip_ctx *c, FitDims d, FitDims dm, const FitWork &wm, bool mad_local) {
     Scope t(c, "prior_mc");
-    double *d_hist = sums_of(c->w) + 32;
+    double *d_hist = resid_hist_of(c->w);
     launch_resid_hist(dm, wm, d_hist, c->stream);
     if (!mad_local)
         if (int rc = do_allreduce(c, d_hist, kPmcBins)) return rc;
@@ -405,39 +414,16 @@ static int read_scalars(chicdiff_hip_ctx *c) {
     return CHICDIFF_OK;
 }
 
-// one pass of a fit, from the counts to the scalars on the host (c->h_sc); fit_dev_impl reads the verdicts and repeats it if need be
-static int fit_pass(chicdiff_hip_ctx *c, const int32_t *d_counts, const double *d_nf, FitDims d, const Opts &o,
-                    const chicdiff_nbglm_out *d_out, bool all_rounds) {
+// The global stage of a pass, between the gene-wise search and the MAP search: the trend (caller-supplied, mean, local, persistent,
+// gathered or driven), the residuals, their median and MAD, and the prior variance (closed form or prior_mc).  Reads the workspace
+// columns baseMean, dispGene and allZero; leaves the trend's scalars, w.resid and — under a local trend — w.dispFit.  tree (may be
+// NULL): the vertices of a local trend, ascending x (nv = 0 when none was fitted).  fit_pass calls it; so does the test entry
+// chicdiff_hip_selftest_global_stage_dev (selftest_api.hip), which fills the three columns from its caller's.
+int cd::global_stage(chicdiff_hip_ctx *c, FitDims d, const Opts &o, bool all_rounds, LfTree *tree) {
     int rc;
     hipStream_t st = c->stream;
     FitWork &w = c->w;
-    c->tg_total = 0;
-    // the scalars, the queue heads and the barrier counters sit next to each other in the workspace: one fill
-    HIPCHK(c, hipMemsetAsync(w.sc, 0, align256(sizeof(FitScalars)) + kQueueBytes + 1024, st));
-    // sharded: the column sums of nf travel as the ranks' double-double pairs (zero-filled slots + sum-all-reduce = an exact gather)
-    // and are added in rank order — the correctly rounded exact sum, as on one rank: same xim, same start values, same bits downstream
-    const int world = c->world > 0 ? c->world : 1;
-    const bool col_slots = c->allreduce && world <= kSelMaxWorld;
-    const size_t slot_doubles = (size_t)(d.S + 1) * 2;
-    double *slots = col_slots ? w.hist : nullptr;  // (the select histograms are idle here)
-    if (col_slots) HIPCHK(c, hipMemsetAsync(slots, 0, sizeof(double) * slot_doubles * world, st));
-    {
-        Scope t(c, "prep");
-        const bool fused = c->fuse.fm != nullptr && d.S <= 16 && d_nf == c->d_nf_tmp;
-        const int nblk = launch_prep(d_counts, const_cast<double *>(d_nf), d, w, o, st, fused ? c->fuse : FusedOffsets(), c->host.prep_blocks);
-        launch_prep_finish(d, w, nblk, col_slots ? slots + slot_doubles * c->rank : nullptr, st);
-    }
-    if (col_slots) {
-        if ((rc = do_allreduce(c, slots, (int64_t)(slot_doubles * world)))) return rc;
-    } else if ((rc = do_allreduce(c, w.sc->colsum, kMaxS + 1)))  // colsum[kMaxS] + nnz are contiguous
-        return rc;
-    if (c->allreduce) launch_xim(d, w, slots, world, st);  // (the ranks' column sums, exchanged above, added in rank order -> xim)
-    {
-        Scope t(c, "disp_gene");
-        Opts og = o;
-        og.xim_here = c->allreduce ? 0 : 1;  // single rank: disp_init forms xim from the column sums itself (one dependent launch less)
-        launch_disp_gene(d_counts, d_nf, d, w, og, st);
-    }
+    if (tree) tree->nv = 0;
     // trend: fit_driver.h runs batches of IRLS passes and polls the finished flag between batches
     bool mad_in_kernel = false;  // the persistent trend kernel went on to the residuals, their median and MAD, and the closed-form prior variance
     if (o.trendIn[0] == o.trendIn[0] && o.trendIn[1] == o.trendIn[1]) {  // caller-supplied dispersion function
@@ -475,7 +461,7 @@ static int fit_pass(chicdiff_hip_ctx *c, const int32_t *d_counts, const double *
         // a parametric fit that failed ("a local regression fit was automatically substituted")
         Scope t(c, "trend_fit");
         launch_trend_init(d, w, o, st);
-        rc = local_trend_fit(c, d, o);
+        rc = local_trend_fit(c, d, o, tree);
         if (rc == CHICDIFF_E_NUMERIC) {
             const int32_t one = 1;  // no local fit either (fewer than four usable rows): report the trend as failed
             HIPCHK(c, hipMemcpyAsync(&w.sc->failed, &one, sizeof one, hipMemcpyHostToDevice, st));
@@ -537,6 +523,43 @@ static int fit_pass(chicdiff_hip_ctx *c, const int32_t *d_counts, const double *
         c->host.fault_inject &= ~1;
         launch_poke(&w.sc->sel_overflow, 1, st);
     }
+    return CHICDIFF_OK;
+}
+
+// one pass of a fit, from the counts to the scalars on the host (c->h_sc); fit_dev_impl reads the verdicts and repeats it if need be
+static int fit_pass(chicdiff_hip_ctx *c, const int32_t *d_counts, const double *d_nf, FitDims d, const Opts &o,
+                    const chicdiff_nbglm_out *d_out, bool all_rounds) {
+    int rc;
+    hipStream_t st = c->stream;
+    FitWork &w = c->w;
+    c->tg_total = 0;
+    // the scalars, the queue heads and the barrier counters sit next to each other in the workspace: one fill
+    HIPCHK(c, hipMemsetAsync(w.sc, 0, align256(sizeof(FitScalars)) + kQueueBytes + 1024, st));
+    // sharded: the column sums of nf travel as the ranks' double-double pairs (zero-filled slots + sum-all-reduce = an exact gather)
+    // and are added in rank order — the correctly rounded exact sum, as on one rank: same xim, same start values, same bits downstream
+    const int world = c->world > 0 ? c->world : 1;
+    const bool col_slots = c->allreduce && world <= kSelMaxWorld;
+    const size_t slot_doubles = (size_t)(d.S + 1) * 2;
+    double *slots = col_slots ? w.hist : nullptr;  // (the select histograms are idle here)
+    if (col_slots) HIPCHK(c, hipMemsetAsync(slots, 0, sizeof(double) * slot_doubles * world, st));
+    {
+        Scope t(c, "prep");
+        const bool fused = c->fuse.fm != nullptr && d.S <= 16 && d_nf == c->d_nf_tmp;
+        const int nblk = launch_prep(d_counts, const_cast<double *>(d_nf), d, w, o, st, fused ? c->fuse : FusedOffsets(), c->host.prep_blocks);
+        launch_prep_finish(d, w, nblk, col_slots ? slots + slot_doubles * c->rank : nullptr, st);
+    }
+    if (col_slots) {
+        if ((rc = do_allreduce(c, slots, (int64_t)(slot_doubles * world)))) return rc;
+    } else if ((rc = do_allreduce(c, w.sc->colsum, kMaxS + 1)))  // colsum[kMaxS] + nnz are contiguous
+        return rc;
+    if (c->allreduce) launch_xim(d, w, slots, world, st);  // (the ranks' column sums, exchanged above, added in rank order -> xim)
+    {
+        Scope t(c, "disp_gene");
+        Opts og = o;
+        og.xim_here = c->allreduce ? 0 : 1;  // single rank: disp_init forms xim from the column sums itself (one dependent launch less)
+        launch_disp_gene(d_counts, d_nf, d, w, og, st);
+    }
+    if ((rc = global_stage(c, d, o, all_rounds, nullptr))) return rc;
     {
         Scope t(c, "disp_map");
         launch_disp_map(d_counts, d_nf, d, w, o, st);
@@ -577,6 +600,11 @@ static int fit_pass(chicdiff_hip_ctx *c, const int32_t *d_counts, const double *
     return CHICDIFF_OK;
 }
 
+// estimateDispersionsFit's answer to a parametric fit that failed (read from the scalars of the pass that just ended): fitType <- "local"
+bool cd::substitute_local_trend(const chicdiff_hip_ctx *c, const Opts &o) {
+    return c->h_sc->failed && o.fit_type == 0 && !(o.trendIn[0] == o.trendIn[0]) && c->host.local_trend_substitute;
+}
+
 // A fit: fit_pass, repeated while the verdicts of a pass ask for it.  all_rounds: the selects take every histogram round from the
 // first pass on (option "select_all_rounds", or the caller's own retry after an overflow of the size-factor select).
 static int fit_dev_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, const double *d_nf, FitDims d, Opts o,
@@ -601,7 +629,7 @@ static int fit_dev_impl(chicdiff_hip_ctx *c, const int32_t *d_counts, const doub
             // with other work): fit again with one launch per IRLS pass, and stay with that for this context
             if (c->no_persistent_trend) return fail(c, CHICDIFF_E_HIP, "trend fit: grid barrier timed out");
             c->no_persistent_trend = true;
-        } else if (c->h_sc->failed && o.fit_type == 0 && !(o.trendIn[0] == o.trendIn[0]) && c->host.local_trend_substitute) {
+        } else if (substitute_local_trend(c, o)) {
             // estimateDispersionsFit: the parametric fit failed -> fitType <- "local", and the fit is done again from the trend on
             // (everything before it is recomputed too: a rare path, kept simple)
             o.fit_type = 2;

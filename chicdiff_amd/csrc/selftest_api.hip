@@ -68,6 +68,94 @@ extern "C" int chicdiff_hip_selftest_objective_dev(chicdiff_hip_ctx *c, const in
     return CHICDIFF_OK;
 }
 
+// the fit's global stage (fit_api.hip global_stage) on the caller's columns: the workspace columns are filled from them, the stage runs
+// as in a pass of a fit, and what a fit does with the verdict of a failed parametric trend (fit_dev_impl) is done here the same way
+extern "C" int chicdiff_hip_selftest_global_stage_dev(chicdiff_hip_ctx *c, const double *d_baseMean, const double *d_dispGeneEst,
+                                                      const int32_t *d_allZero, int64_t n, int32_t S, int32_t p, const chicdiff_nbglm_opts *opts,
+                                                      double *d_dispFit, double *d_resid, double *hist40, int32_t *lf_nv, double *lf_x,
+                                                      double *lf_h, double *lf_f, double *lf_d, chicdiff_nbglm_scalars *scalars) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (!d_baseMean || !d_dispGeneEst || !d_allZero || !d_dispFit || !d_resid || !hist40 || !lf_nv || !lf_x || !lf_h || !lf_f || !lf_d || !scalars ||
+        n < 1 || n > 2147483647ll || S < 2 || S > kMaxS || p < 1 || p > 2 || S <= p)
+        return fail(c, CHICDIFF_E_INVALID, "selftest_global_stage: bad arguments");
+    if (c->allreduce) return fail(c, CHICDIFF_E_INVALID, "selftest_global_stage: single rank only");
+    if (int rc = check_opts(c, opts)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_workspace(c, n, S)) return rc;
+    FitDims d{};
+    d.n = n;
+    d.S = S;
+    d.p = p;
+    d.nB = p == 2 ? S / 2 : 0;  // (the stage reads n, S and p alone)
+    d.nA = S - d.nB;
+    Opts o = make_opts(c, opts, S);
+    FitWork &w = c->w;
+    hipStream_t st = c->stream;
+    LfTree tree;
+    c->refits = 0;
+    for (;;) {
+        c->tg_total = 0;
+        HIPCHK(c, hipMemsetAsync(w.sc, 0, align256(sizeof(FitScalars)) + kQueueBytes + 1024, st));
+        HIPCHK(c, hipMemcpyAsync(w.baseMean, d_baseMean, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(w.dispGene, d_dispGeneEst, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(w.allZero, d_allZero, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, hipMemsetAsync(w.dispFit, 0xff, sizeof(double) * (size_t)n, st));  // NaN: only a local trend writes the column in this stage
+        if (int rc = global_stage(c, d, o, c->host.select_all_rounds != 0, &tree)) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->h_sc, w.sc, sizeof(FitScalars), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        HIPCHK(c, hipGetLastError());
+        if (c->h_sc->failed == 3) {  // the persistent kernel's grid barrier timed out: one launch per pass, as fit_dev_impl answers it
+            if (c->no_persistent_trend) return fail(c, CHICDIFF_E_HIP, "trend fit: grid barrier timed out");
+            c->no_persistent_trend = true;
+        } else if (substitute_local_trend(c, o)) {
+            o.fit_type = 2;
+        } else
+            break;
+        c->refits++;
+    }
+    const bool mc = prior_by_simulation(d, o);
+    double *d_hist = resid_hist_of(w);
+    if (mc) HIPCHK(c, hipMemcpyAsync(hist40, d_hist, sizeof(double) * kPmcBins, hipMemcpyDeviceToHost, st));
+    else memset(hist40, 0, sizeof(double) * kPmcBins);
+    HIPCHK(c, hipMemcpyAsync(d_dispFit, w.dispFit, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_resid, w.resid, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    const FitScalars *s = c->h_sc;
+    *lf_nv = s->trend_local ? tree.nv : 0;
+    for (int i = 0; i < *lf_nv; i++) { lf_x[i] = tree.x[i]; lf_h[i] = tree.h[i]; lf_f[i] = tree.f[i]; lf_d[i] = tree.d[i]; }
+    memset(scalars, 0, sizeof *scalars);
+    int status = 0;
+    if (s->failed) status |= CHICDIFF_ST_TREND_FAILED;
+    if (s->trend_local) status |= CHICDIFF_ST_TREND_LOCAL;
+    if (mc) status |= CHICDIFF_ST_PRIORVAR_MC;
+    scalars->trendCoef[0] = s->coefs[0];
+    scalars->trendCoef[1] = s->coefs[1];
+    scalars->varLogDispEsts = s->varLogDispEsts;
+    scalars->dispPriorVar = s->dispPriorVar;
+    scalars->sumDeviance = NAN;
+    scalars->trendOuterIter = s->outer_it;
+    scalars->status = status;
+    return CHICDIFF_OK;
+}
+
+// launch_resid_hist (resid_hist_kernel, pmc_bin) on the caller's residual column
+extern "C" int chicdiff_hip_selftest_resid_hist_dev(chicdiff_hip_ctx *c, const double *d_resid, int64_t n, double *hist40) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (!d_resid || !hist40 || n < 1 || n > 2147483647ll) return fail(c, CHICDIFF_E_INVALID, "selftest_resid_hist: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_workspace(c, 1, 2)) return rc;
+    FitDims d{};
+    d.n = n;
+    FitWork wm = c->w;
+    wm.resid = const_cast<double *>(d_resid);  // (read only)
+    double *d_hist = resid_hist_of(c->w);
+    launch_resid_hist(d, wm, d_hist, c->stream);
+    HIPCHK(c, hipMemcpyAsync(hist40, d_hist, sizeof(double) * kPmcBins, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return CHICDIFF_OK;
+}
+
 // host-side self tests of the simulation-matched prior variance (no device involved)
 extern "C" int chicdiff_hip_selftest_r_random(int32_t kind, uint32_t seed, double a, double b, int64_t n, double *out) {
     if (!out || n < 0 || kind < 0 || kind > 3) return CHICDIFF_E_INVALID;

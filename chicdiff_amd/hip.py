@@ -41,7 +41,7 @@ EXPORTS = [
     "chicdiff_hip_rccl_unique_id", "chicdiff_hip_rccl_init", "chicdiff_hip_cooks_filter_dev",
     "chicdiff_hip_independent_filtering_dev",
     "chicdiff_hip_nbglm_fit_dev", "chicdiff_hip_nbglm_fit", "chicdiff_hip_wald_test_dev", "chicdiff_hip_theta_grid_dev",
-    "chicdiff_hip_wald_pvalues_dev", "chicdiff_hip_selftest_math_dev", "chicdiff_hip_selftest_math3_dev", "chicdiff_hip_selftest_objective_dev", "chicdiff_hip_selftest_r_random", "chicdiff_hip_selftest_sched_class", "chicdiff_hip_selftest_queue_claim", "chicdiff_hip_selftest_sf_bin",
+    "chicdiff_hip_wald_pvalues_dev", "chicdiff_hip_selftest_math_dev", "chicdiff_hip_selftest_math3_dev", "chicdiff_hip_selftest_objective_dev", "chicdiff_hip_selftest_global_stage_dev", "chicdiff_hip_selftest_resid_hist_dev", "chicdiff_hip_selftest_r_random", "chicdiff_hip_selftest_sched_class", "chicdiff_hip_selftest_queue_claim", "chicdiff_hip_selftest_sf_bin",
     "chicdiff_hip_selftest_prior_mc", "chicdiff_hip_selftest_chinput", "chicdiff_hip_kernel_times", "chicdiff_hip_enable_timing",
 ]
 
@@ -196,6 +196,9 @@ def load_library() -> C.CDLL:
     L.chicdiff_hip_selftest_math3_dev.argtypes = [vp, i32, vp, vp, i64, vp, vp]
     L.chicdiff_hip_selftest_objective_dev.argtypes = [vp, vp, vp, i64, i32, C.POINTER(i32), C.POINTER(Opts), vp, i32, vp, dbl, i32, vp, vp,
                                                       vp, vp, C.POINTER(i32)]
+    L.chicdiff_hip_selftest_global_stage_dev.argtypes = [vp, vp, vp, vp, i64, i32, i32, C.POINTER(Opts), vp, vp, C.POINTER(dbl), C.POINTER(i32),
+                                                         C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(Scalars)]
+    L.chicdiff_hip_selftest_resid_hist_dev.argtypes = [vp, vp, i64, C.POINTER(dbl)]
     L.chicdiff_hip_kernel_times.argtypes = [vp, C.POINTER(KernelTime), i32]
     L.chicdiff_hip_kernel_times.restype = i32
     L.chicdiff_hip_enable_timing.argtypes = [vp, i32]
@@ -1352,6 +1355,35 @@ class HipContext:
             d_log_alpha.data_ptr(), K, d_prior_mean.data_ptr() if d_prior_mean is not None else None, float(prior_var),
             int(live_rows), lp.data_ptr(), dlp.data_ptr(), alpha.data_ptr(), mu.data_ptr(), C.byref(lanes)))
         return dict(lp=lp, dlp=dlp, alpha=alpha, mu=mu, lanes_per_row=lanes.value)
+
+    def selftest_global_stage(self, d_baseMean, d_dispGeneEst, d_allZero, S, p, opts: Opts | None = None):
+        """TEST ENTRY: the fit's global stage (trend, residuals, median / MAD, prior variance) on the caller's columns.  Returns a dict:
+        dispFit, resid (device tensors, n), hist (40 counts), vertices (dict of nv and x, h, f, d: the local trend's, ascending x)
+        and the scalars with their status bits."""
+        t = self.torch
+        n = d_baseMean.numel()
+        self._check_tensor("d_baseMean", d_baseMean, t.float64, (n,))
+        self._check_tensor("d_dispGeneEst", d_dispGeneEst, t.float64, (n,))
+        self._check_tensor("d_allZero", d_allZero, t.int32, (n,))
+        fit, resid = (t.empty(n, dtype=t.float64, device=self.device) for _ in range(2))
+        hist = (C.c_double * 40)()
+        nv = C.c_int32(0)
+        vx, vh, vf, vd = ((C.c_double * 100)() for _ in range(4))
+        sc = Scalars()
+        self._check(self.lib.chicdiff_hip_selftest_global_stage_dev(
+            self.h, d_baseMean.data_ptr(), d_dispGeneEst.data_ptr(), d_allZero.data_ptr(), n, int(S), int(p),
+            C.byref(opts) if opts is not None else None, fit.data_ptr(), resid.data_ptr(), hist, C.byref(nv), vx, vh, vf, vd, C.byref(sc)))
+        k = nv.value
+        return dict(dispFit=fit, resid=resid, hist=np.array(hist[:]),
+                    vertices=dict(nv=k, x=np.array(vx[:k]), h=np.array(vh[:k]), f=np.array(vf[:k]), d=np.array(vd[:k])),
+                    scalars=_scalars_dict(sc))
+
+    def selftest_resid_hist(self, d_resid) -> np.ndarray:
+        """TEST ENTRY: the 40 counts of hist(x[x > -10 & x < 10], breaks = -20:20/2) over a device column, by the fit's kernel."""
+        self._check_tensor("d_resid", d_resid, self.torch.float64, (d_resid.numel(),))
+        hist = (C.c_double * 40)()
+        self._check(self.lib.chicdiff_hip_selftest_resid_hist_dev(self.h, d_resid.data_ptr(), d_resid.numel(), hist))
+        return np.array(hist[:])
 
     def wald_pvalues(self, d_stat):
         out = self.torch.empty_like(d_stat)

@@ -929,6 +929,25 @@ int chicdiff_hip_selftest_objective_dev(chicdiff_hip_ctx *ctx, const int32_t *d_
                                         const double *d_prior_mean, double prior_var, int32_t live_rows, double *d_lp, double *d_dlp,
                                         double *d_alpha, double *d_mu, int32_t *lanes_per_row);
 
+/* TEST ENTRY, not a product path.  The global stage of a fit — what lies between the gene-wise search and the MAP search: the trend
+ * (parametric, opts->fitType = 1 mean, 2 local, or opts->trendCoef given), the log residuals, their median and MAD, and the prior
+ * variance (closed form, opts->dispPriorVar given, or by simulation for S - p <= 3) — on the caller's device columns baseMean,
+ * dispGeneEst (NaN in all-zero rows) and allZero (n rows) instead of the columns the gene-wise search left.  The fit's own function
+ * runs on them, and a parametric trend that fails is answered as a fit answers it (option "local_trend_substitute").  Single rank only.
+ * Results: d_dispFit (n; the stage itself forms the column under a local trend only: NaN otherwise, and in all-zero rows),
+ * d_resid (n; NaN where dispGeneEst < 100 minDisp or the row is all zero), hist40 (HOST, 40: the counts the simulated prior was
+ * matched to; zero when the prior is not found by simulation), the local trend's vertices in ascending x (HOST: *lf_nv, and lf_x,
+ * lf_h, lf_f, lf_d of 100 doubles each: position, bandwidth, value, slope; *lf_nv = 0 without a local trend), and scalars:
+ * trendCoef, varLogDispEsts, dispPriorVar, trendOuterIter and the status bits CHICDIFF_ST_TREND_FAILED / _TREND_LOCAL / _PRIORVAR_MC
+ * (sumDeviance NaN, nAllZero 0: not of this stage).  A mean trend without a usable row: CHICDIFF_E_NUMERIC, as in a fit. */
+int chicdiff_hip_selftest_global_stage_dev(chicdiff_hip_ctx *ctx, const double *d_baseMean, const double *d_dispGeneEst,
+                                           const int32_t *d_allZero, int64_t n, int32_t S, int32_t p, const chicdiff_nbglm_opts *opts,
+                                           double *d_dispFit, double *d_resid, double *hist40, int32_t *lf_nv, double *lf_x, double *lf_h,
+                                           double *lf_f, double *lf_d, chicdiff_nbglm_scalars *scalars);
+/* TEST ENTRY.  hist40 (HOST, 40) = the counts of hist(x[x > -10 & x < 10], breaks = -20:20/2) over the device column d_resid (n; NaN =
+ * no residual), by the kernel the simulated prior counts its residuals with. */
+int chicdiff_hip_selftest_resid_hist_dev(chicdiff_hip_ctx *ctx, const double *d_resid, int64_t n, double *hist40);
+
 /* Host-side self tests of the pieces behind CHICDIFF_ST_PRIORVAR_MC (no device, no context).
  * _r_random: set.seed(seed) followed by n draws of kind 0 runif(n), 1 rnorm(n), 2 rexp(n), 3 rgamma(n, shape = a,
  * scale = b) from R's default generators (Mersenne-Twister, inversion).

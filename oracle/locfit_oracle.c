@@ -21,6 +21,8 @@
 
 #include "oracle.h"
 
+#define ORACLE_LOCFIT_SINGULAR 0x1p-40L /* far above the rounding of the moments (double sums), far below any pivot that leaves a digit */
+
 static double kth_smallest(double *a, int64_t n, int64_t k) { /* 1-based k; reorders a (quickselect) */
     int64_t lo = 0, hi = n - 1, want = k - 1;
     while (lo < hi) {
@@ -64,16 +66,25 @@ static int vertex_fit(const double *x, const double *y, const double *w, int64_t
     }
     /* normal equations in the basis 1, dx, dx^2/2 */
     long double A[3][4] = {{S[0], S[1], S[2] / 2, T[0]}, {S[1], S[2], S[3] / 2, T[1]}, {S[2] / 2, S[3] / 2, S[4] / 4, T[2] / 2}};
-    for (int c = 0; c < 3; c++) { /* Gaussian elimination with partial pivoting */
+    /* Gaussian elimination with partial pivoting.  B carries the sum of the absolute values of the terms an entry was formed from: a
+     * pivot that is no more than ORACLE_LOCFIT_SINGULAR of that sum is what rounding left of an exact zero (fewer than three distinct
+     * x carry weight: the exact system is singular), not a pivot */
+    long double B[3][4];
+    for (int r = 0; r < 3; r++)
+        for (int q = 0; q < 4; q++) B[r][q] = fabsl(A[r][q]);
+    for (int c = 0; c < 3; c++) {
         int piv = c;
         for (int r = c + 1; r < 3; r++)
             if (fabsl(A[r][c]) > fabsl(A[piv][c])) piv = r;
-        if (!(fabsl(A[piv][c]) > 0)) return 1;
+        if (!(fabsl(A[piv][c]) > ORACLE_LOCFIT_SINGULAR * B[piv][c])) return 1;
         if (piv != c)
-            for (int q = 0; q < 4; q++) { const long double t = A[c][q]; A[c][q] = A[piv][q]; A[piv][q] = t; }
+            for (int q = 0; q < 4; q++) {
+                long double t = A[c][q]; A[c][q] = A[piv][q]; A[piv][q] = t;
+                t = B[c][q]; B[c][q] = B[piv][q]; B[piv][q] = t;
+            }
         for (int r = c + 1; r < 3; r++) {
             const long double m = A[r][c] / A[c][c];
-            for (int q = c; q < 4; q++) A[r][q] -= m * A[c][q];
+            for (int q = c; q < 4; q++) { A[r][q] -= m * A[c][q]; B[r][q] += fabsl(m) * B[c][q]; }
         }
     }
     long double b[3];

@@ -452,6 +452,20 @@ static double trimmed_mean(double *v, int n, double trim) {
     return s / (hi - lo);
 }
 
+/* mean(v, trim = 0.001) of the m usable gene-wise estimates (reorders v): 0 and *mean_out, or 4 when there is none */
+int oracle_trimmed_mean_dispersion(double *v, int64_t m, double *mean_out) {
+    if (m <= 0) return 4;
+    qsort(v, (size_t)m, sizeof(double), cmp_double);
+    const int64_t lo = (int64_t)floor((double)m * 0.001), hi = m - lo;
+    long double acc = 0;
+    for (int64_t k = lo; k < hi; k++) acc += v[k];
+    long double mean = acc / (long double)(hi - lo), t = 0;
+    for (int64_t k = lo; k < hi; k++) t += v[k] - mean;
+    mean += t / (long double)(hi - lo);
+    *mean_out = (double)mean;
+    return 0;
+}
+
 static int trim_bin(int n) { return n <= 3 ? 0 : (n <= 23 ? 1 : 2); } /* cut(n, c(0,3.5,23.5,Inf)) */
 
 /* A5 Cook's: robustMethodOfMomentsDisp (trimmedCellVariance over cells with >=3 samples, floor 0.04) */
@@ -602,18 +616,8 @@ int oracle_nbglm_fit(const int32_t *counts, const double *nf, int64_t n, int32_t
         int64_t m = 0;
         for (int64_t i = 0; i < n; i++)
             if (!allZero[i] && dispGene[i] > 10 * o.minDisp) fd[m++] = dispGene[i];
-        if (m == 0) trc = 4;
-        else {
-            qsort(fd, (size_t)m, sizeof(double), cmp_double);
-            const int64_t lo = (int64_t)floor((double)m * 0.001), hi = m - lo;
-            long double acc = 0;
-            for (int64_t k = lo; k < hi; k++) acc += fd[k];
-            long double mean = acc / (long double)(hi - lo), t = 0;
-            for (int64_t k = lo; k < hi; k++) t += fd[k] - mean;
-            mean += t / (long double)(hi - lo);
-            coefs[0] = (double)mean;
-            coefs[1] = 0.0;
-        }
+        if (oracle_trimmed_mean_dispersion(fd, m, &coefs[0])) trc = 4;
+        else coefs[1] = 0.0;
     } else if (o.fitType != 2)
         trc = nfit > 0 ? oracle_parametric_dispersion_fit(fm, fd, nfit, coefs, &outer) : 4;
     /* estimateDispersionsFit: fitType = "local" on request, and as the substitute for a failed parametric fit

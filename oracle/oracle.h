@@ -140,8 +140,10 @@ int oracle_fragment_background(const int32_t *bait, const int32_t *oe, int64_t n
 int oracle_bh_adjust(const double *p, int64_t n, double *padj);
 
 /* A4, residual d.f. <= 3: simulation-matched prior variance (prior_mc_oracle.c) */
+int oracle_trimmed_mean_dispersion(double *v, int64_t m, double *mean_out); /* fitType "mean": mean(v, trim = 0.001); reorders v */
 int oracle_prior_mc_bin(double x);
 double oracle_prior_var_mc(const double *obs_counts /*[40]*/, int df);
+double oracle_prior_var_mc_trace(const double *obs_counts /*[40]*/, int df, double *kl_out /*[200]*/, double *fit_out /*[1000]*/);
 int oracle_prior_mc_table(int df, double *out /*[200*40]*/);
 /* loess(y ~ x, span, degree = 2, family = "gaussian", surface = "interpolate", cell) on sorted distinct x[n],
  * predicted at z[nz] (inside the range of x); returns the number of k-d tree vertices or < 0 */

@@ -382,10 +382,31 @@ def count_table(bait, oe, N, bait_in_RU=None):
     return keys[order], v[order]
 
 
+def mean_dispersion(disps, min_disp=1e-8):
+    """fitType "mean": mean(disps[disps > 10 minDisp], trim = 0.001) (NaN = all-zero row), or None when no estimate is usable."""
+    d = np.asarray(disps, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        v = np.ascontiguousarray(d[d > 10 * min_disp])
+    out = C.c_double(0.0)
+    L = lib()
+    L.oracle_trimmed_mean_dispersion.argtypes = [_PD, C.c_int64, C.POINTER(C.c_double)]
+    return None if L.oracle_trimmed_mean_dispersion(_pd(v), len(v), C.byref(out)) else out.value
+
+
 def prior_var_mc(residuals, df):
     """Simulation-matched dispPriorVar for residual d.f. <= 3 from the log dispersion residuals."""
     r = np.asarray(residuals, dtype=np.float64)
     return lib().oracle_prior_var_mc(_pd(prior_mc_hist(r)), int(df))
+
+
+def prior_var_mc_trace(hist40, df):
+    """(dispPriorVar, the 200 KL sums, the 1 000 loess values) of the simulation-matched prior for the 40 counts `hist40`."""
+    h = np.ascontiguousarray(hist40, dtype=np.float64)
+    kl, fit = np.empty(200), np.empty(1000)
+    L = lib()
+    L.oracle_prior_var_mc_trace.restype = C.c_double
+    L.oracle_prior_var_mc_trace.argtypes = [_PD, C.c_int32, _PD, _PD]
+    return L.oracle_prior_var_mc_trace(_pd(h), int(df), _pd(kl), _pd(fit)), kl, fit
 
 
 def prior_mc_hist(residuals) -> np.ndarray:

@@ -175,7 +175,7 @@ int oracle_loess_interp(const double *x, const double *y, int n, double span, do
 }
 
 /* obs_counts[40]: histogram (oracle_prior_mc_bin) of the log dispersion residuals; df = m - p in 1..3 */
-double oracle_prior_var_mc(const double *obs_counts, int df) {
+static double prior_var_mc(const double *obs_counts, int df, double *kl_out, double *fit_out) {
     if (df < 1 || df > 3) return NAN;
 #pragma omp critical(oracle_prior_mc)
     if (!g_ready[df]) build(df);
@@ -197,8 +197,15 @@ double oracle_prior_var_mc(const double *obs_counts, int df) {
     }
     for (int f = 0; f < NF; f++) zs[f] = f == NF - 1 ? 8.0 : f * (8.0 / (NF - 1));
     oracle_loess_interp(xs, kl, NG, 0.2, 0.2, zs, NF, fit);
+    if (kl_out) memcpy(kl_out, kl, sizeof kl);
+    if (fit_out) memcpy(fit_out, fit, sizeof fit);
     double best = INFINITY, arg = 0;
     for (int f = 0; f < NF; f++)
         if (fit[f] < best) { best = fit[f]; arg = zs[f]; } /* which.min: the first minimum */
     return arg > 0.25 ? arg : 0.25;
+}
+double oracle_prior_var_mc(const double *obs_counts, int df) { return prior_var_mc(obs_counts, df, NULL, NULL); }
+/* the same, with the 200 KL sums and the 1 000 loess values it went through (either may be NULL) */
+double oracle_prior_var_mc_trace(const double *obs_counts, int df, double *kl_out, double *fit_out) {
+    return prior_var_mc(obs_counts, df, kl_out, fit_out);
 }

@@ -313,12 +313,30 @@ def _gamma_identity_glm(x, yv, start, eps=mp.mpf(1e-8), maxit=25):
     return (c0, c1), conv, kappa, closest
 
 
-def global_stage(baseMean, dispGeneEst, S, p, coefs=None):
+def mad_stage(x, ux):
+    """varLogDispEsts = (1.4826 mad)^2 of the residuals x = {row: value} with units ux = {row: unit}.  Returns (v, median, mad, unit of v).
+    The medians are order statistics: their error is that of the elements next to them — bounded here by the largest unit among the
+    residuals within one mad-width of the two medians, twice (median and deviation), relative to mad, twice again for the square."""
+    keep = list(x)
+    med = _median([x[i] for i in keep])
+    mad = _median([abs(x[i] - med) for i in keep])
+    v = (mp.mpf(1.4826) * mad) ** 2
+    near_el = [ux[i] for i in keep if abs(abs(x[i] - med) - mad) <= mad / 8 or abs(x[i] - med) <= mad / 8]
+    if mad == 0:  # every residual between the two medians is one value: v = 0, and an error of the elements enters squared
+        return v, med, mad, (mp.mpf(1.4826) * 2 * (2 * max(near_el) + U * abs(med))) ** 2
+    u_v = 2 * v * (2 * max(near_el) + U * (abs(med) + mad)) / mad + U * v
+    return v, med, mad, u_v
+
+
+def global_stage(baseMean, dispGeneEst, S, p, coefs=None, dens=None):
     """Trend, dispFit, varLogDispEsts and dispPriorVar from the REPORTED baseMean and dispGeneEst (doubles, taken as exact; NaN rows —
     all-zero rows — are left out).  `coefs` given: the trend is not fitted (the pinned cases).  Returns dict(coefs, rounds (glm calls;
     None when the trend failed: a coefficient <= 0 or more than 10 rounds), failed, dispFit (per row given, None for NaN rows),
-    varLogDispEsts, dispPriorVar (None when m - p <= 3: found by simulation, not here), unit = {coefs: (u0, u1), dispFit: [..],
-    varLogDispEsts, dispPriorVar}, near = the smallest relative distance of any filter ratio from 1e-4 / 15, of the outer test from
+    varLogDispEsts, dispPriorVar (m - p <= 3: matched by simulation, tests/trend_twin.prior_var_mc on the histogram of the residuals
+    and the simulated densities `dens`, by default those of the library's host entry; `prior` then holds that function's result and
+    `hist` the counts with each residual's distance from a break), unit = {coefs: (u0, u1), dispFit: [..], varLogDispEsts,
+    dispPriorVar (m - p <= 3: one unit of the grid value — the result is a grid point, right or wrong)}, near = the smallest
+    relative distance of any filter ratio from 1e-4 / 15, of the outer test from
     1e-6 and of a glm convergence test from 1e-8)."""
     rows = [i for i in range(len(baseMean)) if baseMean[i] == baseMean[i] and dispGeneEst[i] == dispGeneEst[i]]
     bm = {i: mp.mpf(float(baseMean[i])) for i in rows}
@@ -360,13 +378,7 @@ def global_stage(baseMean, dispGeneEst, S, p, coefs=None):
     keep = [i for i in rows if al[i] >= mp.mpf(100 * MIN_DISP)]
     x = {i: mp.log(al[i]) - mp.log(fit[i]) for i in keep}
     ux = {i: U * (abs(mp.log(al[i])) + abs(mp.log(fit[i]))) + u_fit[i] / fit[i] for i in keep}
-    med = _median([x[i] for i in keep])
-    mad = _median([abs(x[i] - med) for i in keep])
-    v = (mp.mpf(1.4826) * mad) ** 2
-    # the medians are order statistics: their error is that of the elements next to them — bounded here by the largest unit among the
-    # residuals within one mad-width of the two medians, twice (median and deviation), relative to mad, twice again for the square
-    near_el = [ux[i] for i in keep if abs(abs(x[i] - med) - mad) <= mad / 8 or abs(x[i] - med) <= mad / 8]
-    u_v = 2 * v * (2 * max(near_el) + U * (abs(med) + mad)) / mad + U * v
+    v, med, mad, u_v = mad_stage(x, ux)
     res.update(varLogDispEsts=v, residual_median=med, mad=mad)
     m = S - p
     tri = mp.polygamma(1, mp.mpf(m) / 2)
@@ -375,7 +387,12 @@ def global_stage(baseMean, dispGeneEst, S, p, coefs=None):
         res["dispPriorVar"] = pv if pv > mp.mpf(0.25) else mp.mpf(0.25)
         u_pv = u_v + U * (v + tri)
     else:
-        res["dispPriorVar"], u_pv = None, None
+        import trend_twin as tt
+        n = len(baseMean)
+        counts, info = tt.resid_hist([x.get(i) for i in range(n)], [ux.get(i) for i in range(n)])
+        pm = tt.prior_var_mc(counts, tt.simulated_densities(m) if dens is None else dens, m, var_log_disp_ests=v)
+        res.update(dispPriorVar=pm["value"], prior=pm, hist=(counts, info))
+        u_pv = U * pm["value"]
     res["unit"] = dict(coefs=(U * kappa * abs(c[0]), U * kappa * abs(c[1])), dispFit=[u_fit.get(i) for i in range(len(baseMean))], varLogDispEsts=u_v,
                        dispPriorVar=u_pv)
     return res

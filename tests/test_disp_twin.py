@@ -299,8 +299,8 @@ def rejected(res, bound=SEPARATION):
 
 
 def judge_global(fit, columns, scalars, oracle_yard=None):
-    """The global stage of a free fit: trend coefficients, trendOuterIter, dispFit, varLogDispEsts and dispPriorVar (m - p > 3) against
-    the twin on the fit's own baseMean and dispGeneEst.  Returns dict(errors {quantity: error in units}, violations, near)."""
+    """The global stage of a free fit: trend coefficients, trendOuterIter, dispFit, varLogDispEsts and dispPriorVar against
+    the twin on the fit's own baseMean and dispGeneEst; m - p <= 3: the prior matched by simulation, a grid point, exactly.  Returns dict(errors {quantity: error in units}, violations, near)."""
     with mp.workdps(dt.DPS):
         S = fit["S"]
         p = 2 if fit["group"].any() else 1
@@ -319,7 +319,19 @@ def judge_global(fit, columns, scalars, oracle_yard=None):
         for k in (0, 1):
             res["errors"][f"trendCoef[{k}]"] = float(abs(mp.mpf(float(scalars["trendCoef"][k])) - gs["coefs"][k]) / gs["unit"]["coefs"][k])
         res["errors"]["varLogDispEsts"] = float(abs(mp.mpf(float(scalars["varLogDispEsts"])) - gs["varLogDispEsts"]) / gs["unit"]["varLogDispEsts"])
-        if gs["dispPriorVar"] is not None:
+        pm = gs.get("prior")
+        if pm is not None and not pm["closed_form"]:
+            # m - p <= 3: the value is a point of the fine grid, max(argmin, 0.25) — the twin's, or the runner-up's where the two fitted
+            # values lie within NEAR_UNITS units of each other
+            pv = float(scalars["dispPriorVar"])
+            if pv != float(pm["value"]):
+                import trend_twin as tt
+                if pm["gap"][0] <= NEAR_UNITS * pm["gap"][1] and pv == float(max(tt.grid_x(pm["runner_up"], tt.FINE), mp.mpf(0.25))):
+                    res["near"] += 1
+                else:
+                    res["violations"].append((-1, "argmin of the simulated prior", (pv, float(pm["value"]), pm["argmin"])))
+            res["errors"]["dispPriorVar"] = 0.0
+        else:
             res["errors"]["dispPriorVar"] = float(abs(mp.mpf(float(scalars["dispPriorVar"])) - gs["dispPriorVar"]) / gs["unit"]["dispPriorVar"])
         # dispFit against the REPORTED coefficients: the row formula on its own inputs
         c0, c1 = (mp.mpf(float(v)) for v in scalars["trendCoef"])
@@ -433,7 +445,7 @@ def test_global_stage_of_the_oracle(oracle):
         res = judge_global(fit, ref, ref)
         print(f"{name}: {time.perf_counter() - t0:.1f} s; rounds {res['twin']['rounds']}, closest decision {float(res['twin']['near']):.3g}; {res['errors']}")
         assert not res["violations"] and res["near"] == 0, res["violations"]
-        assert (fit["S"] - 2 > 3) == ("dispPriorVar" in res["errors"])
+        assert "dispPriorVar" in res["errors"]  # (m - p <= 3 too: matched by simulation, tests/trend_twin.py)
         assert all(e < SEPARATION for e in res["errors"].values()), res["errors"]
 
 
