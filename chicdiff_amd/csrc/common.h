@@ -42,6 +42,10 @@ struct FitWork {
     FitScalars *sc;
     const double *logfact;        // log(k!) for k < kLogFactN
 };
+// the fixed-order sums of a reduction pass sit behind the block partials: 128 doubles (the trend's sums first; from + 32 the
+// residual histogram of the simulated prior, ctx.h resid_hist_of).  By value, as the kernels take it: with a reference to their
+// argument, trend_reduce_kernel and trend_step_kernel compile to other code (tools/device_code_diff.py)
+__host__ __device__ inline double *sums_of(FitWork w) { return w.partials + (size_t)kRedBlocks * 72; }
 constexpr int kLogFactN = 1024;
 constexpr int kQueueBytes = 2048;  // FitWork::queue
 // ---- filler waves of the gene-wise line search (disp_kernels.hip, "front waves and fillers") ----
@@ -186,6 +190,7 @@ __device__ __forceinline__ void class_peers(int c, bool valid, int lane, unsigne
 #endif
 
 // ---- launchers (defined in the .hip files; all enqueue on `st` and never synchronise) -------
+// disp_kernels.hip — prep, the gene-wise and MAP dispersion searches, their schedule
 // fm != NULL (S <= 16): the offsets are formed here, from FullMean — sc(theta) of chicdiff.R:1635-1638 / M3 of :1583-1589, the very
 // function offsets16_kernel runs — written to `nf` (the stages behind read them from there) and used at once: one read and one
 // launch less than offsets + prep (round 5)
@@ -197,6 +202,7 @@ void launch_xim(FitDims d, FitWork w, const double *slots, int world, hipStream_
 void launch_disp_gene(const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o, hipStream_t st);
 void launch_order_build(FitDims d, FitWork w, int classesA, bool have_hist, hipStream_t st, bool fine = false);  // w.cls -> w.order (schedule of a row-queue kernel; fine: kSchedClassesFine classes)
 void launch_disp_map(const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o, hipStream_t st);
+// trend_kernels.hip — dispersion trend, residuals and MAD, local fit, prior variance
 // single rank (or the gathered rows of a sharded fit): whole trend fit, one launch; with_mad: the same launch goes on to the residuals,
 // their median and MAD and the closed-form prior variance (w.resid, sc->med / nres / mad / varLogDispEsts / dispPriorVar)
 void launch_trend_persistent(FitDims d, FitWork w, Opts o, hipStream_t st, bool with_mad);
@@ -222,6 +228,7 @@ void launch_dispfit_resid(FitDims d, FitWork w, Opts o, hipStream_t st);
 void launch_prior_var(FitDims d, FitWork w, Opts o, hipStream_t st);
 void launch_resid_hist(FitDims d, FitWork w, double *out40, hipStream_t st);  // residual histogram for the d.f. <= 3 prior
 void launch_prior_mc(FitDims d, FitWork w, const double *hist40, const void *table, hipStream_t st);  // simulation-matched prior variance
+// wald_kernels.hip — the Wald stage and the fit's closing sums
 void launch_wald_prep(const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o, hipStream_t st);
 void launch_wald_irls(const int32_t *counts, const double *nf, FitDims d, FitWork w, Opts o, hipStream_t st);
 // row_constant: sum_j y_j log(alpha mu_j) of a row the IRLS converged on from wald_prep's row constant (option "wald_final_row_constant")
@@ -233,7 +240,8 @@ void launch_wald_intercept(const int32_t *counts, const double *nf, FitDims d, F
 // carry: overflow flag of the size-factor select the caller ran before the fit (may be NULL); sf_dev: its size factors (may be NULL)
 void launch_dev_sum_finish(FitDims d, FitWork w, const int32_t *carry, const double *sf_dev, hipStream_t st);
 
-// radix select over keys produced on the fly; `mode` (SelMode, fit_driver.h) picks the key generator
+// global_kernels.hip — exact medians over all rows: radix select over keys produced on the fly; `mode` (SelMode, fit_driver.h) picks the
+// key generator
 struct SelArgs {
     int mode;
     int ncol;               // columns selected simultaneously (1, or S for size factors)
@@ -285,6 +293,7 @@ __host__ __device__ inline int sf_sub_bin(double x, int nb, int b) {
 // log_table: both passes take log k of a count k < kSfLogK from a table the workgroup fills in LDS (option "sf_log_table")
 void launch_sf_direct(const int32_t *counts, int64_t n, int S, SelArgs a, FitWork w, unsigned int *hist, uint64_t *lists,
                       int32_t *clear_flag, int cus, int log_table, hipStream_t st);
+// region_kernels.hip — offsets, window sums, count join, background, region assembly
 void launch_offsets(const double *fullMean, const double *sf_dev, int64_t n, int S, double theta, int mix,
                     double *out, hipStream_t st);
 void launch_window_sums(const int32_t *fragN, const double *fragFM, int64_t nfrag, int S, const int64_t *rptr,
@@ -296,6 +305,14 @@ void launch_fragment_background(const int32_t *bait, const int32_t *oe, int64_t 
                                 const int64_t *midsum, int32_t S, const double *sj, const double *si, const int32_t *tblb,
                                 const int32_t *tlb, const double *T, int32_t ntblb, int32_t ntlb, const double *distfun_dev,
                                 double *bmean, double *tmean, double *fullmean, hipStream_t st);
+size_t count_join_multi_scratch_bytes(int S, const int64_t *nkeys);
+void launch_count_join_multi(const int32_t *bait, const int32_t *oe, int64_t nru, int S, const int64_t *const *keys, const int32_t *const *vals,
+                             const int64_t *nkeys, int32_t *out, void *scratch, hipStream_t st);
+hipError_t launch_region_assemble(const int32_t *bait, const int32_t *oe, int64_t nru, const int64_t *rptr, int64_t n, int S,
+                                  const int64_t *const *keys, const int32_t *const *vals, const int64_t *nkeys, int32_t id_min, int32_t nid,
+                                  const int64_t *midsum, const double *sj, const double *si, const int32_t *tblb, const int32_t *tlb,
+                                  const double *T, int32_t ntblb, int32_t ntlb, const double *distfun_dev, int32_t *N, double *FM,
+                                  void *scratch, int force_generic, hipStream_t st);
 // post_kernels.hip
 size_t bh_workspace_bytes(int64_t n);
 int launch_bh_adjust(const double *p, int64_t n, double *padj, char *ws, hipStream_t st);
@@ -319,16 +336,9 @@ void launch_ru_fill(const int32_t *bait, const int32_t *oe, int64_t n, int s, co
                     const unsigned int *mask_in = nullptr);  // mask_in: launch_ru_count's masks (NULL: recomputed)
 void launch_region_avdist(const int32_t *bait, const int32_t *oe, const int64_t *ptr, int64_t n, int32_t id_min, int32_t nid,
                           const int64_t *midsum, const int32_t *chr, double *avDist, hipStream_t st);
-size_t count_join_multi_scratch_bytes(int S, const int64_t *nkeys);
-void launch_count_join_multi(const int32_t *bait, const int32_t *oe, int64_t nru, int S, const int64_t *const *keys, const int32_t *const *vals,
-                             const int64_t *nkeys, int32_t *out, void *scratch, hipStream_t st);
-hipError_t launch_region_assemble(const int32_t *bait, const int32_t *oe, int64_t nru, const int64_t *rptr, int64_t n, int S,
-                                  const int64_t *const *keys, const int32_t *const *vals, const int64_t *nkeys, int32_t id_min, int32_t nid,
-                                  const int64_t *midsum, const double *sj, const double *si, const int32_t *tblb, const int32_t *tlb,
-                                  const double *T, int32_t ntblb, int32_t ntlb, const double *distfun_dev, int32_t *N, double *FM,
-                                  void *scratch, int force_generic, hipStream_t st);
 void launch_count_join_inner(const int32_t *bait, const int32_t *oe, int64_t nru, int S, const int64_t *const *keys,
                              const int32_t *const *vals, const int64_t *nkeys, int32_t *out, hipStream_t st);
+void launch_pvalues(const double *stat, int64_t n, double *p, hipStream_t st);
 // candidate_kernels.hip — getCandidateInteractions (chicdiff.R:2068-2163)
 struct CandArgs {
     const int32_t *bait, *minOE, *maxOE;  // region table, caller's row order
@@ -420,9 +430,7 @@ int launch_chinput_count(const unsigned char *text, int64_t nbytes, char *ws, hi
 int launch_chinput_scan(int64_t nbytes, char *ws, hipStream_t st);
 void launch_chinput_parse(const unsigned char *text, int64_t nbytes, int ib, int io, int in, int32_t *bait, int32_t *oe, int32_t *N, int64_t cap,
                           char *ws, hipStream_t st);
-void launch_math_selftest(int op, const double *x, int64_t n, double *out, hipStream_t st);
-void launch_math3_selftest(int op, const double *x, const double *y, int64_t n, const double *logfact, double *out, double *out2, hipStream_t st);
-// the dispersion objective on its own (disp_kernels.hip, objective_probe_kernel): K points a[i * K + k] per row of a prepared fit
+// objective_probe.hip — the dispersion objective on its own (objective_probe_kernel): K points a[i * K + k] per row of a prepared fit
 // (w.rowpack: launch_prep), evaluated row per lane (live_rows = 0) or with `live_rows` rows per wave in the samples-across-lanes layout the
 // line search would choose for that many; returns the lanes per row of that layout (1: row per lane), or -1 if the search has no
 // samples-across-lanes layout for that S and number of rows (nothing is launched then)
@@ -436,7 +444,9 @@ struct ObjectiveProbe {
     double *mu;                // S x n: the means the row's evaluations used
 };
 int launch_objective_probe(FitDims d, FitWork w, Opts o, const ObjectiveProbe &pb, hipStream_t st);
-void launch_pvalues(const double *stat, int64_t n, double *p, hipStream_t st);
+// selftest_kernels.hip — the device math on its own (tests)
+void launch_math_selftest(int op, const double *x, int64_t n, double *out, hipStream_t st);
+void launch_math3_selftest(int op, const double *x, const double *y, int64_t n, const double *logfact, double *out, double *out2, hipStream_t st);
 // table_text_kernels.hip — a table of device columns as text (the rule: include/chicdiff_hip.h, above chicdiff_hip_table_text_dev).
 // The descriptors travel as a kernel argument (2 KiB): every lane reads the same one, through the scalar cache.
 struct TtCol {

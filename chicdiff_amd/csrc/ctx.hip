@@ -354,7 +354,7 @@ int cd::ensure_workspace(chicdiff_hip_ctx *c, int64_t n, int S) {
     }
     const size_t nd = align256(sizeof(double) * (size_t)n), ni = align256(sizeof(int32_t) * (size_t)n);
     const size_t n_double_arrays = 15, n_int_arrays = 9;
-    const size_t partials = align256(sizeof(double) * ((size_t)kRedBlocks * 72 + 128));
+    const size_t partials = align256(sizeof(double) * ((size_t)kRedBlocks * 72 + 128));  // the block partials, then the sums (common.h sums_of)
     const size_t hist = align256(sizeof(double) * (size_t)kMaxS * 2 * kSelBins);
     const size_t nfbytes = align256(sizeof(double) * (size_t)n * S);
     const size_t selcnt = align256(sizeof(double) * (size_t)kSelMaxWorld * kMaxS * 2);

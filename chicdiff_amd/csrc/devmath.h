@@ -351,7 +351,7 @@ __device__ __forceinline__ double pnorm_two_sided(double z) {
 // gives and the NA-row rule of chicdiff.R:1588 reads), the common positive case the table logarithm
 __device__ __forceinline__ double rlog_t(double x, const LogEntry *lt) { return (x > 2.3e-308 && x < 1.7e308) ? tlog(x, lt) : log(x); }
 // a4 — one row of the offsets (chicdiff.R:1583-1589 M3, :1635-1638 / :1666-1669 the theta mix): v[0..S) = FullMean in, the
-// normalisation factors out.  Shared by offsets16_kernel and by prep16_kernel's fused form (global_kernels.hip / disp_kernels.hip),
+// normalisation factors out.  Shared by offsets16_kernel and by prep16_kernel's fused form (region_kernels.hip / disp_kernels.hip),
 // so that the two produce the same bits.  S <= N <= 16; sf: the size factors (nullSizeFactors), wave-uniform loads.  N (4, 8 or 16) is
 // the length of the register array, the sample class of the launch: the operations on the samples j < S and their order are the
 // same for every N, so a row gets the same bits from every class that holds it — a shorter array only frees registers.

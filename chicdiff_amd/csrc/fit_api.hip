@@ -7,7 +7,6 @@
 
 #include "ctx.h"
 
-static double *sums_of(const FitWork &w) { return w.partials + (size_t)kRedBlocks * 72; }
 double *cd::resid_hist_of(const FitWork &w) { return sums_of(w) + 32; }
 
 // ---- HIP backend of fit_driver.h -----------------------------------------------------------
@@ -164,7 +163,7 @@ Opts cd::make_opts(const chicdiff_hip_ctx *c, const chicdiff_nbglm_opts *in, int
     return r;
 }
 
-// ---- DESeq2 localDispersionFit on the device (global_kernels.hip lf_*): the host grows locfit's tree ----------------
+// ---- DESeq2 localDispersionFit on the device (trend_kernels.hip lf_*): the host grows locfit's tree ----------------
 // One order statistic of key(x) or key(|x - xv|) over the rows of the fit: byte-wise radix select, eight histogram rounds
 // (each a sum over rows, all-reduced when sharded).  rank is 0-based; *total gets the number of rows (first round).
 static int lf_order_stat(chicdiff_hip_ctx *c, FitDims d, const Opts &o, int use_dist, double xv, double rank, double *value, double *total) {

@@ -16,6 +16,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "devmath.h"
 
 namespace cd {
 
@@ -437,6 +438,16 @@ void launch_count_join_inner(const int32_t *bait, const int32_t *oe, int64_t nru
 // with its defaults).  Host numpy needs ~5 s for 2 M rows (50 filtered BH passes); here the
 // 50 rejection counts come from ONE sort by p-value and a 50-wide prefix count.
 namespace cd {
+
+__global__ __launch_bounds__(256) void pvalue_kernel(const double *__restrict__ stat, int64_t n, double *__restrict__ p) {
+    for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = pnorm_two_sided(stat[i]);
+}
+void launch_pvalues(const double *stat, int64_t n, double *p, hipStream_t st) {
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    pvalue_kernel<<<(unsigned)blocks, 256, 0, st>>>(stat, n, p);
+}
 
 // p <- NA for Cook's outliers: maxCooks > cutoff, unless (two-group design) at least 3 counts of the row exceed the
 // count of the sample with the largest Cook's distance (then the outlier is a low count and the p-value stays)

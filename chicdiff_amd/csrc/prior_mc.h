@@ -17,7 +17,7 @@
 // two middle points until <= floor(200 * .2 * .2) = 8 points; bounding box widened by 0.5 %), at each of its 33
 // vertices a local quadratic tricube fit over the 40 nearest grid values giving value and slope, cubic Hermite
 // blending inside a cell.  The vertex operator (2 x 40 coefficients per vertex) is built once on the host; the
-// device applies it (prior_mc_kernel in global_kernels.hip).
+// device applies it (prior_mc_kernel in trend_kernels.hip).
 #pragma once
 #include <math.h>
 #include <stdint.h>

@@ -335,7 +335,7 @@ def test_count_join_randomised_shapes(ctx, oracle):
 
 
 def test_count_join_window_boundary(ctx, oracle):
-    """The join's LDS key window holds 768 keys (global_kernels.hip kJoinCap); a tile whose key range is wider goes through the global
+    """The join's LDS key window holds 768 keys (region_kernels.hip kJoinCap); a tile whose key range is wider goes through the global
     search.  One tile of 512 queries over a dense run of keys, the run's width swept across the limit (the range a tile takes is
     rounded up to the table's coarse level, every 64th key, so the sweep covers every residue): both paths, bit-exact, on either side
     of the boundary and exactly on it."""
