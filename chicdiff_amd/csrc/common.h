@@ -39,6 +39,7 @@ struct FitWork {
     unsigned long long *queue;    // work-queue heads (kQueueBytes): [0] gene-wise, [1] MAP, [8..15] spare, [16] / [24] lengths of the gene-wise / MAP grid lists, [32 + 8 h] the IRLS's eight heads, 64 bytes apart, [192 + 8 h] the MAP line search's; [104], [112]: role counters of the gene-wise launch's filler waves (kRoleFront, kRoleFill)
     unsigned long long *place;    // kPlaceWords words: where the waves of a gene-wise launch with fillers landed, one word per compute unit; zeroed by disp_init when such a launch follows
     unsigned int *barrier;        // 9 x 64 B: grid-barrier counters of the persistent trend kernel
+    unsigned long long *xchg;     // kXchgBytes behind them: the self-tagged words of its passes' partial sums (trend_kernels.hip, "exchange"); zeroed with the counters at the head of every fit
     FitScalars *sc;
     const double *logfact;        // log(k!) for k < kLogFactN
 };
@@ -48,6 +49,8 @@ struct FitWork {
 __host__ __device__ inline double *sums_of(FitWork w) { return w.partials + (size_t)kRedBlocks * 72; }
 constexpr int kLogFactN = 1024;
 constexpr int kQueueBytes = 2048;  // FitWork::queue
+constexpr int kXchgBytes = 2 * 16 * 256 * 16;            // FitWork::xchg: [pass parity][16 sums][256 workgroups][2 words]
+constexpr int kBarrierBytes = 1024 + kXchgBytes;         // FitWork::barrier and FitWork::xchg: what a fit's first fill clears behind the scalars and the queue heads
 // ---- filler waves of the gene-wise line search (disp_kernels.hip, "front waves and fillers") ----
 constexpr int kPlaceWords = 2048;  // FitWork::place[cu]: one word per compute unit (XCC, SE, SH, CU ids of HW_ID), arrivals per SIMD in its four 16-bit fields
 constexpr int kRoleFront = 104, kRoleFill = 112;     // queue[104] / queue[112] (cache lines of their own): waves that took a front index / asked to be a filler so far
@@ -107,6 +110,7 @@ struct Opts {
     int32_t filler_stop = -1;  // ... fillers stop claiming once the front waves have claimed this share (percent) of their own chunks (100 = never, -1 = kFillerStopDefault); option "line_search_filler_stop"
     int32_t trend_blocks = 0;  // persistent trend kernel: at most this many workgroups (0 = one per CU); option "trend_persistent_blocks"
     int32_t trend_speculate = 1;  // persistent trend kernel: passes announced by fit_state.h trend_step_spec also sum the next glm() call's start pass; option "trend_speculate"
+    int32_t trend_exchange = 1;   // ... its passes' partial sums travel as self-tagged words, no grid barrier per pass (0 = publish, grid barrier, re-read); option "trend_exchange"
     int32_t mad_route = 1;        // ... its MAD step: 1 = value-binned select (three grid barriers), 0 = two radix selects (six); option "mad_select_route"
     int32_t mad_value_cap = 0;    // ... keys a candidate list of the value-binned select may hold (0 = kVbCap); test hook, option "mad_value_cap"
 };

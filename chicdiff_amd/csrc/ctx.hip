@@ -74,6 +74,7 @@ static const OptionDef kOptions[] = {
     {"sharded_trend_gather", nullptr, &HostOpts::sharded_trend_gather, 0, 1, 1, 0},
     {"trend_persistent_blocks", &Opts::trend_blocks, nullptr, 0, 256, 1, 0},
     {"trend_speculate", &Opts::trend_speculate, nullptr, 0, 1, 1, 0},
+    {"trend_exchange", &Opts::trend_exchange, nullptr, 0, 1, 1, 0},
     {"mad_select_route", &Opts::mad_route, nullptr, 0, 1, 1, 0},
     {"mad_value_cap", &Opts::mad_value_cap, nullptr, 0, kVbCap, 1, 0},
     {"trend_mad_in_kernel", nullptr, &HostOpts::trend_mad_in_kernel, 0, 1, 1, 0},
@@ -360,7 +361,7 @@ int cd::ensure_workspace(chicdiff_hip_ctx *c, int64_t n, int S) {
     const size_t selcnt = align256(sizeof(double) * (size_t)kSelMaxWorld * kMaxS * 2);
     const size_t rowpack = align256((size_t)row_stride(S) * (size_t)n);
     const size_t start4 = align256(sizeof(double) * 4 * (size_t)n);
-    const size_t total = nd * n_double_arrays + ni * n_int_arrays + partials + 2 * hist + selcnt + align256(sizeof(FitScalars)) + kQueueBytes + 1024 + kPlaceWords * 8 + nfbytes + rowpack + start4 + align256(sizeof(unsigned int) * kSfWorkWords);
+    const size_t total = nd * n_double_arrays + ni * n_int_arrays + partials + 2 * hist + selcnt + align256(sizeof(FitScalars)) + kQueueBytes + kBarrierBytes + kPlaceWords * 8 + nfbytes + rowpack + start4 + align256(sizeof(unsigned int) * kSfWorkWords);
     hipError_t e = hipMalloc(&c->ws, total);
     if (e != hipSuccess) return fail(c, CHICDIFF_E_NOMEM, "workspace of %zu bytes: %s", total, hipGetErrorString(e));
     c->ws_bytes = total;
@@ -383,6 +384,7 @@ int cd::ensure_workspace(chicdiff_hip_ctx *c, int64_t n, int S) {
     w.logfact = c->d_logfact;
     w.queue = (unsigned long long *)p; p += kQueueBytes;
     w.barrier = (unsigned int *)p; p += 1024;
+    w.xchg = (unsigned long long *)p; p += kXchgBytes;
     w.place = (unsigned long long *)p; p += kPlaceWords * 8;
     c->d_nf_tmp = (double *)p; p += nfbytes;
     w.rowpack = p; p += rowpack;
@@ -393,7 +395,7 @@ int cd::ensure_workspace(chicdiff_hip_ctx *c, int64_t n, int S) {
     c->cap_S = S;
     // scalars, queue heads and barrier counters start from zero: size_factors_impl runs before any fit has cleared them, and a
     // garbage sel_overflow there would send ONE rank of a sharded call into a second pass its peers do not make
-    HIPCHK(c, hipMemsetAsync(w.sc, 0, align256(sizeof(FitScalars)) + kQueueBytes + 1024, c->stream));
+    HIPCHK(c, hipMemsetAsync(w.sc, 0, align256(sizeof(FitScalars)) + kQueueBytes + kBarrierBytes, c->stream));
     return CHICDIFF_OK;
 }
 

@@ -533,7 +533,7 @@ static int fit_pass(chicdiff_hip_ctx *c, const int32_t *d_counts, const double *
     FitWork &w = c->w;
     c->tg_total = 0;
     // the scalars, the queue heads and the barrier counters sit next to each other in the workspace: one fill
-    HIPCHK(c, hipMemsetAsync(w.sc, 0, align256(sizeof(FitScalars)) + kQueueBytes + 1024, st));
+    HIPCHK(c, hipMemsetAsync(w.sc, 0, align256(sizeof(FitScalars)) + kQueueBytes + kBarrierBytes, st));
     // sharded: the column sums of nf travel as the ranks' double-double pairs (zero-filled slots + sum-all-reduce = an exact gather)
     // and are added in rank order — the correctly rounded exact sum, as on one rank: same xim, same start values, same bits downstream
     const int world = c->world > 0 ? c->world : 1;

@@ -213,6 +213,24 @@ CD_HD bool trend_step_spec(FitScalars *sc, const double *s, const double *u /*[k
     return used;
 }
 
+// ---- exchange of a pass's partial sums between the workgroups of the persistent trend kernel (option "trend_exchange") ----
+// A double travels as two 64-bit words that each say which pass they belong to: (tag << 32) | low half, (tag << 32) | high half,
+// tag = pass + 1.  A 64-bit store lands whole, so a word whose tag is the reader's is that pass's half, whatever else has or has
+// not landed yet — validity travels inside the data and no fence or counter has to order the two.  Tag 0 is never written: it is
+// what the fill at the head of a fit leaves, and no pass accepts it.
+CD_HD void xchg_pack(double x, uint32_t tag, uint64_t *lo, uint64_t *hi) {
+    union { double d; uint64_t u; } c;
+    c.d = x;
+    *lo = ((uint64_t)tag << 32) | (c.u & 0xffffffffull);
+    *hi = ((uint64_t)tag << 32) | (c.u >> 32);
+}
+CD_HD bool xchg_accept(uint64_t word, uint32_t tag) { return tag != 0u && (uint32_t)(word >> 32) == tag; }
+CD_HD double xchg_unpack(uint64_t lo, uint64_t hi) {
+    union { double d; uint64_t u; } c;
+    c.u = (hi << 32) | (lo & 0xffffffffull);
+    return c.d;
+}
+
 // ---- radix select ----------------------------------------------------------------------------
 // ranks of the two middle order statistics (R median(): mean of the two for even counts)
 CD_HD void sel_begin(FitScalars *sc, int col, double population) {

@@ -57,7 +57,7 @@ extern "C" int chicdiff_hip_selftest_objective_dev(chicdiff_hip_ctx *c, const in
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = ensure_workspace(c, n, S)) return rc;
     const Opts o = make_opts(c, opts, S);
-    HIPCHK(c, hipMemsetAsync(c->w.sc, 0, align256(sizeof(FitScalars)) + kQueueBytes + 1024, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->w.sc, 0, align256(sizeof(FitScalars)) + kQueueBytes + kBarrierBytes, c->stream));
     launch_prep(d_counts, const_cast<double *>(d_nf), d, c->w, o, c->stream);  // (not fused: nf is read, never written)
     ObjectiveProbe pb{d_log_alpha, K, d_prior_mean, d_prior_mean ? 1.0 / prior_var : 0.0, live_rows, d_lp, d_dlp, d_alpha, d_mu};
     const int lanes = launch_objective_probe(d, c->w, o, pb, c->stream);
@@ -95,7 +95,7 @@ extern "C" int chicdiff_hip_selftest_global_stage_dev(chicdiff_hip_ctx *c, const
     c->refits = 0;
     for (;;) {
         c->tg_total = 0;
-        HIPCHK(c, hipMemsetAsync(w.sc, 0, align256(sizeof(FitScalars)) + kQueueBytes + 1024, st));
+        HIPCHK(c, hipMemsetAsync(w.sc, 0, align256(sizeof(FitScalars)) + kQueueBytes + kBarrierBytes, st));
         HIPCHK(c, hipMemcpyAsync(w.baseMean, d_baseMean, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
         HIPCHK(c, hipMemcpyAsync(w.dispGene, d_dispGeneEst, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
         HIPCHK(c, hipMemcpyAsync(w.allZero, d_allZero, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
@@ -194,6 +194,19 @@ extern "C" int chicdiff_hip_selftest_queue_claim(uint64_t old, int32_t back, uin
     if (chunk_out) *chunk_out = chunk;
     if (again_out) *again_out = cd::filler_claims(claimed != 0, old, chunks, first_back, cd::filler_stop_f(stop_percent, chunks, first_back));
     return valid ? 1 : 0;
+}
+// the words of the persistent trend kernel's exchange (fit_state.h: xchg_pack, xchg_unpack, xchg_accept), evaluated on the host
+extern "C" int chicdiff_hip_selftest_trend_exchange(int32_t op, uint32_t tag, int64_t n, double *x, uint64_t *words, int32_t *accept) {
+    if (op < 0 || op > 2 || n < 0 || (n > 0 && (!words || (op != 2 && !x) || (op == 2 && !accept)))) return CHICDIFF_E_INVALID;
+    for (int64_t i = 0; i < n; i++) {
+        if (op == 0) cd::xchg_pack(x[i], tag, &words[2 * i], &words[2 * i + 1]);
+        else if (op == 1) {
+            x[i] = cd::xchg_unpack(words[2 * i], words[2 * i + 1]);
+            if (accept) accept[i] = cd::xchg_accept(words[2 * i], tag) && cd::xchg_accept(words[2 * i + 1], tag);
+        } else
+            accept[i] = cd::xchg_accept(words[i], tag);
+    }
+    return CHICDIFF_OK;
 }
 extern "C" int chicdiff_hip_selftest_prior_mc(int32_t df, const double *hist40, double *dens_out, double *prior_var_out) {
     if (df < 1 || df > 3) return CHICDIFF_E_INVALID;

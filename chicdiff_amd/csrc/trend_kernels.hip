@@ -146,11 +146,43 @@ __global__ void trend_step_kernel(FitWork w) { trend_step(w.sc, sums_of(w)); }
 // 30 k x 4 (option "trend_speculate" = 0: every pass as before; same bits either way).
 constexpr int kTpSums = 2 * kTrendSums;  // a workgroup's slot per pass: v[8], then u[8] of a speculative pass
 constexpr int kTpBlocks = 256, kTpThreads = 1024, kTpCap = 8000, kTpMinRows = 2048;  // rows cached per workgroup (2 x 64 000 B of LDS)
+// The exchange of the passes after the first (option "trend_exchange"; 0: every pass by the grid barrier, as pass 0).  What the
+// barrier's two fences, its chain of arrivals and the re-read cost — 7-9 of a pass's ~19 us at 2 M rows — bought was only that a
+// counter could vouch for data that travelled apart from it.  Here every 64-bit word vouches for itself (fit_state.h xchg_pack:
+// tag = pass + 1 beside half a double), so nothing has to be ordered against anything:
+//  * writer: thread t < nsums stores the two words of sum t, relaxed at agent scope — no fence, no counter, no wait;
+//  * reader: wave k < nsums sums quantity k as before, lane l taking workgroups l, l + 64, ... in ascending order; it polls its
+//    words, relaxed at agent scope, until each carries this pass's tag (xchg_accept, word by word: no order between two words is
+//    assumed anywhere), then adds the doubles in that same order: the parent's tree, operand for operand, so every bit stays;
+//  * layout: FitWork::xchg[pass parity][sum][workgroup][2] — a wave's poll is one contiguous run of 16 bytes per workgroup (the
+//    flag barrier below had 256 x 256 polls on sixteen lines), in a buffer nobody else writes: no stale double can pass for a tag;
+//  * stale words of an earlier launch are impossible, not improbable: the buffer lies behind FitWork::barrier and is zero-filled
+//    with it by the one fill at the head of every pass of a fit — refits and the gathered route of sharded fits (which launches on
+//    a copy of the same FitWork) included — and tag 0 is accepted by no pass;
+//  * parity: a workgroup stores pass p + 2 into the buffer of pass p only after it has accepted every workgroup's words of p + 1
+//    (its stores take their values from the state step, which takes its from those loads), and a workgroup stores p + 1 only after
+//    it has accepted — finished reading — all of p.  So when a word of p is overwritten, every reader is done with it;
+//  * a lane that waits kXchgSpins polls in vain (grid_sync's patience: a workgroup that never became resident) marks the workgroup
+//    lost through LDS; it leaves, its peers run out in turn, failed = 3, and the host fits again with one launch per pass.  The
+//    timeout cascades: the peers of the workgroup that left first find out only by waiting in vain for its words of the NEXT pass,
+//    each for its own full patience, so the launch ends after about two patiences where a lost grid_sync ends after one;
+// grid_sync stays where atomics and lists are published: pass 0 (which orders the zeroing of the MAD scratch by workgroup 0 before
+// any workgroup's first MAD atomic), the MAD step and mad_select.  Its counters count those real barriers alone.
+// One round of polls is 256 workgroups x 8 or 16 waves x 4 KB — 8 or 16 MB through the fabric, about 2 us, the price of the barrier
+// route's re-read — so a round that cannot succeed is not free: it holds up the very stores everybody waits for.  A poll issued
+// straight behind the workgroup's own stores always fails (the stores take longer than that to become visible, and the other
+// workgroups are not all there yet), so the reader sleeps kXchgFirstSleep x 64 clocks first, ~0.9 us.  Measured in whole steps, six
+// alternating runs each (profiles/r35_ab_variants.txt): without that sleep and s_sleep 2 between polls 3.230-3.248 ms at 2 M x 8
+// (one run 3.423) against the barrier route's 3.247-3.256; 16 and 8: 3.187-3.209; 32 and 4: 3.167-3.183, and, medians of three runs, barrier
+// route -> 32 and 4: 1.193 -> 1.155 ms at 250 k x 8, 0.697 -> 0.678 at 30 k x 4.
+constexpr int kXchgSpins = 1 << 24, kXchgFirstSleep = 32, kXchgPollSleep = 4;
+static_assert(kXchgBytes == 2 * kTpSums * kTpBlocks * 2 * 8 && kTpBlocks % 64 == 0, "trend exchange: layout of FitWork::xchg");
 
 // Two-level grid barrier: workgroups arrive at one of 8 group counters (blockIdx % 8, i.e. one per XCD under
 // round-robin dispatch — different cache lines, so the arrivals of different groups do not serialise behind one
 // another), the last arrival of a group bumps the top counter, everybody polls the top counter.  256 atomics on
-// one word cost ~10 us per barrier; this way the longest chain is 32 + 8.  `pass` counts barriers from 0.
+// one word cost ~10 us per barrier; this way the longest chain is 32 + 8.  `pass` counts the calls of a launch from 0, without gaps
+// (the counters only ever grow): the kernel's nbar, not the number of the trend pass.
 __device__ __forceinline__ bool grid_sync(unsigned int *top, unsigned int *groups, unsigned int pass) {
     __shared__ int ok;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores have left
@@ -184,7 +216,12 @@ __device__ __forceinline__ bool grid_sync(unsigned int *top, unsigned int *group
 // without the top level — arrivals by an atomic add nobody waits for, lanes 0..7 of every workgroup polling the eight group
 // counters, so that no arrival depends on a returned count: workgroup 0 passes the barriers of the trend passes in 2.2 instead of
 // 3.6 us (250 k rows) and 3.7 instead of 5-6 (2 M), but the barriers of the MAD's histogram rounds, where every workgroup arrives
-// in a burst behind its global atomics, get slower by as much: launch 0.190 -> 0.188 ms at 250 k, 0.365 -> 0.380 at 2 M.)
+// in a burst behind its global atomics, get slower by as much: launch 0.190 -> 0.188 ms at 250 k, 0.365 -> 0.380 at 2 M.
+// Round 35: the trend's passes after the first do without this barrier altogether — their sums travel as self-tagged words
+// ("exchange", above the kernel): workgroup 0's window from its sums to everybody's, stamps 12 -> 14, 6.0-9.3 -> 2.2-2.6 us at 2 M
+// rows, 4.4-5.4 -> 1.8-2.2 at 250 k, 2.8-3.4 -> 1.7-1.8 at 30 k x 4, a whole pass 17.3-20.7 -> 11.1-13.9, 9.5-12.1 -> 6.5-8.9 and
+// 6.7-9.6 -> 6.2-8.5 us (profiles/r35_trend_stamps.txt); the launch 305 -> 233 us at 2 M x 8.  The barrier stays for pass 0 and
+// the MAD step.)
 
 // Sum over the 64 lanes of a wave, result in lane 63, by DPP row shifts and row broadcasts (an inclusive scan: fixed order, no
 // LDS round trips).  The eight sums of a trend pass through ds_bpermute shuffles were 48 dependent LDS trips per wave — with 16
@@ -233,6 +270,7 @@ struct MadArgs {
     double prior_in;   // NaN = estimate; the closed-form prior variance is finished here unless by_simulation
     int by_simulation; // residual d.f. <= 3: the host follows up with the residual histogram and prior_mc
     int speculate;     // the trend's passes may speculate (option "trend_speculate")
+    int exchange;      // the trend's passes after the first hand their sums over as self-tagged words, no grid barrier (option "trend_exchange")
     int value_route;   // median and MAD by the value-binned select, three grid barriers instead of six (option "mad_select_route")
     int value_cap;     // ... keys a candidate list may hold (option "mad_value_cap": a test can force the radix select)
 };
@@ -629,7 +667,8 @@ __device__ __forceinline__ void vb_append(Pred pred, int64_t nrows_block, uint64
 __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d, FitWork w, double minDisp, MadArgs madargs) {
     const bool mad = madargs.enabled != 0;
     __shared__ double s_bm[kTpCap], s_y[kTpCap];  // 1 / baseMean and dispGeneEst (NaN = not used for the fit)
-    __shared__ double red[kTpSums][16];
+    __shared__ double red[kTpSums][16], tot[kTpSums];  // a pass's sums per wave; over all workgroups
+    __shared__ int s_lost;                             // a lane of the exchange ran out of patience
     __shared__ FitScalars st;  // only the trend fields are used
     __shared__ LogEntry s_lt[64];
     __shared__ VbShared vsh;
@@ -645,18 +684,23 @@ __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d,
         s_bm[k] = 1.0 / w.baseMean[i];
         s_y[k] = w.allZero[i] ? NAN : y;  // (useForFit, y > 100 minDisp, is tested per pass: the MAD step below wants y >= 100 minDisp)
     }
-    if (tid == 0) trend_init(&st);
+    if (tid == 0) {
+        trend_init(&st);
+        s_lost = 0;
+    }
     __syncthreads();
     unsigned int *ctr = reinterpret_cast<unsigned int *>(w.barrier), *grp = ctr + 16;  // top counter, then 8 group counters 64 B apart
     double *slots = w.partials;  // [2][gridDim.x][kTpSums], double-buffered by pass parity
-    const bool speculate = madargs.speculate != 0;
+    const bool speculate = madargs.speculate != 0, exchange = madargs.exchange != 0;
     const double thr = 100 * minDisp;
-    // scratch of the MAD step (below): zeroed here, by one workgroup; the barriers of the trend passes publish it
+    // scratch of the MAD step (below): zeroed here, by one workgroup; the grid barrier of the first trend pass publishes it (every
+    // launch runs at least one pass, and pass 0 crosses a real barrier under either exchange route)
     unsigned int *gscratch = reinterpret_cast<unsigned int *>(w.hist);
     if (mad && blockIdx.x == 0)
         for (int k = tid; k < kMadZeroWords; k += kTpThreads) gscratch[k] = 0;
     bool alive = true;
-    unsigned int pass = 0;
+    unsigned int pass = 0;   // trend passes so far: the tag of the exchange's words and the parity of both routes' buffers
+    unsigned int nbar = 0;   // grid_sync calls so far: its counters count real barriers only, consecutively
 #ifdef CHICDIFF_TREND_STAMPS
     if (blockIdx.x == 0 && threadIdx.x == 0) g_tr_n = 0;
 #endif
@@ -700,31 +744,92 @@ __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d,
             }
         }
         __syncthreads();
-        double *mine = slots + ((size_t)(pass & 1) * gridDim.x + blockIdx.x) * kTpSums;
-        if (tid < nsums) {
-            double acc = 0;
-            for (int q = 0; q < kTpThreads / 64; q++) acc += red[tid][q];
-            mine[tid] = acc;
+        if (!(exchange && pass > 0)) {
+            // publish, grid barrier, re-read: pass 0 always (its barrier also publishes the MAD scratch zeroed above), and every
+            // pass with "trend_exchange" = 0
+            double *mine = slots + ((size_t)(pass & 1) * gridDim.x + blockIdx.x) * kTpSums;
+            if (tid < nsums) {
+                double acc = 0;
+                for (int q = 0; q < kTpThreads / 64; q++) acc += red[tid][q];
+                mine[tid] = acc;
+            }
+            TSTAMP(12);
+            alive = grid_sync(ctr, grp, nbar++);
+            TSTAMP(13);
+            if (!alive) break;
+            // every workgroup: fixed-order sum of all partials (wave k sums quantity k: 64 lanes x strided
+            // partials, then a shuffle tree — the same order in every workgroup), then the same state-machine step
+            const double *all = slots + (size_t)(pass & 1) * gridDim.x * kTpSums;
+            if (wave < nsums) {
+                double acc = 0;
+                for (unsigned int b = lane; b < gridDim.x; b += 64) acc += all[(size_t)b * kTpSums + wave];
+                acc = wave_sum_to_lane63(acc);
+                if (lane == 63) tot[wave] = acc;
+            }
+            __syncthreads();
+        } else {
+            // the exchange (above the kernel): thread t stores the two words of sum t, wave k polls and adds sum k of every workgroup
+            const unsigned int tag = pass + 1u, nblk = gridDim.x;
+            unsigned long long *xbuf = w.xchg + (size_t)(pass & 1) * kTpSums * kTpBlocks * 2;
+            if (tid < nsums) {
+                double acc = 0;
+                for (int q = 0; q < kTpThreads / 64; q++) acc += red[tid][q];
+                uint64_t lo, hi;
+                xchg_pack(acc, tag, &lo, &hi);
+                unsigned long long *mine = xbuf + ((size_t)tid * kTpBlocks + blockIdx.x) * 2;
+                __hip_atomic_store(mine, (unsigned long long)lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(mine + 1, (unsigned long long)hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            TSTAMP(12);
+            if (wave < nsums) {
+                unsigned long long *src = xbuf + (size_t)wave * kTpBlocks * 2;  // this wave's poll: one contiguous run of nblk x 16 bytes
+                constexpr int kStrides = kTpBlocks / 64;
+                uint64_t lo[kStrides], hi[kStrides];
+                bool ready = true;
+                __builtin_amdgcn_s_sleep(kXchgFirstSleep);  // (no word can have arrived yet: see kXchgFirstSleep)
+#pragma unroll
+                for (int j = 0; j < kStrides; j++) {
+                    const unsigned int b = lane + 64u * j;
+                    lo[j] = hi[j] = 0;
+                    if (b < nblk) {
+                        lo[j] = __hip_atomic_load(src + 2 * b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        hi[j] = __hip_atomic_load(src + 2 * b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        ready = ready && xchg_accept(lo[j], tag) && xchg_accept(hi[j], tag);
+                    }
+                }
+                int spins = 0;
+                while (!ready && spins < kXchgSpins) {  // only the lanes with a word missing, and only for those words
+                    __builtin_amdgcn_s_sleep(kXchgPollSleep);
+                    spins++;
+                    ready = true;
+#pragma unroll
+                    for (int j = 0; j < kStrides; j++) {
+                        const unsigned int b = lane + 64u * j;
+                        if (b < nblk) {
+                            if (!xchg_accept(lo[j], tag)) lo[j] = __hip_atomic_load(src + 2 * b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            if (!xchg_accept(hi[j], tag)) hi[j] = __hip_atomic_load(src + 2 * b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            ready = ready && xchg_accept(lo[j], tag) && xchg_accept(hi[j], tag);
+                        }
+                    }
+                }
+                if (!ready) s_lost = 1;  // a bounded spin, as grid_sync's: a lost workgroup must not hang the device
+                double acc = 0;          // the parent's tree, operand for operand: workgroups lane, lane + 64, ... in ascending order
+#pragma unroll
+                for (int j = 0; j < kStrides; j++)
+                    if (lane + 64u * j < nblk) acc += xchg_unpack(lo[j], hi[j]);
+                acc = wave_sum_to_lane63(acc);
+                if (lane == 63) tot[wave] = acc;
+            }
+            TSTAMP(13);
+            __syncthreads();
+            alive = s_lost == 0;
+            if (!alive) break;
         }
-        TSTAMP(12);
-        alive = grid_sync(ctr, grp, pass);
-        TSTAMP(13);
-        if (!alive) break;
-        // every workgroup: fixed-order sum of all partials (wave k sums quantity k: 64 lanes x strided
-        // partials, then a shuffle tree — the same order in every workgroup), then the same state-machine step
-        const double *all = slots + (size_t)(pass & 1) * gridDim.x * kTpSums;
-        if (wave < nsums) {
-            double acc = 0;
-            for (unsigned int b = lane; b < gridDim.x; b += 64) acc += all[(size_t)b * kTpSums + wave];
-            acc = wave_sum_to_lane63(acc);
-            if (lane == 63) red[wave][0] = acc;
-        }
-        __syncthreads();
         TSTAMP(14);
         if (tid == 0) {
             double sv[kTrendSums], su[kTrendSums];  // (su is stale unless the pass speculated: not looked at then)
 #pragma unroll
-            for (int k = 0; k < kTrendSums; k++) { sv[k] = red[k][0]; su[k] = red[kTrendSums + k][0]; }
+            for (int k = 0; k < kTrendSums; k++) { sv[k] = tot[k]; su[k] = tot[kTrendSums + k]; }
             if (spec) trend_step_spec(&st, sv, su, speculate);
             else trend_step_spec(&st, sv, nullptr, speculate);
         }
@@ -778,7 +883,7 @@ __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d,
             for (int k = tid; k < kVbBins; k += kTpThreads)
                 if (s_h[k]) atomicAdd(&vhist[k], s_h[k]);
             MSTAMP(21);
-            alive = grid_sync(ctr, grp, pass++);
+            alive = grid_sync(ctr, grp, nbar++);
             MSTAMP(22);
             if (alive) {
                 vb_load(vhist, s_h);
@@ -804,7 +909,7 @@ __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d,
                     };
                     vb_append(in_bins, nrows, sortbuf, vcap, &vcnt[0], vcand, vsh);
                     MSTAMP(24);
-                    alive = grid_sync(ctr, grp, pass++);
+                    alive = grid_sync(ctr, grp, nbar++);
                     MSTAMP(25);
                     if (alive && vcnt[0] == pk.count) {
                         const double vlo = (double)binA / kVbScale - kVbOffset, scale = (double)kVbSub * kVbScale / (double)(binB + 1 - binA);
@@ -815,7 +920,7 @@ __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d,
                 }
             }
         }
-        if (alive && !empty && !med_done) alive = mad_select(key_resid, nrows, 0, gscratch, s_a, s_b, sortbuf, ctr, grp, pass, res, pop);
+        if (alive && !empty && !med_done) alive = mad_select(key_resid, nrows, 0, gscratch, s_a, s_b, sortbuf, ctr, grp, nbar, res, pop);
         if (alive) {
             nres = pop;
             med = pop > 0 ? (value_of(res[0]) + value_of(res[1])) / 2.0 : NAN;  // R median(): mean of the two middles
@@ -855,7 +960,7 @@ __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d,
                 if (tid == 0 && vsh.pop) atomicAdd(&vcnt[3], vsh.pop);
                 if (tid == 0 && vsh.below) atomicAdd(&vcnt[2], vsh.below);
                 MSTAMP(28);
-                alive = grid_sync(ctr, grp, pass++);
+                alive = grid_sync(ctr, grp, nbar++);
                 MSTAMP(29);
                 if (alive) {
                     uint32_t kA = 0, kB = 0;
@@ -867,7 +972,7 @@ __global__ __launch_bounds__(kTpThreads) void trend_persistent_kernel(FitDims d,
                 }
                 MSTAMP(30);
             }
-            if (alive && !mad_done) alive = mad_select(key_absdev, nrows, 1, gscratch, s_a, s_b, sortbuf, ctr, grp, pass, res, pop);
+            if (alive && !mad_done) alive = mad_select(key_absdev, nrows, 1, gscratch, s_a, s_b, sortbuf, ctr, grp, nbar, res, pop);
             if (alive) madv = 1.4826 * (pop > 0 ? (value_of(res[0]) + value_of(res[1])) / 2.0 : NAN);  // R mad(): constant 1.4826
         }
     }
@@ -928,7 +1033,9 @@ __global__ void flag_to_double_kernel(const int32_t *flag, double *out) { *out =
 void launch_flag_to_double(const int32_t *flag, double *out, hipStream_t st) { flag_to_double_kernel<<<1, 1, 0, st>>>(flag, out); }
 int trend_persistent_blocks() { return kTpBlocks; }
 void launch_trend_persistent(FitDims d, FitWork w, Opts o, hipStream_t st, bool with_mad) {
-    // (the barrier counters were zeroed with the fit's scalars; the trend runs once per fit)
+    // (the barrier counters AND the exchange's words, FitWork::xchg, were zeroed with the fit's scalars, and the trend runs once per
+    // fill: a second launch of this kernel behind the same fill would find the counters advanced and, in xchg, words that carry the
+    // tags of its own passes — stale sums it would accept.  Whoever launches it twice in one fit_pass must clear both in between)
     // as few workgroups as keep every row LDS-resident: the pass time is the grid barrier plus the all-partials sum,
     // both of which grow with the number of workgroups (small fits are latency-bound by these ~20 passes)
     // rows per workgroup: at most kTpCap (LDS), at least ~2 per thread — with 8 per thread the row loop (4 us) was as long
@@ -946,6 +1053,7 @@ void launch_trend_persistent(FitDims d, FitWork w, Opts o, hipStream_t st, bool 
     m.prior_in = o.dispPriorVarIn;
     m.by_simulation = (!(o.dispPriorVarIn == o.dispPriorVarIn) && d.S - d.p <= 3 && d.S > d.p) ? 1 : 0;
     m.speculate = o.trend_speculate ? 1 : 0;
+    m.exchange = o.trend_exchange ? 1 : 0;
     m.value_route = o.mad_route ? 1 : 0;
     m.value_cap = (o.mad_value_cap > 0 && o.mad_value_cap < kVbCap) ? o.mad_value_cap : kVbCap;
     trend_persistent_kernel<<<(unsigned)blocks, kTpThreads, 0, st>>>(d, w, o.minDisp, m);

@@ -113,6 +113,9 @@ int32_t chicdiff_hip_last_refits(const chicdiff_hip_ctx *ctx);
  *                               coefficients then differ in summation order only (1e-13)
  *   "trend_speculate"           1 (default) | 0: passes of the single-launch trend kernel that are likely to end a glm() call also sum
  *                               what the next call's start pass would, so that pass is not run; 0 = every pass is run: same bits
+ *   "trend_exchange"            1 (default) | 0: the workgroups of the single-launch trend kernel hand each other a pass's partial sums as
+ *                               64-bit words that carry the pass number beside half a double, polled without fences; 0 = every pass
+ *                               publishes its sums, crosses a grid barrier and reads them back: same bits
  *   "mad_select_route"          1 (default) | 0: the single-launch trend kernel takes the median and MAD of the residuals from one histogram over
  *                               their values (three grid-wide rounds, radix select only where a candidate list does not fit); 0 = two
  *                               radix selects (six rounds): same bits
@@ -981,6 +984,11 @@ int chicdiff_hip_selftest_sched_class(int32_t mode, double min_disp, const doubl
  * in the rows fillers may take (first_back; >= chunks: none) and the stop share in percent ("line_search_filler_stop"). */
 int chicdiff_hip_selftest_queue_claim(uint64_t old, int32_t back, uint32_t chunks, uint32_t first_back, int32_t stop_percent, int32_t claimed,
                                       uint32_t *chunk_out, int32_t *again_out);
+/* _trend_exchange (host only): the words in which the single-launch trend kernel's workgroups hand each other a pass's partial sums
+ * ("trend_exchange"), as the kernel forms and accepts them.  op 0: words[2 i], words[2 i + 1] = x[i] packed under `tag` (pass + 1), i < n;
+ * op 1: x[i] = the double in words[2 i], words[2 i + 1], and accept[i] (may be NULL) = whether a reader of `tag` takes both words;
+ * op 2: accept[k] = whether a reader of `tag` takes words[k], k < n.  Tag 0 (never written) is taken by nobody. */
+int chicdiff_hip_selftest_trend_exchange(int32_t op, uint32_t tag, int64_t n, double *x, uint64_t *words, int32_t *accept);
 /* _sf_bin (host only): the value bins of the single-rank size-factor select, as its kernels apply them.  *nbins_out (may be NULL): the
  * number of bins per column for S samples (<= 16); bin_out[n]: the bin of each key x (log count - row log geometric mean); sub_out[n] (may be NULL):
  * its sub-bin inside bin `sub_of`.  Both never decrease as x grows: all the select's exactness asks of them. */

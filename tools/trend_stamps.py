@@ -6,13 +6,13 @@ kernel when it ends; profiles/r04_trend_pass_stamps.txt).  Needs a library whose
     hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -DCHICDIFF_TREND_STAMPS -c chicdiff_amd/csrc/trend_kernels.hip -o chicdiff_amd/lib/obj_ts/trend_kernels.o
     hipcc --offload-arch=gfx950 -shared -fPIC -o chicdiff_amd/lib/ab/trend_stamps.so chicdiff_amd/lib/obj_ts/*.o
 
-usage (GPU box): python tools/trend_stamps.py <rows>"""
+usage (GPU box): [CHICDIFF_HIP_LIB=<another such library>] python tools/trend_stamps.py <rows> [samples, default 8]"""
 import os, sys
 sys.path.insert(0, '.')
-os.environ["CHICDIFF_HIP_LIB"] = "chicdiff_amd/lib/ab/trend_stamps.so"
+os.environ.setdefault("CHICDIFF_HIP_LIB", "chicdiff_amd/lib/ab/trend_stamps.so")
 import numpy as np
 from chicdiff_amd import hip, synth
-n = int(sys.argv[1]); S = 8
+n = int(sys.argv[1]); S = int(sys.argv[2]) if len(sys.argv) > 2 else 8
 d = synth.make(n, S)
 ctx = hip.HipContext(0)
 dk, dn = ctx.to_device(d["counts"], np.int32), ctx.to_device(d["nf"], np.float64)
