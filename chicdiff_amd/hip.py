@@ -26,6 +26,7 @@ EXPORTS = [
     "chicdiff_hip_set_allreduce", "chicdiff_hip_set_allgather", "chicdiff_hip_last_refits", "chicdiff_hip_set_option", "chicdiff_hip_default_opts", "chicdiff_hip_size_factors_dev",
     "chicdiff_hip_offsets_dev", "chicdiff_hip_window_sums_dev", "chicdiff_hip_count_join_dev",
     "chicdiff_hip_fragment_background_dev", "chicdiff_hip_bh_adjust_dev", "chicdiff_hip_ihw_apply_dev",
+    "chicdiff_hip_ihw_train_dev", "chicdiff_hip_ihw_caps", "chicdiff_hip_selftest_ihw_knots_dev", "chicdiff_hip_selftest_ihw_orient",
     "chicdiff_hip_region_universe_count_dev", "chicdiff_hip_region_universe_fill_dev", "chicdiff_hip_region_universe_dev", "chicdiff_hip_count_table_dev",
     "chicdiff_hip_candidate_interactions_dev", "chicdiff_hip_candidate_interactions_method_dev", "chicdiff_hip_selftest_landau_dev", "chicdiff_hip_chicago_tables_dev", "chicdiff_hip_chicago_tables_caps",
     "chicdiff_hip_control_draws_dev", "chicdiff_hip_countput_dev", "chicdiff_hip_countput_caps",
@@ -71,6 +72,15 @@ class Scalars(C.Structure):
 class ResultsInfo(C.Structure):
     _fields_ = [("filterThreshold", C.c_double), ("filterTheta", C.c_double), ("alpha", C.c_double), ("index", C.c_int32),
                 ("_pad", C.c_int32), ("theta", C.c_double * 50), ("numRej", C.c_double * 50), ("lowess", C.c_double * 50)]
+
+
+IHW_MAX_FOLDS = 16   # CHICDIFF_IHW_MAX_FOLDS (include/chicdiff_hip.h)
+
+
+class IhwInfo(C.Structure):
+    """chicdiff_ihw_info (include/chicdiff_hip.h)."""
+    _fields_ = [("m", C.c_int64), ("nbins", C.c_int32), ("nfolds", C.c_int32), ("chunk_len", C.c_int32), ("_pad", C.c_int32),
+                ("nseg", C.c_int64 * IHW_MAX_FOLDS), ("T", C.c_double * IHW_MAX_FOLDS), ("H", C.c_double * IHW_MAX_FOLDS)]
 
 
 class TableColumn(C.Structure):
@@ -163,6 +173,10 @@ def load_library() -> C.CDLL:
     L.chicdiff_hip_region_assemble_dev.argtypes = [vp, vp, vp, i64, vp, i64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), i32, i32,
                                                    vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(dbl), vp, vp]
     L.chicdiff_hip_ihw_apply_dev.argtypes = [vp, vp, vp, i64, C.POINTER(dbl), C.POINTER(dbl), i32, vp, vp, vp, vp]
+    L.chicdiff_hip_ihw_train_dev.argtypes = [vp, vp, vp, i64, dbl, i32, i32, C.c_uint64, vp, vp, vp, C.POINTER(IhwInfo)]
+    L.chicdiff_hip_ihw_caps.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, C.POINTER(i32)]
+    L.chicdiff_hip_selftest_ihw_knots_dev.argtypes = [vp, vp, vp, i64, i32, i32, C.c_uint64, i32, i64, vp, vp, vp, C.POINTER(i32), C.POINTER(i64)]
+    L.chicdiff_hip_selftest_ihw_orient.argtypes = [vp, vp, vp, vp, vp, vp, i64, vp]
     L.chicdiff_hip_region_universe_count_dev.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp, vp, vp, C.POINTER(i64)]
     L.chicdiff_hip_region_universe_fill_dev.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp, vp, vp, vp]
     L.chicdiff_hip_region_universe_dev.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
@@ -231,6 +245,30 @@ def countput_caps() -> dict:
     m, k, r = C.c_int32(0), C.c_int32(0), C.c_int32(0)
     load_library().chicdiff_hip_countput_caps(C.byref(m), C.byref(k), C.byref(r))
     return dict(max_rep=m.value, key_rows_per_workgroup=k.value, reduce_rows_per_workgroup=r.value)
+
+
+def ihw_caps() -> dict:
+    """The limits of ``HipContext.ihw_train`` as the library was built (include/chicdiff_hip.h, CHICDIFF_IHW_*): the most groups and
+    folds, the largest automatic number of groups, and the chunk lengths it accepts (ascending; the last is the default)."""
+    a, b, c, k = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    lens = (C.c_int32 * 16)()
+    load_library().chicdiff_hip_ihw_caps(C.byref(a), C.byref(b), C.byref(c), lens, 16, C.byref(k))
+    return dict(max_bins=a.value, max_folds=b.value, auto_max_bins=c.value, chunk_lens=[lens[i] for i in range(min(k.value, 16))])
+
+
+def selftest_ihw_orient(ax, ac, bx, bc, cx, cc):
+    """The exact knot test of the IHW training stage as compiled for the host (chicdiff_hip_selftest_ihw_orient): the sign, per triple
+    of points (x, count), of (b.c - a.c) (c.x - a.x) - (c.c - a.c) (b.x - a.x).  No GPU is needed."""
+    xs = [np.ascontiguousarray(v, dtype=np.float64) for v in (ax, bx, cx)]
+    cs = [np.ascontiguousarray(v, dtype=np.int32) for v in (ac, bc, cc)]
+    n = len(xs[0])
+    assert all(len(v) == n for v in xs + cs)
+    out = np.empty(n, dtype=np.int32)
+    rc = load_library().chicdiff_hip_selftest_ihw_orient(xs[0].ctypes.data, cs[0].ctypes.data, xs[1].ctypes.data, cs[1].ctypes.data,
+                                                         xs[2].ctypes.data, cs[2].ctypes.data, n, out.ctypes.data)
+    if rc:
+        raise ChicdiffHipError(f"[{rc}] selftest_ihw_orient: bad arguments")
+    return out
 
 
 # include/chicdiff_hip.h, CHICDIFF_COL_* / CHICDIFF_TABLE_*
@@ -990,6 +1028,48 @@ class HipContext:
                                                         w.ctypes.data_as(P), len(w), group.data_ptr(), weight.data_ptr(),
                                                         wp.data_ptr(), wpadj.data_ptr()))
         return dict(group=group, weight=weight, weighted_pvalue=wp, weighted_padj=wpadj)
+
+    def _ihw_args(self, d_pvalue, d_covariate, nbins, nfolds, seed, chunk_len):
+        torch = self.torch
+        self._check_tensor("d_pvalue", d_pvalue, torch.float64, (-1,))
+        self._check_tensor("d_covariate", d_covariate, torch.float64, (d_pvalue.numel(),))
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+            raise ValueError(f"ihw_train: seed must be an integer in [0, 2^64), got {seed!r}")
+        return d_pvalue.numel(), 0 if nbins is None else int(nbins), int(nfolds), int(seed), 0 if chunk_len is None else int(chunk_len)
+
+    def ihw_train(self, d_pvalue, d_covariate, alpha=0.05, nbins=None, nfolds=5, seed=0, chunk_len=None):
+        """The training side of IHWcorrection, ihw(pvalue ~ covariate, alpha) of chicdiff.R:1994, by this library's own statement of
+        it (the rule and its differences from the IHW package are above chicdiff_hip_ihw_train_dev in include/chicdiff_hip.h).
+        ``d_pvalue, d_covariate``: float64 (n,) device tensors, NaN p = a row left out; ``nbins`` None = automatic; ``chunk_len`` None
+        = the default, else one of ``ihw_caps()["chunk_lens"]`` (the results never depend on it).
+
+        Returns dict(group, fold: int32 device tensors (INT32_MIN / -1 on left-out rows), weights: (nbins, nfolds) numpy array,
+        m, nbins, nseg, T, H: the info block)."""
+        torch = self.torch
+        n, nb, nf, sd, cl = self._ihw_args(d_pvalue, d_covariate, nbins, nfolds, seed, chunk_len)
+        group, fold = (torch.empty(max(n, 1), dtype=torch.int32, device=self.device) for _ in range(2))
+        w = np.zeros(IHW_MAX_FOLDS * 256, dtype=np.float64)
+        info = IhwInfo()
+        info.chunk_len = cl
+        self._check(self.lib.chicdiff_hip_ihw_train_dev(self.h, d_pvalue.data_ptr(), d_covariate.data_ptr(), n, float(alpha), nb, nf, sd,
+                                                        group.data_ptr(), fold.data_ptr(), w.ctypes.data, C.byref(info)))
+        self.last_ihw_train_ms = {k: v[0] for k, v in self.kernel_times().items() if k.startswith("ihw_")}
+        k = info.nbins
+        return dict(group=group[:n], fold=fold[:n], weights=w[: k * nf].reshape(nf, k).T.copy(), m=info.m, nbins=k, chunk_len=info.chunk_len,
+                    nseg=np.array(info.nseg[:nf]), T=np.array(info.T[:nf]), H=np.array(info.H[:nf]))
+
+    def selftest_ihw_knots(self, d_pvalue, d_covariate, nbins=None, nfolds=5, seed=0, chunk_len=None):
+        """The knots of every (fold, group) as the device finds them (chicdiff_hip_selftest_ihw_knots_dev): dict(ptr, x, c, nbins),
+        entry f * nbins + (g - 1) owning x, c [ptr[q] .. ptr[q + 1])."""
+        n, nb, nf, sd, cl = self._ihw_args(d_pvalue, d_covariate, nbins, nfolds, seed, chunk_len)
+        k, nk = C.c_int32(0), C.c_int64(0)
+        args = (self.h, d_pvalue.data_ptr(), d_covariate.data_ptr(), n, nb, nf, sd, cl)
+        self._check(self.lib.chicdiff_hip_selftest_ihw_knots_dev(*args, 0, None, None, None, C.byref(k), C.byref(nk)))
+        ptr = np.zeros(nf * k.value + 1, dtype=np.int64)
+        x, c = np.zeros(nk.value, dtype=np.float64), np.zeros(nk.value, dtype=np.int32)
+        self._check(self.lib.chicdiff_hip_selftest_ihw_knots_dev(*args, nk.value, ptr.ctypes.data, x.ctypes.data, c.ctypes.data, C.byref(k),
+                                                                 C.byref(nk)))
+        return dict(ptr=ptr, x=x, c=c, nbins=k.value)
 
     # -- f4: region universe ---------------------------------------------------------------------
     def region_universe(self, d_bait, d_oe, RUexpand, d_chr_of):

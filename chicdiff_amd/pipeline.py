@@ -746,6 +746,23 @@ def dist_lookup(ihw_df, ihw_weights):
     return dict(group=groups, minLogDist=lo, maxLogDist=hi, avWeights=avW)
 
 
+def ihw_device(ctx, seed, nbins=None, nfolds=5):
+    """An ``ihw=`` callable for IHWcorrection / chicdiffPipeline that trains the weights on the device (``HipContext.ihw_train``): this
+    library's statement of IHW::ihw(pvalue ~ covariate, alpha), not the package's — no regularisation, folds from ``seed`` (the rule and
+    the differences are above chicdiff_hip_ihw_train_dev in include/chicdiff_hip.h).  ``nbins`` None: max(1, min(40, m / 1500)).
+    Returns ``(df, weights)`` as ``ihw`` must: df with columns pvalue, covariate, group (NaN on the rows left out), weights nbins x nfolds."""
+    def ihw(pvalue, covariate, alpha):
+        import pandas as pd
+        p = np.ascontiguousarray(pvalue, dtype=np.float64)
+        cov = np.ascontiguousarray(covariate, dtype=np.float64)
+        r = ctx.ihw_train(ctx.torch.from_numpy(p).to(ctx.device), ctx.torch.from_numpy(cov).to(ctx.device), alpha=alpha, nbins=nbins,
+                          nfolds=nfolds, seed=seed)
+        g = r["group"].cpu().numpy()
+        group = np.where(g == np.iinfo(np.int32).min, np.nan, g.astype(np.float64))
+        return pd.DataFrame({"pvalue": p, "covariate": cov, "group": group}), r["weights"]
+    return ihw
+
+
 def IHWcorrection(chicdiff_settings, DESeqOut, FullRegionData, DESeqOutControl, FullControlRegionData, countput=None,
                   DiagPlot=True, diffbaitPlot=True, suffix="", ctx=None, ihw=None, rng=None, device_write=False):
     """chicdiff.R:1956-2065.  ``ihw(pvalue, covariate, alpha)`` stands for IHW::ihw(pvalue ~ abs(avDist), data =

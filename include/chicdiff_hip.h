@@ -587,6 +587,70 @@ int chicdiff_hip_ihw_apply_dev(chicdiff_hip_ctx *ctx, const double *d_avDist, co
                                int32_t *d_group, double *d_weight, double *d_weighted_pvalue,
                                double *d_weighted_padj);
 
+/* limits of chicdiff_hip_ihw_train_dev (below) */
+#define CHICDIFF_IHW_MAX_BINS 256      /* ihw_apply's own limit */
+#define CHICDIFF_IHW_MAX_FOLDS 16
+#define CHICDIFF_IHW_PHILOX_STREAM 16u /* counter word 3 of the fold draws (the control draws use streams 0 and 1) */
+typedef struct {
+    int64_t m;         /* kept rows */
+    int32_t nbins;     /* the number of groups used */
+    int32_t nfolds;
+    int32_t chunk_len; /* IN: 0 = the default, or one of chicdiff_hip_ihw_caps' chunk lengths (results never depend on it); OUT: the one used */
+    int32_t _pad;
+    int64_t nseg[CHICDIFF_IHW_MAX_FOLDS]; /* segments of all groups, per fold */
+    double T[CHICDIFF_IHW_MAX_FOLDS];     /* step 5's T and H, per fold */
+    double H[CHICDIFF_IHW_MAX_FOLDS];
+} chicdiff_ihw_info;
+/* Training side of IHWcorrection: ihw(pvalue ~ abs(avDist), data = out.control, alpha = 0.05) (chicdiff.R:1994), as far as distLookup
+ * (:2012-2031) reads its result: the group of every row and the nbins x nfolds weight matrix.  This is THIS LIBRARY'S STATEMENT of
+ * independent hypothesis weighting, not a port of the IHW package (differences below).  Every operation of the rule is an integer
+ * operation, an IEEE double + - * / in the stated order (the library is built with -ffp-contract=off) or an exact comparison: the
+ * result is a pure function of the inputs, the same bits on every run, chunk length and launch shape.
+ *
+ * Inputs: d_pvalue[n], d_covariate[n] (device, float64), alpha in (0, 1), nbins (0 = auto), nfolds, a 64-bit seed.
+ *
+ * 1. Kept rows.  A row whose p-value is NaN is left out: its group is INT32_MIN and its fold -1, whatever its covariate.  m = the
+ *    number of kept rows.  A p-value of -0 is taken as +0.  nbins = 0 means max(1, min(40, m / 1500)) in integer division.  Limits:
+ *    1 <= nbins <= min(m, CHICDIFF_IHW_MAX_BINS), 2 <= nfolds <= CHICDIFF_IHW_MAX_FOLDS, n * nfolds < 2^31.
+ * 2. Groups (groups_by_filter: ceiling(rank(cov, ties = "first") / m * nbins)).  r_i = 1 + the number of kept rows that precede row i
+ *    in the stable order by covariate: -0 and +0 are equal, +Inf sorts last, ties go by row index.
+ *    group_i = ceil(((double)r_i / (double)m) * (double)nbins): exactly these two double operations; groups are 1-based.
+ * 3. Folds.  fold_i = ((uint64)w0 * nfolds) >> 32, w0 = word 0 of philox4x32_10(counter = (i & 0xffffffff, i >> 32, 0,
+ *    CHICDIFF_IHW_PHILOX_STREAM), key = (seed & 0xffffffff, seed >> 32)) (the generator of chicdiff_hip_control_draws_dev); i is the
+ *    row's index in the caller's array, so a row's fold does not depend on which rows are NA.
+ * 4. Grenander estimator of (fold f, group g).  P = the p-values of the kept rows of group g whose fold is NOT f, M = |P|.  The points
+ *    are (0, 0), then (u, c(u)) for every distinct u in P with c(u) = #{p in P: p <= u}, then (1, M); of points with equal x only the
+ *    one with the largest count is a point.  The knots are the vertices of the least concave majorant of the points: a point b between
+ *    its neighbours a and c (of the knots) is a knot iff (b.c - a.c) * (c.x - a.x) > (c.c - a.c) * (b.x - a.x) IN EXACT ARITHMETIC —
+ *    collinear points are not knots.  M = 0: the knots are (0, 0), (1, 1), and M is taken as 1.  Per segment j between consecutive
+ *    knots j - 1 and j, in double, in this order: d = x_j - x_{j-1}; dF = (double)(c_j - c_{j-1}) / (double)M; s = dF / d.
+ *    F(0) = (double)c_0 / (double)M, c_0 the count of the first knot (positive when P holds zeros).
+ * 5. Weights of fold f.  h_g = the kept rows of group g IN fold f, H = sum h_g (integers).  All segments of all groups are put in the
+ *    order (s descending, g ascending, j ascending).  B = 0; for g = 1, 2, ..: B = B - (alpha * (double)h_g) * F_g(0).  Walking the
+ *    order: cost = (double)h_g * (d - alpha * dF); while B + cost <= 0 the whole segment is taken: t_g = t_g + d, B = B + cost; at the
+ *    first segment where that fails t_g = t_g + (-B / cost) * d, and the walk stops.  T = sum_g (double)h_g * t_g, summed in group
+ *    order from 0.  w[g][f] = (t_g * (double)H) / T; T = 0 (H = 0 included): every weight of the fold is 1.
+ *    This is the exact optimum of IHW's linear programme without a regularisation term (maximise sum h_g F_g(t_g) subject to
+ *    sum h_g t_g <= alpha sum h_g F_g(t_g)): a fractional knapsack over segments ordered by slope.
+ *
+ * Differences from the package: no total-variation penalty and no nested cross-validation over lambdas (the rule is the package's
+ * with lambdas = Inf); folds from this library's Philox stream, not R's sample() under set.seed(1); no null-proportion adjustment;
+ * no adjusted p-values (Chicdiff discards them).  On null data the unregularised weights are valid through cross-weighting but erratic.
+ *
+ * Outputs: d_group[n], d_fold[n] (device int32; d_fold may be NULL); weights_host[nbins x nfolds], R's column-major matrix
+ * (w[g][f] at [g - 1 + nbins * f]); *info (its chunk_len is read first).  Everything is enqueued on the context's stream, with two host
+ * stops: the read of the verdicts and the segment total (which sizes the sort by slope), and the read of the weights and of info.
+ * CHICDIFF_E_INVALID, the message naming the cause and, where there is one, the row: a p-value outside [0, 1]; a NaN covariate on a
+ * kept row; no kept row; nbins > m or > CHICDIFF_IHW_MAX_BINS; nfolds outside its limits; alpha outside (0, 1); a chunk length not in
+ * chicdiff_hip_ihw_caps' list.  On a refusal the outputs are unspecified. */
+int chicdiff_hip_ihw_train_dev(chicdiff_hip_ctx *ctx, const double *d_pvalue, const double *d_covariate, int64_t n, double alpha,
+                               int32_t nbins, int32_t nfolds, uint64_t seed, int32_t *d_group, int32_t *d_fold, double *weights_host,
+                               chicdiff_ihw_info *info);
+/* The limits above, the largest automatic nbins, and the chunk lengths the library accepts (up to `cap` of them into chunk_lens,
+ * ascending, the last being the default; *nchunk_lens = how many there are).  Every pointer may be NULL. */
+int chicdiff_hip_ihw_caps(int32_t *max_bins, int32_t *max_folds, int32_t *auto_max_bins, int32_t *chunk_lens, int32_t cap,
+                          int32_t *nchunk_lens);
+
 /* f4 — getRegionUniverse, window mode (chicdiff.R:353-426).  For peak i (regionID i + 1): the otherEndIDs
  * .expandAvoidBait(baitID, oeID, RUexpand) (:353-367), kept when 1 <= ID <= maxfrag (:383-384) and on the bait's
  * chromosome (:386-401).  d_chr_of[0 .. maxfrag]: chromosome code of each restriction-map ID (-1 = ID not on
@@ -993,6 +1057,17 @@ int chicdiff_hip_selftest_trend_exchange(int32_t op, uint32_t tag, int64_t n, do
  * number of bins per column for S samples (<= 16); bin_out[n]: the bin of each key x (log count - row log geometric mean); sub_out[n] (may be NULL):
  * its sub-bin inside bin `sub_of`.  Both never decrease as x grows: all the select's exactness asks of them. */
 int chicdiff_hip_selftest_sf_bin(int32_t S, const double *x, int64_t n, int32_t *nbins_out, int32_t *bin_out, int32_t sub_of, int32_t *sub_out);
+/* _ihw_knots_dev: the knots of every (fold, group) of chicdiff_hip_ihw_train_dev's step 4, as the device finds them with chunks of
+ * `chunk_len` rows (0 = the default, else one of chicdiff_hip_ihw_caps' list), as CSR on the HOST: entry q = f * nbins + (g - 1) owns
+ * x_host / c_host [ptr_host[q] .. ptr_host[q + 1]).  *nbins_host = the groups used, *nknots_host = the knots in all.  Two calls: with
+ * cap = 0 only the two counts are written; else ptr_host needs nfolds * nbins + 1 entries and x_host, c_host `cap` >= *nknots_host. */
+int chicdiff_hip_selftest_ihw_knots_dev(chicdiff_hip_ctx *ctx, const double *d_pvalue, const double *d_covariate, int64_t n, int32_t nbins,
+                                        int32_t nfolds, uint64_t seed, int32_t chunk_len, int64_t cap, int64_t *ptr_host, double *x_host,
+                                        int32_t *c_host, int32_t *nbins_host, int64_t *nknots_host);
+/* _ihw_orient (host only, no context): step 4's exact knot test as compiled for the host, on n triples of points (x in [0, 1], count
+ * below 2^31): sign[i] = +1 when b lies strictly above the chord from a to c (a knot), 0 when the three are collinear, -1 below. */
+int chicdiff_hip_selftest_ihw_orient(const double *ax, const int32_t *ac, const double *bx, const int32_t *bc, const double *cx,
+                                     const int32_t *cc, int64_t n, int32_t *sign);
 
 /* Timing of the last *_dev call's kernels, measured with HIP events on the context's stream:
  * fills up to `cap` (name, milliseconds, launches) records; returns the number available. */
