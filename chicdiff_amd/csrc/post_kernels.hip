@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "devmath.h"
+#include "ru_window.h"
 
 namespace cd {
 
@@ -204,18 +205,8 @@ int launch_count_table(const int32_t *bait, const int32_t *oe, const int32_t *N,
 
 // ---- region universe (chicdiff.R:353-426) ----------------------------------------------------------------
 // .expandAvoidBait(bait, oe, s): (oe-s):(oe+s) unless the bait is within s+1 fragments, then the range stops two
-// fragments short of the bait.  R's a:b counts down when a > b, so the set is [min(a,b), max(a,b)].
-__device__ __forceinline__ bool expand_range(int bait, int oe, int s, int &lo, int &hi) {
-    const int dist = bait > oe ? bait - oe : oe - bait;
-    int a, b;
-    if (dist > s + 1) { a = oe - s; b = oe + s; }
-    else if (oe > bait) { a = bait + 2; b = oe + s; }
-    else if (oe < bait) { a = oe - s; b = bait - 2; }
-    else return false;  // stop("Invalid parameters ...")
-    lo = a < b ? a : b;
-    hi = a < b ? b : a;
-    return true;
-}
+// fragments short of the bait.  The window comes from ru_window() (ru_window.h: 64-bit arithmetic, clamped to [1, maxfrag]) in every
+// place that forms it, so mask base, mask width and the mask / walk choice (hi - lo < 32) follow the clamped window everywhere.
 // kept: 1 <= id <= maxfrag (the rmap join drops ids the map does not hold; `otherEndID <= maxfrag`, :384),
 // same chromosome as the bait (:399), bait itself on the map
 __device__ __forceinline__ bool ru_keep(int id, int bait_chr, const int32_t *chr_of, int maxfrag) {
@@ -228,7 +219,7 @@ __global__ __launch_bounds__(256) void ru_count_kernel(const int32_t *__restrict
         int lo, hi, cnt = 0, mn = INT32_MAX, mx = INT32_MIN;
         unsigned int mask = 0;  // bit (id - lo): candidate id is kept (windows of <= 32 candidates; what the fill kernel reads instead of walking)
         const int b = bait[i];
-        if (!expand_range(b, oe[i], s, lo, hi)) {
+        if (!ru_window(b, oe[i], s, maxfrag, lo, hi)) {
             atomicExch(bad, 1);
         } else {
             const int bc = (b >= 1 && b <= maxfrag) ? chr_of[b] : -1;
@@ -239,7 +230,7 @@ __global__ __launch_bounds__(256) void ru_count_kernel(const int32_t *__restrict
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     const int id = id0 + q;
-                    cc[q] = (id <= hi && id >= 1 && id <= maxfrag) ? chr_of[id] : -1;
+                    cc[q] = id <= hi ? chr_of[id] : -1;  // 1 <= lo <= id <= hi <= maxfrag < 2^30: on the table, and id0 + 4 fits
                 }
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
@@ -280,9 +271,9 @@ __global__ __launch_bounds__(256) void ru_fill_kernel(const int32_t *__restrict_
         if ((int)threadIdx.x <= nreg) s_ptr[threadIdx.x] = ptr[i0 + threadIdx.x];
         if (threadIdx.x == 0) s_ptr[nreg] = ptr[i0 + nreg];
         if ((int)threadIdx.x < nreg) {
-            int lo = 0, hi = -1;
+            int lo, hi;
             const int b = bait[i0 + threadIdx.x];
-            (void)expand_range(b, oe[i0 + threadIdx.x], s, lo, hi);
+            (void)ru_window(b, oe[i0 + threadIdx.x], s, maxfrag, lo, hi);  // (baitID == oeID: the empty window; the entry point refuses)
             const int bc = (b >= 1 && b <= maxfrag) ? chr_of[b] : -1;
             unsigned int mask = 0;
             if (mask_in) mask = mask_in[i0 + threadIdx.x];  // (left by ru_count_kernel in the one-call entry point: no gathers here at all)
@@ -367,6 +358,8 @@ __global__ __launch_bounds__(256) void region_avdist_kernel(const int32_t *__res
         int64_t cnt = 0;
         bool na = false;
         for (int64_t r = lo; r < hi; r++) {
+            // (a 32-bit subtraction, unlike the window of ru_window.h: with id_min >= 1 and nid < 2^31 - id_min a difference that wraps
+            // round is >= 2^31 - id_min > nid, so it cannot land inside [0, nid))
             const int32_t b = bait[r] - id_min, o = oe[r] - id_min;
             if (b < 0 || b >= nid || o < 0 || o >= nid || (chr && (chr[b] < 0 || chr[o] < 0)))
                 continue;  // a fragment the map does not hold: merge(x, rmap) drops the row (chicdiff.R:873-874)

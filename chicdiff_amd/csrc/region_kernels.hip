@@ -533,6 +533,8 @@ struct BgArgs {
 // bg_row_geometry: what is the same for every replicate — the two fragments' indices into the dense tables, whether both are on
 // the map, and log|distance| (0 where they are not: never read).
 __device__ __forceinline__ bool bg_row_geometry(const BgArgs &a, int32_t bait, int32_t oe, int32_t &b, int32_t &o, double &ld) {
+    // (32-bit subtractions: with id_min >= 1 and nid < 2^31 - id_min a difference that wraps round is >= 2^31 - id_min > nid, so it
+    // cannot land inside [0, nid); the region universe's window is another matter, see ru_window.h)
     b = bait - a.id_min;
     o = oe - a.id_min;
     const bool on_map = b >= 0 && b < a.nid && o >= 0 && o < a.nid;

@@ -1,6 +1,7 @@
 // stage_api.hip — entry points of the stages around the fit: one stream, one synchronisation per call.
 #include "ctx.h"
 #include "philox.h"
+#include "ru_window.h"
 
 extern "C" {
 
@@ -118,6 +119,8 @@ extern "C" int chicdiff_hip_region_universe_count_dev(chicdiff_hip_ctx *c, const
     if (!c) return CHICDIFF_E_INVALID;
     if (!d_bait || !d_oe || !d_chr_of || !d_region_ptr || !total_host || n < 1 || RUexpand < 0 || RUexpand > (1 << 20) || maxfrag < 1)
         return fail(c, CHICDIFF_E_INVALID, "region_universe: bad arguments");
+    if (maxfrag > kRuMaxFrag)
+        return fail(c, CHICDIFF_E_INVALID, "region_universe: maxfrag = %d (1 <= maxfrag < 2^30: the window's counters are 32-bit)", (int)maxfrag);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t scan = ru_scan_bytes(n);
     int rc = ensure_aux(c, 256 + scan);
@@ -145,6 +148,8 @@ extern "C" int chicdiff_hip_region_universe_fill_dev(chicdiff_hip_ctx *c, const 
     if (!c) return CHICDIFF_E_INVALID;
     if (!d_bait || !d_oe || !d_chr_of || !d_region_ptr || !d_ru_bait || !d_ru_region || !d_ru_oe || n < 1 || RUexpand < 0 || maxfrag < 1)
         return fail(c, CHICDIFF_E_INVALID, "region_universe: bad arguments");
+    if (maxfrag > kRuMaxFrag)
+        return fail(c, CHICDIFF_E_INVALID, "region_universe: maxfrag = %d (1 <= maxfrag < 2^30: the window's counters are 32-bit)", (int)maxfrag);
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
     {
@@ -166,6 +171,8 @@ extern "C" int chicdiff_hip_region_universe_dev(chicdiff_hip_ctx *c, const int32
     if (!d_bait || !d_oe || !d_chr_of || !d_region_ptr || !d_ru_bait || !d_ru_region || !d_ru_oe || !total_host || n < 1 || RUexpand < 0 ||
         RUexpand > (1 << 20) || maxfrag < 1)
         return fail(c, CHICDIFF_E_INVALID, "region_universe: bad arguments");
+    if (maxfrag > kRuMaxFrag)
+        return fail(c, CHICDIFF_E_INVALID, "region_universe: maxfrag = %d (1 <= maxfrag < 2^30: the window's counters are 32-bit)", (int)maxfrag);
     // rows per peak: (oe - s):(oe + s) = 2 s + 1 — or, for RUexpand = 0 and a peak right beside its bait, R's DESCENDING (bait + 2):(oe + 0): two
     const int64_t per_peak = RUexpand > 0 ? 2 * (int64_t)RUexpand + 1 : 2;
     if (capacity < n * per_peak)

@@ -326,7 +326,10 @@ int chicdiff_hip_fragment_background_dev(chicdiff_hip_ctx *ctx, const int32_t *d
  * setkey(x, baitID); x <- x[J(baits)] (chicdiff.R:828-831: only rows whose bait is an RU bait) and
  * setkey(temp, baitID, otherEndID) (:849).  d_bait_in_RU: one byte per ID 0..max_id (non-zero = keep) or NULL =
  * keep every row.  d_keys / d_vals hold nrows entries; the first *nkeys_host are the table, ascending in
- * (baitID << 32 | otherEndID).  The chinput text is read by host threads (chicdiff_hip_chinput_read) or, opt-in, parsed on the
+ * (baitID << 32 | otherEndID), the otherEndID as its 32-bit pattern (a negative one sorts behind the positive ones of its bait; a
+ * row with a negative baitID is dropped).  The sort is stable: rows that repeat a (baitID, otherEndID) pair stay in file order, each
+ * with its own N.  The joins are written for a table of unique pairs and promise nothing about which of the repeats they return.
+ * The chinput text is read by host threads (chicdiff_hip_chinput_read) or, opt-in, parsed on the
  * device (chicdiff_hip_chinput_read_dev); only the header line is host code in both. */
 int chicdiff_hip_count_table_dev(chicdiff_hip_ctx *ctx, const int32_t *d_bait, const int32_t *d_oe, const int32_t *d_N,
                                  int64_t nrows, const uint8_t *d_bait_in_RU, int32_t max_id, int64_t *d_keys,
@@ -657,7 +660,15 @@ int chicdiff_hip_ihw_caps(int32_t *max_bins, int32_t *max_folds, int32_t *auto_m
  * the map; entry 0 unused).  Two calls: _count fills d_region_ptr[n + 1] (CSR offsets), optional d_minOE /
  * d_maxOE (INT32_MIN for an empty region) and *total_host = number of RU rows; _fill writes the rows in
  * (regionID, otherEndID) order — RU.DT's own order is the stable sort of these rows by baitID after
- * otherEndID (setkey, :389/:393).  baitID == oeID is the reference's stop("Invalid parameters"): E_INVALID. */
+ * otherEndID (setkey, :389/:393).  baitID == oeID is the reference's stop("Invalid parameters"): E_INVALID.
+ *
+ * IDs off the map, at any int32 value (this holds for _count, _fill and the one call alike): d_bait and d_oe may hold every int32,
+ * INT32_MIN and INT32_MAX included.  The window is formed in 64-bit arithmetic and clamped to the map, [1, maxfrag]; IDs outside the
+ * map are never kept, so the clamp changes no row.  A peak whose window misses the map, or whose bait is not on it, gives an empty
+ * region (no rows, INT32_MIN in d_minOE / d_maxOE) and no refusal; baitID == oeID is refused whatever the ID.  The reference itself
+ * stops short of this: R's integer arithmetic gives NA where oeID + RUexpand or baitID + 2 overflows, and `NA:b` is an error.
+ * Limit: 1 <= maxfrag < 2^30 (a larger one is E_INVALID, the message naming the limit): with the window inside the map no 32-bit
+ * counter over it can overflow. */
 int chicdiff_hip_region_universe_count_dev(chicdiff_hip_ctx *ctx, const int32_t *d_bait, const int32_t *d_oe, int64_t n,
                                            int32_t RUexpand, const int32_t *d_chr_of, int32_t maxfrag,
                                            int64_t *d_region_ptr, int32_t *d_minOE, int32_t *d_maxOE,

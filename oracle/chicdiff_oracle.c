@@ -198,17 +198,22 @@ int64_t oracle_region_universe(const int32_t *bait, const int32_t *oe, int64_t n
                                int32_t maxfrag, int64_t *region_ptr, int32_t *ru_bait, int32_t *ru_region, int32_t *ru_oe) {
     int64_t pos = 0;
     for (int64_t i = 0; i < n; i++) {
-        const int b = bait[i], o = oe[i];
-        int a, e;
-        if (abs(b - o) > s + 1) { a = o - s; e = o + s; }
-        else if (o > b) { a = b + 2; e = o + s; }
-        else if (o < b) { a = o - s; e = b - 2; }
+        /* bait and oe are any int32, so o + s, o - s, b + 2, b - 2 and |b - o| need 64 bits; the window is clamped to the map
+         * [1, maxfrag] (IDs outside it are never kept), which also bounds the loop: in 32 bits a window near INT32_MAX wrapped round
+         * to the whole map, and `id <= hi` with hi = INT32_MAX never ended */
+        const int64_t b = bait[i], o = oe[i], w = s;
+        int64_t a, e;
+        if ((b > o ? b - o : o - b) > w + 1) { a = o - w; e = o + w; }
+        else if (o > b) { a = b + 2; e = o + w; }
+        else if (o < b) { a = o - w; e = b - 2; }
         else return -1;
-        const int lo = a < e ? a : e, hi = a < e ? e : a;
+        int64_t lo = a < e ? a : e, hi = a < e ? e : a;
+        if (lo < 1) lo = 1;
+        if (hi > maxfrag) hi = maxfrag;
         if (region_ptr) region_ptr[i] = pos;
         const int bc = (b >= 1 && b <= maxfrag) ? chr_of[b] : -1;
-        for (int id = lo; id <= hi; id++) {
-            if (id < 1 || id > maxfrag || bc < 0 || chr_of[id] != bc) continue;
+        for (int64_t id = lo; id <= hi; id++) {
+            if (bc < 0 || chr_of[id] != bc) continue;
             if (ru_bait) { ru_bait[pos] = b; ru_region[pos] = (int32_t)(i + 1); ru_oe[pos] = id; }
             pos++;
         }

@@ -369,15 +369,17 @@ def count_join_inner(ru_bait, ru_oe, tables):
 
 def count_table(bait, oe, N, bait_in_RU=None):
     """f2: chicdiff.R:826-831 and :849 on the parsed chinput columns: keep rows whose bait is an RU bait
-    (x[J(baits)]), key by (baitID, otherEndID).  Returns keys (baitID << 32 | otherEndID, ascending) and N."""
+    (x[J(baits)]), key by (baitID, otherEndID).  Returns keys (baitID << 32 | otherEndID, ascending) and N.  A row with a
+    negative bait is dropped; the otherEndID enters the key as its 32-bit pattern."""
     b = np.asarray(bait, dtype=np.int64)
     o = np.asarray(oe, dtype=np.int64)
     v = np.asarray(N, dtype=np.int32)
+    keep = b >= 0
     if bait_in_RU is not None:
         flags = np.asarray(bait_in_RU).astype(bool)
-        keep = (b < len(flags)) & flags[np.minimum(b, len(flags) - 1)]
-        b, o, v = b[keep], o[keep], v[keep]
-    keys = (b << 32) | o
+        keep &= (b < len(flags)) & flags[np.clip(b, 0, len(flags) - 1)]
+    b, o, v = b[keep], o[keep], v[keep]
+    keys = (b << 32) | (o & 0xFFFFFFFF)
     order = np.argsort(keys, kind="stable")
     return keys[order], v[order]
 

@@ -73,19 +73,15 @@ def test_count_join_inner_is_reduce_merge():
     S, nru = 3, 4000
     ru_bait = rng.integers(1, 30, nru).astype(np.int32)
     ru_oe = rng.integers(1, 200, nru).astype(np.int32)
-    tables, dicts = [], []
+    tables = []
     for s in range(S):
         b, o = rng.integers(1, 30, 3000), rng.integers(1, 200, 3000)
         k = np.unique((b.astype(np.int64) << 32) | o)
         v = rng.integers(0, 50, len(k)).astype(np.int32)   # a Chicago table may hold N = 0 rows: presence, not N > 0, decides
         tables.append((k, v))
-        dicts.append(dict(zip(k.tolist(), v.tolist())))
     got = oracle.count_join_inner(ru_bait, ru_oe, tables)
-    merged = set(dicts[0])
-    for d in dicts[1:]:
-        merged &= set(d)                                    # merge(): inner join on (baitID, otherEndID)
-    exp = np.zeros((nru, S), dtype=np.int32)
-    for r, key in enumerate(((ru_bait.astype(np.int64) << 32) | ru_oe).tolist()):
-        if key in merged:
-            exp[r] = [d[key] for d in dicts]                # merge(x, temp, all.x = TRUE); N[is.na(N)] <- 0
+    from region_twin import join_inner, reduce_merge, table_dict     # the dict version lives with the region stage's twin
+    dicts = [table_dict(k, v) for k, v in tables]                   # {(baitID, otherEndID): N}
+    merged = reduce_merge(dicts)                                    # merge(): inner join on (baitID, otherEndID)
+    exp = join_inner(ru_bait, ru_oe, dicts)                         # merge(x, temp, all.x = TRUE); N[is.na(N)] <- 0
     assert np.array_equal(got, exp) and (exp.sum(1) > 0).mean() > 0.05 and len(merged) < min(len(d) for d in dicts)
