@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 from chicdiff_amd import synth
+from sharded_transport import ThreadTransport as _ThreadTransport   # (shared with tests/test_gpu_sharded_small.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -180,63 +181,6 @@ def test_world4_processes_sharing_the_gpu_at_2Mx8_equal_the_single_rank_fit(refe
                 p.kill()
     assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
     _check_reports(reports, world)
-
-
-class _ThreadTransport:
-    """In-process stand-in for RCCL: the ranks are threads, each with its own context and stream; a collective waits for
-    every rank's stream, then adds (all-reduce) or lays out (all-gather) the ranks' device buffers in rank order."""
-
-    def __init__(self, world, torch, device):
-        from chicdiff_amd.dist import ALLGATHER_FN, ALLREDUCE_FN, _RawDevice
-        self.world, self.torch = world, torch
-        self.barrier = threading.Barrier(world, timeout=300)
-        self.slots = [None] * world
-        self.error = None
-        self.reduce_fns, self.gather_fns = [], []
-        view = lambda ptr, count: torch.as_tensor(_RawDevice(int(ptr), int(count)), device=device)
-
-        def make(rank):
-            def reduce_cb(_u, ptr, count):
-                try:
-                    self.slots[rank] = view(ptr, count)
-                    torch.cuda.synchronize()       # this rank's stream has produced the buffer (device-wide: simplest)
-                    self.barrier.wait()
-                    if rank == 0:
-                        acc = self.slots[0].clone()
-                        for r in range(1, world):  # fixed order
-                            acc += self.slots[r]
-                        self.total = acc
-                        torch.cuda.synchronize()
-                    self.barrier.wait()
-                    self.slots[rank].copy_(self.total)
-                    torch.cuda.synchronize()
-                    self.barrier.wait()
-                    return 0
-                except Exception as e:  # noqa: BLE001 — must not cross the C boundary
-                    self.error = e
-                    return 1
-
-            def gather_cb(_u, send, recv, count):
-                try:
-                    self.slots[rank] = view(send, count)
-                    torch.cuda.synchronize()
-                    self.barrier.wait()
-                    out = view(recv, int(count) * world)
-                    for r in range(world):
-                        out[r * int(count):(r + 1) * int(count)].copy_(self.slots[r])
-                    torch.cuda.synchronize()
-                    self.barrier.wait()
-                    return 0
-                except Exception as e:  # noqa: BLE001
-                    self.error = e
-                    return 1
-
-            return ALLREDUCE_FN(reduce_cb), ALLGATHER_FN(gather_cb)
-
-        for r in range(world):
-            a, g = make(r)
-            self.reduce_fns.append(a)
-            self.gather_fns.append(g)
 
 
 def _run_thread_ranks(world, ref_dir, n_rows=N_ROWS, S=S, legs=None):
