@@ -57,6 +57,10 @@ class Opts(C.Structure):
 OUT_DOUBLE = ["baseMean", "baseVar", "dispGeneEst", "dispFit", "dispMAP", "dispersion", "log2FoldChange",
               "lfcSE", "stat", "pvalue", "intercept", "interceptSE", "deviance", "maxCooks"]
 OUT_INT = ["dispGeneIter", "dispIter", "dispOutlier", "betaConv", "betaIter", "allZero", "cooksArgmax"]
+FIT_COLUMNS = ["baseMean", "dispersion", "log2FoldChange", "lfcSE", "stat", "pvalue"]   # what a device fit returns unless told otherwise
+
+
+_OUT_COLUMNS = {k: (f"outputs[{k!r}]", k in OUT_DOUBLE) for k in OUT_DOUBLE + OUT_INT}   # name -> (its argument's name, float64?)
 
 
 class Out(C.Structure):
@@ -213,6 +217,15 @@ def load_library() -> C.CDLL:
     L.chicdiff_hip_selftest_global_stage_dev.argtypes = [vp, vp, vp, vp, i64, i32, i32, C.POINTER(Opts), vp, vp, C.POINTER(dbl), C.POINTER(i32),
                                                          C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(Scalars)]
     L.chicdiff_hip_selftest_resid_hist_dev.argtypes = [vp, vp, i64, C.POINTER(dbl)]
+    # the host forms of device rules (no context): what the CPU tests call directly
+    u32, pd, pi = C.c_uint32, C.POINTER(dbl), C.POINTER(i32)
+    L.chicdiff_hip_selftest_chinput.argtypes = [C.c_char_p, i32, i64, pi, pi, pi, C.POINTER(i64), C.c_char_p, i32]
+    L.chicdiff_hip_selftest_r_random.argtypes = [i32, u32, dbl, dbl, i64, pd]
+    L.chicdiff_hip_selftest_prior_mc.argtypes = [i32, vp, vp, vp]
+    L.chicdiff_hip_selftest_sched_class.argtypes = [i32, dbl, pd, pd, i64, pi, pi]
+    L.chicdiff_hip_selftest_queue_claim.argtypes = [C.c_uint64, i32, u32, u32, i32, i32, C.POINTER(u32), pi]
+    L.chicdiff_hip_selftest_trend_exchange.argtypes = [i32, u32, i64, pd, C.POINTER(C.c_uint64), pi]
+    L.chicdiff_hip_selftest_sf_bin.argtypes = [i32, pd, i64, pi, pi, i32, pi]
     L.chicdiff_hip_kernel_times.argtypes = [vp, C.POINTER(KernelTime), i32]
     L.chicdiff_hip_kernel_times.restype = i32
     L.chicdiff_hip_enable_timing.argtypes = [vp, i32]
@@ -262,7 +275,8 @@ def selftest_ihw_orient(ax, ac, bx, bc, cx, cc):
     xs = [np.ascontiguousarray(v, dtype=np.float64) for v in (ax, bx, cx)]
     cs = [np.ascontiguousarray(v, dtype=np.int32) for v in (ac, bc, cc)]
     n = len(xs[0])
-    assert all(len(v) == n for v in xs + cs)
+    if any(v.shape != (n,) for v in xs + cs):
+        raise ValueError(f"selftest_ihw_orient: six vectors of one length are required, got shapes {[v.shape for v in xs + cs]}")
     out = np.empty(n, dtype=np.int32)
     rc = load_library().chicdiff_hip_selftest_ihw_orient(xs[0].ctypes.data, cs[0].ctypes.data, xs[1].ctypes.data, cs[1].ctypes.data,
                                                          xs[2].ctypes.data, cs[2].ctypes.data, n, out.ctypes.data)
@@ -501,6 +515,11 @@ class Peaks:
                 setattr(self, name, ints[k])
 
 
+def _contiguous(t):
+    """A column of a ``Peaks`` laid out for the C ABI (anything but a tensor goes on as it is, to the marshalling layer's refusal)."""
+    return t.contiguous() if hasattr(t, "contiguous") else t
+
+
 def _scalars_dict(s: Scalars) -> dict:
     return dict(trendCoef=np.array(s.trendCoef[:]), varLogDispEsts=s.varLogDispEsts, dispPriorVar=s.dispPriorVar,
                 sumDeviance=s.sumDeviance, nAllZero=s.nAllZero, trendOuterIter=s.trendOuterIter, status=s.status)
@@ -627,62 +646,15 @@ class HipContext:
         t = self.torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=dtype).T))
         return t.to(self.device)
 
-    # -- a5 ---------------------------------------------------------------------------------
-    def size_factors(self, d_counts) -> np.ndarray:
-        S, n = d_counts.shape
-        sf = (C.c_double * S)()
-        self._check(self.lib.chicdiff_hip_size_factors_dev(self.h, d_counts.data_ptr(), n, S, sf))
-        return np.array(sf[:])
-
-    # -- a4 ---------------------------------------------------------------------------------
-    def offsets(self, d_fullmean, size_factors, theta=None, out=None):
-        S, n = d_fullmean.shape
-        sf = (C.c_double * S)(*[float(x) for x in size_factors])
-        if out is None:
-            out = self.torch.empty_like(d_fullmean)
-        th = float("nan") if theta is None else float(theta)
-        self._check(self.lib.chicdiff_hip_offsets_dev(self.h, d_fullmean.data_ptr(), sf, n, S, th, out.data_ptr()))
-        return out
-
-    # -- a2 ---------------------------------------------------------------------------------
-    def window_sums(self, d_fragN, d_fragFM, d_region_ptr):
-        torch = self.torch
-        ref = d_fragN if d_fragN is not None else d_fragFM
-        S, nfrag = ref.shape
-        n = d_region_ptr.numel() - 1
-        N = torch.empty((S, n), dtype=torch.int32, device=self.device) if d_fragN is not None else None
-        FM = torch.empty((S, n), dtype=torch.float64, device=self.device) if d_fragFM is not None else None
-        self._check(self.lib.chicdiff_hip_window_sums_dev(
-            self.h, d_fragN.data_ptr() if d_fragN is not None else None,
-            d_fragFM.data_ptr() if d_fragFM is not None else None, nfrag, S, d_region_ptr.data_ptr(), n,
-            N.data_ptr() if N is not None else None, FM.data_ptr() if FM is not None else None))
-        return N, FM
-
-    # -- a1 ---------------------------------------------------------------------------------
-    def count_join(self, d_bait, d_oe, d_keys, d_vals):
-        out = self.torch.empty_like(d_bait)
-        self._check(self.lib.chicdiff_hip_count_join_dev(self.h, d_bait.data_ptr(), d_oe.data_ptr(), d_bait.numel(),
-                                                         d_keys.data_ptr(), d_vals.data_ptr(), d_keys.numel(),
-                                                         out.data_ptr()))
-        return out
-
-    def count_join_multi(self, d_bait, d_oe, tables, out=None):
-        """The chinput branch for all replicates at once (chicdiff.R:843-858, the loop over the replicates): ``tables`` =
-        [(keys, vals)] per replicate; N (S, nru), row s = ``count_join`` with table s, from ONE read of the RU rows."""
-        S, nru = len(tables), d_bait.numel()
-        if out is None:
-            out = self.torch.empty((S, nru), dtype=self.torch.int32, device=self.device)
-        assert out.shape == (S, nru) and out.dtype == self.torch.int32 and out.is_contiguous() and S >= 1
-        kp = (C.c_void_p * S)(*[k.data_ptr() for k, _ in tables])
-        vp_ = (C.c_void_p * S)(*[v.data_ptr() for _, v in tables])
-        nk = (C.c_int64 * S)(*[k.numel() for k, _ in tables])
-        self._check(self.lib.chicdiff_hip_count_join_multi_dev(self.h, d_bait.data_ptr(), d_oe.data_ptr(), nru, S, kp, vp_, nk,
-                                                               out.data_ptr()))
-        return out
-
+    # -- marshalling: the one way a caller's object reaches the C ABI -------------------------------------
+    # (One exception, kept as it was: the columns of ``table_text`` / ``write_table`` go through ``table_columns`` above.  Its rule is
+    # another one — a column may have one of three dtypes, all columns share a row count — it also serves ``table_check``, which has no
+    # context or device, and the tests hold its messages word for word.)
     def _check_tensor(self, name, t, dtype, shape=None):
         """ValueError unless ``t`` is a contiguous tensor of ``dtype`` on this context's device (and of ``shape``, -1 = any)."""
         torch = self.torch
+        if isinstance(t, torch.Tensor) and t.dtype is dtype and t.device == self.device and t.is_contiguous() and (shape is None or t.shape == shape):
+            return                                                     # (the whole rule at once; below, which part of it failed)
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name}: a torch tensor is required, got {type(t).__name__}")
         if t.dtype != dtype:
@@ -694,6 +666,165 @@ class HipContext:
         if shape is not None and (t.dim() != len(shape) or any(w != -1 and w != g for w, g in zip(shape, t.shape))):
             raise ValueError(f"{name}: shape {tuple(shape)} is required (-1 = any), got {tuple(t.shape)}")
 
+    def _ptr(self, name, t, dtype, shape=None):
+        """``_check_tensor``, then the tensor's device address."""
+        self._check_tensor(name, t, dtype, shape)
+        return t.data_ptr()
+
+    def _ptr_or_none(self, name, t, dtype, shape=None):
+        """``_ptr``; None stays None, the C ABI's NULL for an argument left out."""
+        return None if t is None else self._ptr(name, t, dtype, shape)
+
+    def _tables(self, who, tables):
+        """``tables`` = [(keys, vals)] per replicate, int64 / int32 device vectors of one length each, 1 <= S <= 64 of them ->
+        (S, keys' addresses, vals' addresses, lengths) as the C ABI takes them."""
+        torch = self.torch
+        try:
+            S = len(tables)
+        except TypeError:
+            raise ValueError(f"{who}: tables must be a sequence of (keys, vals) pairs") from None
+        if not 1 <= S <= 64:
+            raise ValueError(f"{who}: 1 <= S <= 64 replicates are supported, got {S}")
+        kp, vp, nk = (C.c_void_p * S)(), (C.c_void_p * S)(), (C.c_int64 * S)()
+        for s, kv in enumerate(tables):
+            if not isinstance(kv, (tuple, list)) or len(kv) != 2:
+                raise ValueError(f"tables[{s}]: a (keys, vals) pair is required")
+            kp[s] = self._ptr(f"tables[{s}] keys", kv[0], torch.int64, (-1,))
+            vp[s] = self._ptr(f"tables[{s}] vals", kv[1], torch.int32, (-1,))
+            nk[s] = kv[0].numel()
+            if kv[0].numel() != kv[1].numel():
+                raise ValueError(f"tables[{s}]: {kv[0].numel()} keys but {kv[1].numel()} vals")
+        return S, kp, vp, nk
+
+    def _matrices(self, name, d_counts, d_other):
+        """The counts, int32 (S, n), and the float64 matrix ``name`` of the same shape beside them -> (their addresses, S, n)."""
+        pk = self._ptr("d_counts", d_counts, self.torch.int32, (-1, -1))
+        S, n = d_counts.shape
+        return pk, self._ptr(name, d_other, self.torch.float64, (S, n)), S, n
+
+    @staticmethod
+    def _group(group, S):
+        """The condition code of every sample, S integers -> int32[S]."""
+        g = np.asarray(group)
+        if g.dtype.kind not in "iu" or g.ndim != 1:
+            raise ValueError(f"group: a sequence of {S} integers is required, got {group!r}")
+        if len(g) != S:
+            raise ValueError(f"group: one entry per sample ({S}) is required, got {len(g)}")
+        return (C.c_int32 * S)(*g.tolist())
+
+    def _outputs(self, want, default, n, outputs=None, host=False):
+        """The columns asked for -> (Out, {name: buffer of n entries}).  ``outputs``: the caller's device buffers by name, used where
+        present; ``host``: numpy buffers instead of device tensors (always fresh)."""
+        torch = self.torch
+        out, bufs, shape = Out(), ({} if outputs is None else outputs), (n,)
+        for k in (default if want is None else want):
+            column = _OUT_COLUMNS.get(k)
+            if column is None:
+                raise ValueError(f"want: unknown column {k!r}; the columns are {OUT_DOUBLE + OUT_INT}")
+            name, double = column
+            if host:
+                bufs[k] = np.empty(n, dtype=np.float64 if double else np.int32)
+                setattr(out, k, bufs[k].ctypes.data)
+                continue
+            dtype = torch.float64 if double else torch.int32
+            if k not in bufs:
+                bufs[k] = torch.empty(n, dtype=dtype, device=self.device)
+            setattr(out, k, self._ptr(name, bufs[k], dtype, shape))
+        return out, bufs
+
+    @staticmethod
+    def _opts(opts):
+        """``Opts`` or None (the library's defaults) -> what the C ABI takes for ``const chicdiff_nbglm_opts *``."""
+        if opts is None:
+            return None
+        if not isinstance(opts, Opts):
+            raise ValueError(f"opts: an Opts (hip.default_opts(...)) or None is required, got {type(opts).__name__}")
+        return C.byref(opts)
+
+    @staticmethod
+    def _seed(who, seed):
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+            raise ValueError(f"{who}: seed must be an integer in [0, 2^64), got {seed!r}")
+        return int(seed)
+
+    @staticmethod
+    def _host(name, a, dtype, shape):
+        """A host vector or matrix -> (contiguous numpy array of ``dtype`` and ``shape``, -1 = any; its address as the C ABI's typed
+        pointer).  The array is to be kept alive for the call."""
+        try:
+            a = np.ascontiguousarray(a, dtype=dtype)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}: numbers convertible to {np.dtype(dtype).name} are required, got {type(a).__name__}") from None
+        if a.ndim != len(shape) or any(w != -1 and w != g for w, g in zip(shape, a.shape)):
+            raise ValueError(f"{name}: shape {tuple(shape)} is required{' (-1 = any)' if -1 in shape else ''}, got {a.shape}")
+        return a, a.ctypes.data_as(C.POINTER(C.c_double if dtype is np.float64 else C.c_int32))
+
+    # -- a5 ---------------------------------------------------------------------------------
+    def size_factors(self, d_counts) -> np.ndarray:
+        dc = self._ptr("d_counts", d_counts, self.torch.int32, (-1, -1))
+        S, n = d_counts.shape
+        sf = (C.c_double * S)()
+        self._check(self.lib.chicdiff_hip_size_factors_dev(self.h, dc, n, S, sf))
+        return np.array(sf[:])
+
+    # -- a4 ---------------------------------------------------------------------------------
+    def offsets(self, d_fullmean, size_factors, theta=None, out=None):
+        torch = self.torch
+        dfm = self._ptr("d_fullmean", d_fullmean, torch.float64, (-1, -1))
+        S, n = d_fullmean.shape
+        sf, psf = self._host("size_factors", size_factors, np.float64, (S,))
+        if out is None:
+            out = torch.empty_like(d_fullmean)
+        pout = self._ptr("out", out, torch.float64, (S, n))
+        th = float("nan") if theta is None else float(theta)
+        self._check(self.lib.chicdiff_hip_offsets_dev(self.h, dfm, psf, n, S, th, pout))
+        return out
+
+    # -- a2 ---------------------------------------------------------------------------------
+    def window_sums(self, d_fragN, d_fragFM, d_region_ptr):
+        torch = self.torch
+        if d_fragN is not None:
+            self._check_tensor("d_fragN", d_fragN, torch.int32, (-1, -1))
+            S, nfrag = d_fragN.shape
+        else:
+            self._check_tensor("d_fragFM", d_fragFM, torch.float64, (-1, -1))
+            S, nfrag = d_fragFM.shape
+        pN = self._ptr_or_none("d_fragN", d_fragN, torch.int32, (S, nfrag))
+        pFM = self._ptr_or_none("d_fragFM", d_fragFM, torch.float64, (S, nfrag))
+        ptr = self._ptr("d_region_ptr", d_region_ptr, torch.int64, (-1,))
+        n = d_region_ptr.numel() - 1
+        N = torch.empty((S, n), dtype=torch.int32, device=self.device) if d_fragN is not None else None
+        FM = torch.empty((S, n), dtype=torch.float64, device=self.device) if d_fragFM is not None else None
+        self._check(self.lib.chicdiff_hip_window_sums_dev(self.h, pN, pFM, nfrag, S, ptr, n, N.data_ptr() if N is not None else None,
+                                                          FM.data_ptr() if FM is not None else None))
+        return N, FM
+
+    # -- a1 ---------------------------------------------------------------------------------
+    def count_join(self, d_bait, d_oe, d_keys, d_vals):
+        torch = self.torch
+        pb = self._ptr("d_bait", d_bait, torch.int32, (-1,))
+        nru = d_bait.numel()
+        po = self._ptr("d_oe", d_oe, torch.int32, (nru,))
+        pk = self._ptr("d_keys", d_keys, torch.int64, (-1,))
+        pv = self._ptr("d_vals", d_vals, torch.int32, (d_keys.numel(),))
+        out = torch.empty_like(d_bait)
+        self._check(self.lib.chicdiff_hip_count_join_dev(self.h, pb, po, nru, pk, pv, d_keys.numel(), out.data_ptr()))
+        return out
+
+    def count_join_multi(self, d_bait, d_oe, tables, out=None):
+        """The chinput branch for all replicates at once (chicdiff.R:843-858, the loop over the replicates): ``tables`` =
+        [(keys, vals)] per replicate; N (S, nru), row s = ``count_join`` with table s, from ONE read of the RU rows."""
+        torch = self.torch
+        S, kp, vp, nk = self._tables("count_join_multi", tables)
+        pb = self._ptr("d_bait", d_bait, torch.int32, (-1,))
+        nru = d_bait.numel()
+        po = self._ptr("d_oe", d_oe, torch.int32, (nru,))
+        if out is None:
+            out = torch.empty((S, nru), dtype=torch.int32, device=self.device)
+        pout = self._ptr("out", out, torch.int32, (S, nru))
+        self._check(self.lib.chicdiff_hip_count_join_multi_dev(self.h, pb, po, nru, S, kp, vp, nk, pout))
+        return out
+
     def region_assemble(self, d_bait, d_oe, d_region_ptr, tables, id_min, d_midsum, d_sj, d_si, d_tblb, d_tlb, d_T, distfun,
                         want_N=True, want_FullMean=True):
         """Region-level N and FullMean (S, n) of the chinput branch in one kernel (chicdiff.R:843-858, 628-703, 894-896, 1540-1547):
@@ -703,73 +834,68 @@ class HipContext:
         torch = self.torch
         if not (want_N or want_FullMean):
             raise ValueError("region_assemble: neither N nor FullMean is wanted")
-        try:
-            S = len(tables)
-        except TypeError:
-            raise ValueError("region_assemble: tables must be a sequence of (keys, vals) pairs") from None
-        if not 1 <= S <= 64:
-            raise ValueError(f"region_assemble: 1 <= S <= 64 replicates are supported, got {S}")
-        self._check_tensor("d_bait", d_bait, torch.int32, (-1,))
-        self._check_tensor("d_oe", d_oe, torch.int32, (d_bait.numel(),))
-        self._check_tensor("d_region_ptr", d_region_ptr, torch.int64, (-1,))
-        nru, n = d_bait.numel(), d_region_ptr.numel() - 1
+        S, kp, vp, nk = self._tables("region_assemble", tables)
+        pb = self._ptr("d_bait", d_bait, torch.int32, (-1,))
+        nru = d_bait.numel()
+        po = self._ptr("d_oe", d_oe, torch.int32, (nru,))
+        ptr = self._ptr("d_region_ptr", d_region_ptr, torch.int64, (-1,))
+        n = d_region_ptr.numel() - 1
         if n < 1:
             raise ValueError("region_assemble: region_ptr must hold at least one region (two entries)")
-        for s, kv in enumerate(tables):
-            if not isinstance(kv, (tuple, list)) or len(kv) != 2:
-                raise ValueError(f"tables[{s}]: a (keys, vals) pair is required")
-            self._check_tensor(f"tables[{s}] keys", kv[0], torch.int64, (-1,))
-            self._check_tensor(f"tables[{s}] vals", kv[1], torch.int32, (-1,))
-            if kv[0].numel() != kv[1].numel():
-                raise ValueError(f"tables[{s}]: {kv[0].numel()} keys but {kv[1].numel()} vals")
-        self._check_tensor("d_midsum", d_midsum, torch.int64, (-1,))
+        nid, pm, tabs, _df = self._background(S, d_midsum, d_sj, d_si, d_tblb, d_tlb, d_T, distfun)
+        N = torch.empty((S, n), dtype=torch.int32, device=self.device) if want_N else None
+        FM = torch.empty((S, n), dtype=torch.float64, device=self.device) if want_FullMean else None
+        self._check(self.lib.chicdiff_hip_region_assemble_dev(
+            self.h, pb, po, nru, ptr, n, S, kp, vp, nk, int(id_min), nid, pm, *tabs,
+            N.data_ptr() if want_N else None, FM.data_ptr() if want_FullMean else None))
+        return N, FM
+
+    def _background(self, S, d_midsum, d_sj, d_si, d_tblb, d_tlb, d_T, distfun):
+        """The Chicago background tables of S replicates as ``region_assemble`` and ``fragment_background`` take them -> (nid, d_midsum's
+        address, the C ABI's eight arguments from d_sj to distfun_host, which follow one another in both entry points, and the
+        distfun array those point into, to be kept alive for the call)."""
+        torch = self.torch
+        pm = self._ptr("d_midsum", d_midsum, torch.int64, (-1,))
         nid = d_midsum.numel()
         if nid < 1:
             raise ValueError("d_midsum: empty restriction map")
-        self._check_tensor("d_sj", d_sj, torch.float64, (S, nid))
-        self._check_tensor("d_si", d_si, torch.float64, (S, nid))
-        self._check_tensor("d_tblb", d_tblb, torch.int32, (S, nid))
-        self._check_tensor("d_tlb", d_tlb, torch.int32, (S, nid))
-        self._check_tensor("d_T", d_T, torch.float64, (S, -1, -1))
+        psj = self._ptr("d_sj", d_sj, torch.float64, (S, nid))
+        psi = self._ptr("d_si", d_si, torch.float64, (S, nid))
+        ptb = self._ptr("d_tblb", d_tblb, torch.int32, (S, nid))
+        ptl = self._ptr("d_tlb", d_tlb, torch.int32, (S, nid))
+        pT = self._ptr("d_T", d_T, torch.float64, (S, -1, -1))
         if d_T.shape[1] < 1 or d_T.shape[2] < 1:
             raise ValueError(f"d_T: shape (S, ntblb >= 1, ntlb >= 1) is required, got {tuple(d_T.shape)}")
-        df = np.ascontiguousarray(distfun, dtype=np.float64)
-        if df.shape != (S, 10):
-            raise ValueError(f"distfun: shape ({S}, 10) is required, got {df.shape}")
-        N = torch.empty((S, n), dtype=torch.int32, device=self.device) if want_N else None
-        FM = torch.empty((S, n), dtype=torch.float64, device=self.device) if want_FullMean else None
-        kp = (C.c_void_p * S)(*[k.data_ptr() for k, _ in tables])
-        vp_ = (C.c_void_p * S)(*[v.data_ptr() for _, v in tables])
-        nk = (C.c_int64 * S)(*[k.numel() for k, _ in tables])
-        self._check(self.lib.chicdiff_hip_region_assemble_dev(
-            self.h, d_bait.data_ptr(), d_oe.data_ptr(), nru, d_region_ptr.data_ptr(), n, S, kp, vp_, nk, int(id_min), nid,
-            d_midsum.data_ptr(), d_sj.data_ptr(), d_si.data_ptr(), d_tblb.data_ptr(), d_tlb.data_ptr(), d_T.data_ptr(),
-            d_T.shape[1], d_T.shape[2], df.ctypes.data_as(C.POINTER(C.c_double)),
-            N.data_ptr() if want_N else None, FM.data_ptr() if want_FullMean else None))
-        return N, FM
+        df, pdf = self._host("distfun", distfun, np.float64, (S, 10))
+        return nid, pm, (psj, psi, ptb, ptl, pT, d_T.shape[1], d_T.shape[2], pdf), df
 
     def count_join_inner(self, d_bait, d_oe, tables):
         """No-chinput branch (chicdiff.R:774-807): ``tables`` = [(keys, vals)] per replicate (device tensors as
         ``count_table`` returns them); N (S, nru) with the reference's Reduce(merge) semantics — a pair keeps its
         counts only when every replicate's table holds it."""
-        S, nru = len(tables), d_bait.numel()
-        out = self.torch.empty((S, nru), dtype=self.torch.int32, device=self.device)
-        kp = (C.c_void_p * S)(*[k.data_ptr() for k, _ in tables])
-        vp_ = (C.c_void_p * S)(*[v.data_ptr() for _, v in tables])
-        nk = (C.c_int64 * S)(*[k.numel() for k, _ in tables])
-        self._check(self.lib.chicdiff_hip_count_join_inner_dev(self.h, d_bait.data_ptr(), d_oe.data_ptr(), nru, S, kp, vp_, nk,
-                                                               out.data_ptr()))
+        torch = self.torch
+        S, kp, vp, nk = self._tables("count_join_inner", tables)
+        pb = self._ptr("d_bait", d_bait, torch.int32, (-1,))
+        nru = d_bait.numel()
+        po = self._ptr("d_oe", d_oe, torch.int32, (nru,))
+        out = torch.empty((S, nru), dtype=torch.int32, device=self.device)
+        self._check(self.lib.chicdiff_hip_count_join_inner_dev(self.h, pb, po, nru, S, kp, vp, nk, out.data_ptr()))
         return out
 
     def region_avdist(self, d_bait, d_oe, d_region_ptr, id_min, d_midsum, d_chr=None):
         """avDist = mean(distSign) by regionID (chicdiff.R:1965-1967, :868-882) for CSR-ordered RU rows: the covariate
         IHWcorrection() takes from the long table."""
+        torch = self.torch
+        pb = self._ptr("d_bait", d_bait, torch.int32, (-1,))
+        nru = d_bait.numel()
+        po = self._ptr("d_oe", d_oe, torch.int32, (nru,))
+        ptr = self._ptr("d_region_ptr", d_region_ptr, torch.int64, (-1,))
+        pm = self._ptr("d_midsum", d_midsum, torch.int64, (-1,))
+        nid = d_midsum.numel()
+        pc = self._ptr_or_none("d_chr", d_chr, torch.int32, (nid,))
         n = d_region_ptr.numel() - 1
-        out = self.torch.empty(n, dtype=self.torch.float64, device=self.device)
-        self._check(self.lib.chicdiff_hip_region_avdist_dev(self.h, d_bait.data_ptr(), d_oe.data_ptr(), d_bait.numel(),
-                                                            d_region_ptr.data_ptr(), n, int(id_min), d_midsum.numel(),
-                                                            d_midsum.data_ptr(), d_chr.data_ptr() if d_chr is not None else None,
-                                                            out.data_ptr()))
+        out = torch.empty(n, dtype=torch.float64, device=self.device)
+        self._check(self.lib.chicdiff_hip_region_avdist_dev(self.h, pb, po, nru, ptr, n, int(id_min), nid, pm, pc, out.data_ptr()))
         return out
 
     # -- a3 ---------------------------------------------------------------------------------
@@ -777,16 +903,15 @@ class HipContext:
         """Bmean, Tmean, FullMean (S, nru) for RU rows (d_bait, d_oe); tables as in the header.  ``only_fullmean``: the first two
         come back as None and are never written (FullMean is the one column DESeq2Wrap reads, chicdiff.R:896, :1543)."""
         torch = self.torch
-        S, nid = d_sj.shape
+        pb = self._ptr("d_bait", d_bait, torch.int32, (-1,))
         nru = d_bait.numel()
-        df = np.ascontiguousarray(distfun, dtype=np.float64)
-        assert df.shape == (S, 10) and d_T.shape[0] == S
+        po = self._ptr("d_oe", d_oe, torch.int32, (nru,))
+        self._check_tensor("d_sj", d_sj, torch.float64, (-1, -1))
+        S = d_sj.shape[0]
+        nid, pm, tabs, _df = self._background(S, d_midsum, d_sj, d_si, d_tblb, d_tlb, d_T, distfun)
         outs = [None if (only_fullmean and k < 2) else torch.empty((S, nru), dtype=torch.float64, device=self.device) for k in range(3)]
-        ptr = lambda t: t.data_ptr() if t is not None else None
         self._check(self.lib.chicdiff_hip_fragment_background_dev(
-            self.h, d_bait.data_ptr(), d_oe.data_ptr(), nru, int(id_min), nid, d_midsum.data_ptr(), S, d_sj.data_ptr(),
-            d_si.data_ptr(), d_tblb.data_ptr(), d_tlb.data_ptr(), d_T.data_ptr(), d_T.shape[1], d_T.shape[2],
-            df.ctypes.data_as(C.POINTER(C.c_double)), ptr(outs[0]), ptr(outs[1]), ptr(outs[2])))
+            self.h, pb, po, nru, int(id_min), nid, pm, S, *tabs, *[None if t is None else t.data_ptr() for t in outs]))
         return outs
 
     # -- f2: chinput columns -> key table of the count join -------------------------------------
@@ -794,36 +919,47 @@ class HipContext:
         """(keys, vals) of ``count_join`` from unsorted chinput columns; rows whose bait is not flagged in
         ``d_bait_in_RU`` (uint8 per ID) are dropped (chicdiff.R:828-831, :849)."""
         torch = self.torch
+        pb = self._ptr("d_bait", d_bait, torch.int32, (-1,))
         n = d_bait.numel()
+        po, pN = self._ptr("d_oe", d_oe, torch.int32, (n,)), self._ptr("d_N", d_N, torch.int32, (n,))
+        pf, max_id = self._bait_flags(d_bait_in_RU)
         keys = torch.empty(n, dtype=torch.int64, device=self.device)
         vals = torch.empty(n, dtype=torch.int32, device=self.device)
         nk = C.c_int64(0)
-        self._check(self.lib.chicdiff_hip_count_table_dev(
-            self.h, d_bait.data_ptr(), d_oe.data_ptr(), d_N.data_ptr(), n,
-            d_bait_in_RU.data_ptr() if d_bait_in_RU is not None else None,
-            d_bait_in_RU.numel() - 1 if d_bait_in_RU is not None else 0, keys.data_ptr(), vals.data_ptr(), C.byref(nk)))
+        self._check(self.lib.chicdiff_hip_count_table_dev(self.h, pb, po, pN, n, pf, max_id, keys.data_ptr(), vals.data_ptr(), C.byref(nk)))
         return keys[: nk.value], vals[: nk.value]
+
+    def _bait_flags(self, d_bait_in_RU):
+        """uint8 per ID 0 .. max_id (non-zero = keep), or None = keep every bait -> (address, max_id)."""
+        if d_bait_in_RU is None:
+            return None, 0
+        return self._ptr("d_bait_in_RU", d_bait_in_RU, self.torch.uint8, (-1,)), d_bait_in_RU.numel() - 1
+
+    def _text(self, d_text):
+        """The body of a text file, a one-dimensional uint8 device tensor -> (the tensor, or its copy on a 16-byte boundary where it
+        does not start on one; its address)."""
+        pt = self._ptr("d_text", d_text, self.torch.uint8, (-1,))
+        if pt % 16:
+            d_text = d_text.clone()
+            pt = d_text.data_ptr()
+        return d_text, pt
 
     def parse_chinput_text(self, d_text, cols):
         """The body of a .chinput file (the bytes after its header line) as a uint8 device tensor -> (bait, oe, N), int32 device
         tensors in file order; ``cols`` = the 0-based columns (ib, io, in) of baitID, otherEndID, N.  The rule stands above
         chicdiff_hip_chinput_parse_dev in include/chicdiff_hip.h.  A malformed line raises, the message naming its byte offset."""
         torch = self.torch
-        if d_text.dtype != torch.uint8 or d_text.dim() != 1:
-            raise ValueError("parse_chinput_text: d_text is a one-dimensional uint8 tensor")
-        d_text = d_text.contiguous()
-        if d_text.data_ptr() % 16:
-            d_text = d_text.clone()
+        d_text, pt = self._text(d_text)
         n = d_text.numel()
         ib, io, in_ = (int(x) for x in cols)
         nrows, bad = C.c_int64(0), C.c_int64(-1)
         # first with no room at all: the call reports the row count before it writes anything
-        rc = self.lib.chicdiff_hip_chinput_parse_dev(self.h, d_text.data_ptr(), n, ib, io, in_, None, None, None, 0, C.byref(nrows), C.byref(bad))
+        rc = self.lib.chicdiff_hip_chinput_parse_dev(self.h, pt, n, ib, io, in_, None, None, None, 0, C.byref(nrows), C.byref(bad))
         if rc and nrows.value == 0:
             self._check(rc)
         out = [torch.empty(nrows.value, dtype=torch.int32, device=self.device) for _ in range(3)]
         if nrows.value:
-            rc = self.lib.chicdiff_hip_chinput_parse_dev(self.h, d_text.data_ptr(), n, ib, io, in_, out[0].data_ptr(), out[1].data_ptr(),
+            rc = self.lib.chicdiff_hip_chinput_parse_dev(self.h, pt, n, ib, io, in_, out[0].data_ptr(), out[1].data_ptr(),
                                                          out[2].data_ptr(), nrows.value, C.byref(nrows), C.byref(bad))
             if rc:
                 err = ChicdiffHipError(f"[{rc}] " + self.lib.chicdiff_hip_last_error(self.h).decode())
@@ -837,6 +973,7 @@ class HipContext:
         as bytes and is parsed there (chicdiff_hip_chinput_read_dev; ``nthreads`` is not used: the upload runs with the context's
         host_copy_threads) — the same triple."""
         torch = self.torch
+        pf, max_id = self._bait_flags(d_bait_in_RU)
         nrows = C.c_int64(0)
         if device:
             self._check(self.lib.chicdiff_hip_chinput_read_dev(self.h, os.fsencode(path), C.byref(nrows)))
@@ -845,9 +982,7 @@ class HipContext:
         keys = torch.empty(nrows.value, dtype=torch.int64, device=self.device)
         vals = torch.empty(nrows.value, dtype=torch.int32, device=self.device)
         nk = C.c_int64(0)
-        self._check(self.lib.chicdiff_hip_chinput_table_dev(
-            self.h, d_bait_in_RU.data_ptr() if d_bait_in_RU is not None else None,
-            d_bait_in_RU.numel() - 1 if d_bait_in_RU is not None else 0, keys.data_ptr(), vals.data_ptr(), C.byref(nk)))
+        self._check(self.lib.chicdiff_hip_chinput_table_dev(self.h, pf, max_id, keys.data_ptr(), vals.data_ptr(), C.byref(nk)))
         return keys[: nk.value], vals[: nk.value], nrows.value
 
     # -- readAndFilterPeakMatrix on the device (chicdiff.R:218-277) -------------------------------------
@@ -860,27 +995,21 @@ class HipContext:
         """The body of a peak matrix (the bytes after its header line) as a uint8 device tensor -> ``Peaks``; ``sep``: the separator
         (one character), ``score_cols``: the 0-based fields of the score columns, ascending, from 11 on.  The rule stands above
         chicdiff_hip_peaks_parse_dev in include/chicdiff_hip.h.  A malformed line raises, ``.offset`` its body offset."""
-        torch = self.torch
-        if d_text.dtype != torch.uint8 or d_text.dim() != 1:
-            raise ValueError("parse_peaks_text: d_text is a one-dimensional uint8 tensor")
-        d_text = d_text.contiguous()
-        if d_text.data_ptr() % 16:
-            d_text = d_text.clone()
+        d_text, pt = self._text(d_text)
         n = d_text.numel()
-        cols = np.ascontiguousarray(score_cols, dtype=np.int32)
+        cols, cp = self._host("score_cols", score_cols, np.int32, (-1,))
         ns = len(cols)
-        cp = cols.ctypes.data_as(C.POINTER(C.c_int32))
         sepb = ord(sep) if isinstance(sep, str) else int(sep)
         info = (C.c_int64 * len(PEAKS_INFO))()
         # first with no room at all: the call reports the row count before it writes anything
-        rc = self.lib.chicdiff_hip_peaks_parse_dev(self.h, d_text.data_ptr(), n, sepb, cp, ns, None, None, None, None, 0, info)
+        rc = self.lib.chicdiff_hip_peaks_parse_dev(self.h, pt, n, sepb, cp, ns, None, None, None, None, 0, info)
         if rc and info[0] == 0:
             self._check(rc)
         if info[1]:
             return Peaks(dict(zip(PEAKS_INFO, info)))
         ints, dist, scores, line_off = self._peaks_empty(info[0], ns)
         if info[0]:
-            rc = self.lib.chicdiff_hip_peaks_parse_dev(self.h, d_text.data_ptr(), n, sepb, cp, ns, ints.data_ptr(), dist.data_ptr(),
+            rc = self.lib.chicdiff_hip_peaks_parse_dev(self.h, pt, n, sepb, cp, ns, ints.data_ptr(), dist.data_ptr(),
                                                        scores.data_ptr(), line_off.data_ptr(), info[0], info)
             if rc:
                 err = ChicdiffHipError(f"[{rc}] " + self.lib.chicdiff_hip_last_error(self.h).decode())
@@ -937,14 +1066,22 @@ class HipContext:
             raise ValueError(f"merge_peaks: 2 .. {PEAKS_MERGE_MAX_FILES} files")
         if any(p.status or p.ints is None or p.chr_keys is None for p in peaks):
             raise ValueError("merge_peaks: every file comes from read_peaks(text_keys=True) with status 0")
-        keep = [(p.ints.contiguous(), p.dist.contiguous(), p.scores.contiguous(), p.chr_keys.contiguous(), p.name_hash.contiguous()) for p in peaks]
-        arr = lambda k: (C.c_void_p * F)(*[t[k].data_ptr() if t[k].numel() else None for t in keep])
+        keep, arrs = [], []          # the columns as the C ABI reads them, and per column the files' addresses (NULL for no rows)
+        for name, dtype in (("ints", torch.int32), ("dist", torch.float64), ("scores", torch.float64), ("chr_keys", torch.int64),
+                            ("name_hash", torch.int64)):
+            arr = (C.c_void_p * F)()
+            for f, p in enumerate(peaks):
+                shape = {"ints": (6, p.n), "dist": (p.n,), "scores": (p.nscore, p.n)}.get(name, (2, p.n))
+                t = _contiguous(getattr(p, name))                              # (a merged file's columns are views)
+                arr[f] = self._ptr(f"peaks[{f}].{name}", t, dtype, shape) or None
+                keep.append(t)
+            arrs.append(arr)
         nrows, nsc = (C.c_int64 * F)(*[p.n for p in peaks]), (C.c_int32 * F)(*[p.nscore for p in peaks])
         N, T = sum(p.n for p in peaks), sum(p.nscore for p in peaks)
         ints, dist, scores, _ = self._peaks_empty(N, T)
         src_file, src_row = torch.empty(N, dtype=torch.int32, device=self.device), torch.empty(N, dtype=torch.int64, device=self.device)
         info = (C.c_int64 * 2)()
-        self._check(self.lib.chicdiff_hip_peaks_merge_dev(self.h, F, arr(0), arr(1), arr(2), arr(3), arr(4), nrows, nsc, N, ints.data_ptr(),
+        self._check(self.lib.chicdiff_hip_peaks_merge_dev(self.h, F, *arrs, nrows, nsc, N, ints.data_ptr(),
                                                           dist.data_ptr(), scores.data_ptr(), src_file.data_ptr(), src_row.data_ptr(), info))
         n = info[0]
         d = dict(zip(PEAKS_INFO, [0] * len(PEAKS_INFO)))
@@ -971,37 +1108,44 @@ class HipContext:
         torch = self.torch
         n, ns = peaks.n, peaks.nscore
         cond = np.ascontiguousarray(cond_of_col, dtype=np.int32)
-        if len(cond) != ns:
+        if cond.shape != (ns,):
             raise ValueError("filter_peaks: one condition per score column")
         ncond = int(cond.max()) + 1 if ns else 0
+        if peaks.status or peaks.ints is None:
+            raise ValueError("filter_peaks: a Peaks with status 0, its columns held, is required")
+        bait, oe, dist, scores = (_contiguous(t) for t in (peaks.baitID, peaks.oeID, peaks.dist, peaks.scores))   # (views after a merge)
+        pb, po = self._ptr("peaks.baitID", bait, torch.int32, (n,)), self._ptr("peaks.oeID", oe, torch.int32, (n,))
+        pd, ps = self._ptr("peaks.dist", dist, torch.float64, (n,)), self._ptr("peaks.scores", scores, torch.float64, (ns, n))
         kept = torch.empty(n, dtype=torch.int64, device=self.device)
         kb, ko, fb = (torch.empty(n, dtype=torch.int32, device=self.device) for _ in range(3))
         nk, nf = C.c_int64(0), C.c_int64(0)
-        scores = peaks.scores.contiguous()
         self._check(self.lib.chicdiff_hip_peaks_filter_dev(
-            self.h, peaks.baitID.data_ptr(), peaks.oeID.data_ptr(), peaks.dist.data_ptr(), scores.data_ptr(), n, ns, float(score),
-            cond.ctypes.data_as(C.POINTER(C.c_int32)), ncond, int(bool(replicate_rule)), int(peaks.maxbait), kept.data_ptr(), kb.data_ptr(),
-            ko.data_ptr(), fb.data_ptr(), C.byref(nk), C.byref(nf)))
+            self.h, pb, po, pd, ps, n, ns, float(score), cond.ctypes.data_as(C.POINTER(C.c_int32)), ncond, int(bool(replicate_rule)),
+            int(peaks.maxbait), kept.data_ptr(), kb.data_ptr(), ko.data_ptr(), fb.data_ptr(), C.byref(nk), C.byref(nf)))
         return dict(kept_idx=kept[: nk.value], baitID=kb[: nk.value], oeID=ko[: nk.value], filtered_baits=fb[: nf.value])
 
     # -- a9: results() ---------------------------------------------------------------------------
     def cooks_filter(self, d_counts, group, d_maxCooks, d_cooksArgmax, d_pvalue, cutoff):
         """p <- NA for Cook's outliers, in place on ``d_pvalue``; returns the number of rows set to NA."""
+        torch = self.torch
+        dc = self._ptr("d_counts", d_counts, torch.int32, (-1, -1))
         S, n = d_counts.shape
-        g = (C.c_int32 * S)(*[int(x) for x in group])
+        g = self._group(group, S)
+        pmc, pam = self._ptr("d_maxCooks", d_maxCooks, torch.float64, (n,)), self._ptr("d_cooksArgmax", d_cooksArgmax, torch.int32, (n,))
+        pp = self._ptr("d_pvalue", d_pvalue, torch.float64, (n,))
         nout = C.c_int64(0)
-        self._check(self.lib.chicdiff_hip_cooks_filter_dev(self.h, d_counts.data_ptr(), n, S, g, d_maxCooks.data_ptr(),
-                                                           d_cooksArgmax.data_ptr(), float(cutoff), d_pvalue.data_ptr(), C.byref(nout)))
+        self._check(self.lib.chicdiff_hip_cooks_filter_dev(self.h, dc, n, S, g, pmc, pam, float(cutoff), pp, C.byref(nout)))
         return nout.value
 
     def independent_filtering(self, d_baseMean, d_pvalue, alpha=0.1):
         """DESeq2 pvalueAdjustment(independentFiltering = TRUE): returns (padj device tensor, info dict)."""
         torch = self.torch
+        pp = self._ptr("d_pvalue", d_pvalue, torch.float64, (-1,))
         n = d_pvalue.numel()
+        pm = self._ptr("d_baseMean", d_baseMean, torch.float64, (n,))
         padj = torch.empty(n, dtype=torch.float64, device=self.device)
         info = ResultsInfo()
-        self._check(self.lib.chicdiff_hip_independent_filtering_dev(self.h, d_baseMean.data_ptr(), d_pvalue.data_ptr(), n, float(alpha),
-                                                                    padj.data_ptr(), C.byref(info)))
+        self._check(self.lib.chicdiff_hip_independent_filtering_dev(self.h, pm, pp, n, float(alpha), padj.data_ptr(), C.byref(info)))
         return padj, dict(filterThreshold=info.filterThreshold, filterTheta=info.filterTheta, index=info.index,
                           theta=np.array(info.theta[:]), numRej=np.array(info.numRej[:]), lowess=np.array(info.lowess[:]))
 
@@ -1009,33 +1153,31 @@ class HipContext:
     def bh_adjust(self, d_p):
         """p.adjust(p, "BH") on a device vector (NaN = NA)."""
         torch = self.torch
-        assert d_p.dtype == torch.float64 and d_p.is_contiguous()
+        pp = self._ptr("d_p", d_p, torch.float64, (-1,))
         out = torch.empty_like(d_p)
-        self._check(self.lib.chicdiff_hip_bh_adjust_dev(self.h, d_p.data_ptr(), d_p.numel(), out.data_ptr()))
+        self._check(self.lib.chicdiff_hip_bh_adjust_dev(self.h, pp, d_p.numel(), out.data_ptr()))
         return out
 
     def ihw_apply(self, d_avDist, d_pvalue, breaks, avWeights):
         """chicdiff.R:2038-2049: returns dict(group, weight, weighted_pvalue, weighted_padj) of device tensors."""
         torch = self.torch
+        pa = self._ptr("d_avDist", d_avDist, torch.float64, (-1,))
         n = d_avDist.numel()
-        b = np.ascontiguousarray(breaks, dtype=np.float64)
-        w = np.ascontiguousarray(avWeights, dtype=np.float64)
-        assert len(b) == len(w) + 1 and d_pvalue.numel() == n
+        pp = self._ptr("d_pvalue", d_pvalue, torch.float64, (n,))
+        w, pw = self._host("avWeights", avWeights, np.float64, (-1,))
+        b, pb = self._host("breaks", breaks, np.float64, (len(w) + 1,))
         group = torch.empty(n, dtype=torch.int32, device=self.device)
         weight, wp, wpadj = (torch.empty(n, dtype=torch.float64, device=self.device) for _ in range(3))
-        P = C.POINTER(C.c_double)
-        self._check(self.lib.chicdiff_hip_ihw_apply_dev(self.h, d_avDist.data_ptr(), d_pvalue.data_ptr(), n, b.ctypes.data_as(P),
-                                                        w.ctypes.data_as(P), len(w), group.data_ptr(), weight.data_ptr(),
+        self._check(self.lib.chicdiff_hip_ihw_apply_dev(self.h, pa, pp, n, pb, pw, len(w), group.data_ptr(), weight.data_ptr(),
                                                         wp.data_ptr(), wpadj.data_ptr()))
         return dict(group=group, weight=weight, weighted_pvalue=wp, weighted_padj=wpadj)
 
     def _ihw_args(self, d_pvalue, d_covariate, nbins, nfolds, seed, chunk_len):
         torch = self.torch
-        self._check_tensor("d_pvalue", d_pvalue, torch.float64, (-1,))
-        self._check_tensor("d_covariate", d_covariate, torch.float64, (d_pvalue.numel(),))
-        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
-            raise ValueError(f"ihw_train: seed must be an integer in [0, 2^64), got {seed!r}")
-        return d_pvalue.numel(), 0 if nbins is None else int(nbins), int(nfolds), int(seed), 0 if chunk_len is None else int(chunk_len)
+        pp = self._ptr("d_pvalue", d_pvalue, torch.float64, (-1,))
+        pc = self._ptr("d_covariate", d_covariate, torch.float64, (d_pvalue.numel(),))
+        sd = self._seed("ihw_train", seed)
+        return pp, pc, d_pvalue.numel(), 0 if nbins is None else int(nbins), int(nfolds), sd, 0 if chunk_len is None else int(chunk_len)
 
     def ihw_train(self, d_pvalue, d_covariate, alpha=0.05, nbins=None, nfolds=5, seed=0, chunk_len=None):
         """The training side of IHWcorrection, ihw(pvalue ~ covariate, alpha) of chicdiff.R:1994, by this library's own statement of
@@ -1046,12 +1188,12 @@ class HipContext:
         Returns dict(group, fold: int32 device tensors (INT32_MIN / -1 on left-out rows), weights: (nbins, nfolds) numpy array,
         m, nbins, nseg, T, H: the info block)."""
         torch = self.torch
-        n, nb, nf, sd, cl = self._ihw_args(d_pvalue, d_covariate, nbins, nfolds, seed, chunk_len)
+        pp, pc, n, nb, nf, sd, cl = self._ihw_args(d_pvalue, d_covariate, nbins, nfolds, seed, chunk_len)
         group, fold = (torch.empty(max(n, 1), dtype=torch.int32, device=self.device) for _ in range(2))
         w = np.zeros(IHW_MAX_FOLDS * 256, dtype=np.float64)
         info = IhwInfo()
         info.chunk_len = cl
-        self._check(self.lib.chicdiff_hip_ihw_train_dev(self.h, d_pvalue.data_ptr(), d_covariate.data_ptr(), n, float(alpha), nb, nf, sd,
+        self._check(self.lib.chicdiff_hip_ihw_train_dev(self.h, pp, pc, n, float(alpha), nb, nf, sd,
                                                         group.data_ptr(), fold.data_ptr(), w.ctypes.data, C.byref(info)))
         self.last_ihw_train_ms = {k: v[0] for k, v in self.kernel_times().items() if k.startswith("ihw_")}
         k = info.nbins
@@ -1061,9 +1203,9 @@ class HipContext:
     def selftest_ihw_knots(self, d_pvalue, d_covariate, nbins=None, nfolds=5, seed=0, chunk_len=None):
         """The knots of every (fold, group) as the device finds them (chicdiff_hip_selftest_ihw_knots_dev): dict(ptr, x, c, nbins),
         entry f * nbins + (g - 1) owning x, c [ptr[q] .. ptr[q + 1])."""
-        n, nb, nf, sd, cl = self._ihw_args(d_pvalue, d_covariate, nbins, nfolds, seed, chunk_len)
+        pp, pc, n, nb, nf, sd, cl = self._ihw_args(d_pvalue, d_covariate, nbins, nfolds, seed, chunk_len)
         k, nk = C.c_int32(0), C.c_int64(0)
-        args = (self.h, d_pvalue.data_ptr(), d_covariate.data_ptr(), n, nb, nf, sd, cl)
+        args = (self.h, pp, pc, n, nb, nf, sd, cl)
         self._check(self.lib.chicdiff_hip_selftest_ihw_knots_dev(*args, 0, None, None, None, C.byref(k), C.byref(nk)))
         ptr = np.zeros(nf * k.value + 1, dtype=np.int64)
         x, c = np.zeros(nk.value, dtype=np.float64), np.zeros(nk.value, dtype=np.int32)
@@ -1077,16 +1219,19 @@ class HipContext:
         Returns dict(region_ptr, minOE, maxOE, baitID, regionID, otherEndID); the RU rows are in
         (regionID, otherEndID) order."""
         torch = self.torch
+        pb = self._ptr("d_bait", d_bait, torch.int32, (-1,))
         n = d_bait.numel()
+        po = self._ptr("d_oe", d_oe, torch.int32, (n,))
+        pc = self._ptr("d_chr_of", d_chr_of, torch.int32, (-1,))
         maxfrag = d_chr_of.numel() - 1
         ptr = torch.empty(n + 1, dtype=torch.int64, device=self.device)
         mn, mx = (torch.empty(n, dtype=torch.int32, device=self.device) for _ in range(2))
         total = C.c_int64(0)
         cap = n * max(2 * int(RUexpand) + 1, 2)   # the upper bound (two for RUexpand = 0: R's descending a:b beside a bait): scan and fill in one call (round 5)
         rb, rr, ro = (torch.empty(max(cap, 1), dtype=torch.int32, device=self.device) for _ in range(3))
-        self._check(self.lib.chicdiff_hip_region_universe_dev(self.h, d_bait.data_ptr(), d_oe.data_ptr(), n, int(RUexpand), d_chr_of.data_ptr(),
-                                                              maxfrag, ptr.data_ptr(), mn.data_ptr(), mx.data_ptr(), rb.data_ptr(), rr.data_ptr(),
-                                                              ro.data_ptr(), cap, C.byref(total)))
+        self._check(self.lib.chicdiff_hip_region_universe_dev(
+            self.h, pb, po, n, int(RUexpand), pc, maxfrag, ptr.data_ptr(), mn.data_ptr(), mx.data_ptr(), rb.data_ptr(), rr.data_ptr(),
+            ro.data_ptr(), cap, C.byref(total)))
         self.last_region_universe_ms = self.kernel_times().get("region_universe", (0.0, 0))[0]
         rb, rr, ro = rb[: total.value], rr[: total.value], ro[: total.value]
         if 2 * total.value < cap:  # (a view would pin the whole upper-bound allocation for as long as the universe lives)
@@ -1113,27 +1258,28 @@ class HipContext:
             if method not in CAND_METHODS:
                 raise ValueError(f"candidate_interactions: unknown method {method!r} (should be 'min' or 'hmp')")
             method = CAND_METHODS[method]
-        n, (ncols, npeaks) = d_baitID.numel(), d_scores.shape
-        for t in (d_baitID, d_minOE, d_maxOE, d_peak_baitID, d_peak_oeID):
-            assert t.dtype == torch.int32 and t.is_contiguous()
-        assert d_p.dtype == torch.float64 and d_scores.dtype == torch.float64 and d_p.is_contiguous() and d_scores.is_contiguous()
-        assert d_minOE.numel() == n and d_maxOE.numel() == n and d_p.numel() == n
-        assert d_peak_baitID.numel() == npeaks and d_peak_oeID.numel() == npeaks
+        pb = self._ptr("d_baitID", d_baitID, torch.int32, (-1,))
+        n = d_baitID.numel()
+        pmn, pmx = self._ptr("d_minOE", d_minOE, torch.int32, (n,)), self._ptr("d_maxOE", d_maxOE, torch.int32, (n,))
+        pp = self._ptr("d_p", d_p, torch.float64, (n,))
+        ps = self._ptr("d_scores", d_scores, torch.float64, (-1, -1))
+        ncols, npeaks = d_scores.shape
+        ppb = self._ptr("d_peak_baitID", d_peak_baitID, torch.int32, (npeaks,))
+        ppo = self._ptr("d_peak_oeID", d_peak_oeID, torch.int32, (npeaks,))
         gpeak = torch.empty(max(npeaks, 1), dtype=torch.int32, device=self.device)
         gptr = torch.empty(npeaks + 1, dtype=torch.int64, device=self.device)
         gmin, gdelta = (torch.empty(max(npeaks, 1), dtype=torch.float64, device=self.device) for _ in range(2))
         ng, npairs = C.c_int64(0), C.c_int64(0)
 
         def call(pairs):
+            ppairs = self._ptr("pair_row", pairs, torch.int32, (-1,))
             return self.lib.chicdiff_hip_candidate_interactions_method_dev(
-                self.h, d_baitID.data_ptr(), d_minOE.data_ptr(), d_maxOE.data_ptr(), d_p.data_ptr(), n, d_peak_baitID.data_ptr(),
-                d_peak_oeID.data_ptr(), d_scores.data_ptr(), npeaks, ncols, int(ncond1), int(ncond2), int(bool(merged)), float(score),
+                self.h, pb, pmn, pmx, pp, n, ppb, ppo, ps, npeaks, ncols, int(ncond1), int(ncond2), int(bool(merged)), float(score),
                 float(pvcut), float(minDeltaAsinhScore), int(method), pairs.numel(), gpeak.data_ptr(), gptr.data_ptr(), gmin.data_ptr(),
-                gdelta.data_ptr(), pairs.data_ptr(), C.byref(ng), C.byref(npairs))
+                gdelta.data_ptr(), ppairs, C.byref(ng), C.byref(npairs))
 
         own = pair_row is None
         pairs = torch.empty(max(16 * npeaks, 1), dtype=torch.int32, device=self.device) if own else pair_row
-        assert pairs.dtype == torch.int32 and pairs.is_contiguous()
         rc = call(pairs)
         if rc and npairs.value > pairs.numel():          # the capacity status: both counts are written, no pair is
             if not own:
@@ -1162,30 +1308,27 @@ class HipContext:
         Returns dict(baitID, oeID, max_contact, n_regions, m): the m kept pairs sorted by (baitID, oeID) as int32 device tensors,
         the largest contact per chromosome code (int32 device tensor, 0 = none) and the number of non-empty regions of RU."""
         torch = self.torch
-        self._check_tensor("d_ru_baitID", d_ru_baitID, torch.int32, (-1,))
-        self._check_tensor("d_region_ptr", d_region_ptr, torch.int64, (-1,))
+        pru = self._ptr("d_ru_baitID", d_ru_baitID, torch.int32, (-1,))
+        ptr = self._ptr("d_region_ptr", d_region_ptr, torch.int64, (-1,))
         n = d_region_ptr.numel() - 1
         if n < 1:
             raise ValueError("control_draws: region_ptr must hold at least one region (two entries)")
-        self._check_tensor("d_minOE", d_minOE, torch.int32, (n,))
-        self._check_tensor("d_maxOE", d_maxOE, torch.int32, (n,))
-        self._check_tensor("d_bmap_id", d_bmap_id, torch.int32, (-1,))
+        pmn, pmx = self._ptr("d_minOE", d_minOE, torch.int32, (n,)), self._ptr("d_maxOE", d_maxOE, torch.int32, (n,))
+        pbi = self._ptr("d_bmap_id", d_bmap_id, torch.int32, (-1,))
         nb = d_bmap_id.numel()
         if nb < 1:
             raise ValueError("control_draws: the baitmap is empty (nb = 0)")
-        self._check_tensor("d_bmap_chr", d_bmap_chr, torch.int32, (nb,))
+        pbc = self._ptr("d_bmap_chr", d_bmap_chr, torch.int32, (nb,))
         lo, hi = (np.ascontiguousarray(a, dtype=np.int32) for a in (chr_min, chr_max))
         if lo.ndim != 1 or lo.shape != hi.shape or len(lo) < 1:
             raise ValueError(f"chr_min, chr_max: two vectors of one length >= 1 are required, got shapes {lo.shape} and {hi.shape}")
-        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
-            raise ValueError(f"control_draws: seed must be an integer in [0, 2^64), got {seed!r}")
+        seed = self._seed("control_draws", seed)
         bait, oe = (torch.empty(n, dtype=torch.int32, device=self.device) for _ in range(2))
         contact = torch.empty(len(lo), dtype=torch.int32, device=self.device)
         n_regions, m = C.c_int64(0), C.c_int64(0)
         P = C.POINTER(C.c_int32)
         self._check(self.lib.chicdiff_hip_control_draws_dev(
-            self.h, d_ru_baitID.data_ptr(), d_ru_baitID.numel(), d_region_ptr.data_ptr(), d_minOE.data_ptr(), d_maxOE.data_ptr(), n,
-            d_bmap_id.data_ptr(), d_bmap_chr.data_ptr(), nb, lo.ctypes.data_as(P), hi.ctypes.data_as(P), len(lo), int(seed),
+            self.h, pru, d_ru_baitID.numel(), ptr, pmn, pmx, n, pbi, pbc, nb, lo.ctypes.data_as(P), hi.ctypes.data_as(P), len(lo), seed,
             bait.data_ptr(), oe.data_ptr(), contact.data_ptr(), C.byref(n_regions), C.byref(m)))
         self.last_control_draws_ms = self.kernel_times().get("control_draws", (0.0, 0))[0]
         k = m.value
@@ -1204,23 +1347,20 @@ class HipContext:
         none), and whether some code carries two different values — ``ref`` is then not the distance function's input, and the
         caller builds that replicate's on the host."""
         torch = self.torch
-        self._check_tensor("d_bait", d_bait, torch.int32, (-1,))
+        pb = self._ptr("d_bait", d_bait, torch.int32, (-1,))
         n = d_bait.numel()
         if not 1 <= n < 1 << 32:
             raise ValueError(f"chicago_tables: 1 <= nrows < 2^32 rows are supported, got {n}")
-        self._check_tensor("d_oe", d_oe, torch.int32, (n,))
-        for name, t in (("d_s_j", d_s_j), ("d_s_i", d_s_i), ("d_Tmean", d_Tmean), ("d_refBinMean", d_refBinMean)):
-            self._check_tensor(name, t, torch.float64, (n,))
-        for name, t in (("d_tblb", d_tblb), ("d_tlb", d_tlb), ("d_distbin", d_distbin)):
-            self._check_tensor(name, t, torch.int32, (n,))
-        self._check_tensor("sj", sj, torch.float64, (-1,))
+        cols = [pb, self._ptr("d_oe", d_oe, torch.int32, (n,))]
+        cols += [self._ptr(name, t, torch.float64, (n,))
+                 for name, t in (("d_s_j", d_s_j), ("d_s_i", d_s_i), ("d_Tmean", d_Tmean), ("d_refBinMean", d_refBinMean))]
+        cols += [self._ptr(name, t, torch.int32, (n,)) for name, t in (("d_tblb", d_tblb), ("d_tlb", d_tlb), ("d_distbin", d_distbin))]
+        psj = self._ptr("sj", sj, torch.float64, (-1,))
         nid = sj.numel()
         if nid < 1:
             raise ValueError("sj: empty restriction map")
-        self._check_tensor("si", si, torch.float64, (nid,))
-        self._check_tensor("tblb_of", tblb_of, torch.int32, (nid,))
-        self._check_tensor("tlb_of", tlb_of, torch.int32, (nid,))
-        self._check_tensor("T", T, torch.float64, (-1, -1))
+        outs = [psj, self._ptr("si", si, torch.float64, (nid,)), self._ptr("tblb_of", tblb_of, torch.int32, (nid,)),
+                self._ptr("tlb_of", tlb_of, torch.int32, (nid,)), self._ptr("T", T, torch.float64, (-1, -1))]
         caps = chicago_tables_caps()
         if T.shape[0] < 1 or T.shape[1] < 1 or T.numel() > caps["max_pairs"]:
             raise ValueError(f"T: shape (ntblb >= 1, ntlb >= 1) with at most {caps['max_pairs']} cells is required, got {tuple(T.shape)}")
@@ -1229,12 +1369,10 @@ class HipContext:
             raise ValueError(f"chicago_tables: 0 <= ndistbin <= {caps['max_distbin']} is required, got {ndistbin}")
         if ref is None:
             ref = torch.empty(ndistbin + 1, dtype=torch.float64, device=self.device)
-        self._check_tensor("ref", ref, torch.float64, (ndistbin + 1,))
+        outs.append(self._ptr("ref", ref, torch.float64, (ndistbin + 1,)))
         flag = C.c_int32(0)
-        self._check(self.lib.chicdiff_hip_chicago_tables_dev(
-            self.h, d_bait.data_ptr(), d_oe.data_ptr(), d_s_j.data_ptr(), d_s_i.data_ptr(), d_Tmean.data_ptr(), d_refBinMean.data_ptr(),
-            d_tblb.data_ptr(), d_tlb.data_ptr(), d_distbin.data_ptr(), n, int(id_min), nid, T.shape[0], T.shape[1], ndistbin,
-            sj.data_ptr(), si.data_ptr(), tblb_of.data_ptr(), tlb_of.data_ptr(), T.data_ptr(), ref.data_ptr(), C.byref(flag)))
+        self._check(self.lib.chicdiff_hip_chicago_tables_dev(self.h, *cols, n, int(id_min), nid, T.shape[0], T.shape[1], ndistbin, *outs,
+                                                             C.byref(flag)))
         kt = self.kernel_times()
         self.last_chicago_tables_ms = {k[len("chicago_tables_"):]: v[0] for k, v in kt.items() if k.startswith("chicago_tables_")}
         return ref, bool(flag.value)
@@ -1255,28 +1393,28 @@ class HipContext:
             raise ValueError(f"countput: 1 <= replicates <= {caps['max_rep']} are supported, got {len(reps)}")
         dtypes = (torch.int32, torch.int32, torch.int32, torch.float64, torch.float64, torch.float64)
         names = ("baitID", "otherEndID", "N", "Bmean", "score", "distSign")
+        nrep = len(reps)
+        ptrs = [(C.c_void_p * nrep)() for _ in range(6)]
         for r, cols in enumerate(reps):
             if len(cols) != 6:
                 raise ValueError(f"countput: replicate {r} must be (baitID, otherEndID, N, Bmean, score, distSign), got {len(cols)} columns")
-            self._check_tensor(f"reps[{r}].baitID", cols[0], torch.int32, (-1,))
-            for name, t, dt in zip(names[1:], cols[1:], dtypes[1:]):
-                self._check_tensor(f"reps[{r}].{name}", t, dt, (cols[0].numel(),))
-        self._check_tensor("d_midsum", d_midsum, torch.int64, (-1,))
+            ptrs[0][r] = self._ptr(f"reps[{r}].baitID", cols[0], torch.int32, (-1,)) or None
+            for k in range(1, 6):
+                ptrs[k][r] = self._ptr(f"reps[{r}].{names[k]}", cols[k], dtypes[k], (cols[0].numel(),)) or None
+        pm = self._ptr("d_midsum", d_midsum, torch.int64, (-1,))
         nid = d_midsum.numel()
         if nid < 1:
             raise ValueError("d_midsum: empty restriction map")
-        self._check_tensor("d_chr", d_chr, torch.int32, (nid,))
-        nrep = len(reps)
+        pc = self._ptr("d_chr", d_chr, torch.int32, (nid,))
         n = sum(cols[0].numel() for cols in reps)
         if n >= 1 << 31:
             raise ValueError(f"countput: the replicates of one condition must hold fewer than 2^31 rows together, got {n}")
-        ptrs = [(C.c_void_p * nrep)(*[cols[k].data_ptr() if cols[k].numel() else None for cols in reps]) for k in range(6)]
         nrows = (C.c_int64 * nrep)(*[cols[0].numel() for cols in reps])
         ob, oo = (torch.empty(n, dtype=torch.int32, device=self.device) for _ in range(2))
         nav, bav, sc, mid = (torch.empty(n, dtype=torch.float64, device=self.device) for _ in range(4))
         g = C.c_int64(0)
         self._check(self.lib.chicdiff_hip_countput_dev(
-            self.h, nrep, *ptrs, nrows, int(id_min), nid, d_midsum.data_ptr(), d_chr.data_ptr(), ob.data_ptr(), oo.data_ptr(),
+            self.h, nrep, *ptrs, nrows, int(id_min), nid, pm, pc, ob.data_ptr(), oo.data_ptr(),
             nav.data_ptr(), bav.data_ptr(), sc.data_ptr(), mid.data_ptr(), C.byref(g)))
         self.last_countput_ms = self.kernel_times().get("countput", (0.0, 0))[0]
         k = g.value
@@ -1320,11 +1458,11 @@ class HipContext:
     def selftest_format_double_dev(self, d_x):
         """The library's double -> text function on the device (chicdiff_hip_selftest_format_double_dev): the cells as a list of bytes."""
         torch = self.torch
-        self._check_tensor("d_x", d_x, torch.float64, (-1,))
+        px = self._ptr("d_x", d_x, torch.float64, (-1,))
         n = d_x.numel()
         text = torch.empty((n, TABLE_MAX_CELL_BYTES), dtype=torch.uint8, device=self.device)
         length = torch.empty(n, dtype=torch.int32, device=self.device)
-        self._check(self.lib.chicdiff_hip_selftest_format_double_dev(self.h, d_x.data_ptr(), n, text.data_ptr(), length.data_ptr()))
+        self._check(self.lib.chicdiff_hip_selftest_format_double_dev(self.h, px, n, text.data_ptr(), length.data_ptr()))
         return _format_double_cells(text.cpu().numpy(), length.cpu().numpy())
 
     # -- a6 + a7 ----------------------------------------------------------------------------
@@ -1333,43 +1471,23 @@ class HipContext:
 
         Returns (outputs, scalars): ``outputs`` maps the requested column names to device
         tensors of length n (pass ``outputs`` to reuse buffers)."""
-        torch = self.torch
-        S, n = d_counts.shape
-        assert d_nf.shape == (S, n) and d_counts.dtype == torch.int32 and d_nf.dtype == torch.float64
-        assert d_counts.is_contiguous() and d_nf.is_contiguous()
-        want = list(want) if want is not None else ["baseMean", "dispersion", "log2FoldChange", "lfcSE", "stat", "pvalue"]
-        out = Out()
-        bufs = outputs if outputs is not None else {}
-        for k in want:
-            if k not in bufs:
-                bufs[k] = torch.empty(n, dtype=torch.float64 if k in OUT_DOUBLE else torch.int32, device=self.device)
-            setattr(out, k, bufs[k].data_ptr())
-        g = (C.c_int32 * S)(*[int(x) for x in group])
+        pk, pnf, S, n = self._matrices("d_nf", d_counts, d_nf)
+        g, o = self._group(group, S), self._opts(opts)
+        out, bufs = self._outputs(want, FIT_COLUMNS, n, outputs)
         sc = Scalars()
-        self._check(self.lib.chicdiff_hip_nbglm_fit_dev(self.h, d_counts.data_ptr(), d_nf.data_ptr(), n, S, g,
-                                                        C.byref(opts) if opts is not None else None, C.byref(out),
-                                                        C.byref(sc)))
+        self._check(self.lib.chicdiff_hip_nbglm_fit_dev(self.h, pk, pnf, n, S, g, o, C.byref(out), C.byref(sc)))
         return bufs, _scalars_dict(sc)
 
     def wald_test(self, d_counts, d_fullmean, group, theta=None, want=None, opts: Opts | None = None,
                   outputs: dict | None = None):
         """size factors -> offsets(theta) -> dispersions -> Wald test in one enqueue (device-resident)."""
-        torch = self.torch
-        S, n = d_counts.shape
-        assert d_fullmean.shape == (S, n) and d_counts.is_contiguous() and d_fullmean.is_contiguous()
-        want = list(want) if want is not None else ["baseMean", "dispersion", "log2FoldChange", "lfcSE", "stat", "pvalue"]
-        out = Out()
-        bufs = outputs if outputs is not None else {}
-        for k in want:
-            if k not in bufs:
-                bufs[k] = torch.empty(n, dtype=torch.float64 if k in OUT_DOUBLE else torch.int32, device=self.device)
-            setattr(out, k, bufs[k].data_ptr())
-        g = (C.c_int32 * S)(*[int(x) for x in group])
+        pk, pfm, S, n = self._matrices("d_fullmean", d_counts, d_fullmean)
+        g, o = self._group(group, S), self._opts(opts)
+        out, bufs = self._outputs(want, FIT_COLUMNS, n, outputs)
         sc = Scalars()
         sf = (C.c_double * S)()
-        self._check(self.lib.chicdiff_hip_wald_test_dev(
-            self.h, d_counts.data_ptr(), d_fullmean.data_ptr(), n, S, g, float("nan") if theta is None else float(theta),
-            C.byref(opts) if opts is not None else None, C.byref(out), C.byref(sc), sf))
+        self._check(self.lib.chicdiff_hip_wald_test_dev(self.h, pk, pfm, n, S, g, float("nan") if theta is None else float(theta), o,
+                                                        C.byref(out), C.byref(sc), sf))
         res = _scalars_dict(sc)
         res["sizeFactors"] = np.array(sf[:])
         return bufs, res
@@ -1378,61 +1496,60 @@ class HipContext:
         """Host-buffer entry point (what the R .Call shim uses): numpy (n, S) in, numpy out."""
         k = np.asfortranarray(np.asarray(counts, dtype=np.int32))
         f = np.asfortranarray(np.asarray(nf, dtype=np.float64))
+        if k.ndim != 2 or f.shape != k.shape:
+            raise ValueError(f"counts, nf: two (n, S) matrices of one shape are required, got shapes {k.shape} and {f.shape}")
         n, S = k.shape
-        want = list(want) if want is not None else OUT_DOUBLE + OUT_INT
-        out = Out()
-        res = {}
-        for name in want:
-            res[name] = np.empty(n, dtype=np.float64 if name in OUT_DOUBLE else np.int32)
-            setattr(out, name, res[name].ctypes.data)
-        g = (C.c_int32 * S)(*[int(x) for x in group])
+        g, o = self._group(group, S), self._opts(opts)
+        out, res = self._outputs(want, OUT_DOUBLE + OUT_INT, n, host=True)
         sc = Scalars()
-        self._check(self.lib.chicdiff_hip_nbglm_fit(self.h, k.ctypes.data, f.ctypes.data, n, S, g,
-                                                    C.byref(opts) if opts is not None else None, C.byref(out), C.byref(sc)))
+        self._check(self.lib.chicdiff_hip_nbglm_fit(self.h, k.ctypes.data, f.ctypes.data, n, S, g, o, C.byref(out), C.byref(sc)))
         return res, _scalars_dict(sc)
 
     # -- a8 ---------------------------------------------------------------------------------
     def theta_grid(self, d_counts, d_fullmean, size_factors, thetas, opts: Opts | None = None) -> np.ndarray:
-        S, n = d_counts.shape
-        sf = (C.c_double * S)(*[float(x) for x in size_factors])
-        th = (C.c_double * len(thetas))(*[float(x) for x in thetas])
-        dev = (C.c_double * len(thetas))()
-        self._check(self.lib.chicdiff_hip_theta_grid_dev(self.h, d_counts.data_ptr(), d_fullmean.data_ptr(), sf, n, S, th,
-                                                         len(thetas), C.byref(opts) if opts is not None else None, dev))
+        pk, pfm, S, n = self._matrices("d_fullmean", d_counts, d_fullmean)
+        sf, psf = self._host("size_factors", size_factors, np.float64, (S,))
+        th, pth = self._host("thetas", thetas, np.float64, (-1,))
+        o = self._opts(opts)
+        dev = (C.c_double * len(th))()
+        self._check(self.lib.chicdiff_hip_theta_grid_dev(self.h, pk, pfm, psf, n, S, pth, len(th), o, dev))
         return np.array(dev[:])
 
     def selftest_math(self, op: int, d_x):
+        px = self._ptr("d_x", d_x, self.torch.float64)
         out = self.torch.empty_like(d_x)
-        self._check(self.lib.chicdiff_hip_selftest_math_dev(self.h, op, d_x.data_ptr(), d_x.numel(), out.data_ptr()))
+        self._check(self.lib.chicdiff_hip_selftest_math_dev(self.h, op, px, d_x.numel(), out.data_ptr()))
         return out
 
     def selftest_landau(self, d_z):
         """landau_tail(z) (devmath.h), the Landau tail behind method = "hmp", as the overlap kernel calls it."""
-        assert d_z.dtype == self.torch.float64 and d_z.is_contiguous()
+        pz = self._ptr("d_z", d_z, self.torch.float64)
         out = self.torch.empty_like(d_z)
-        self._check(self.lib.chicdiff_hip_selftest_landau_dev(self.h, d_z.data_ptr(), d_z.numel(), out.data_ptr()))
+        self._check(self.lib.chicdiff_hip_selftest_landau_dev(self.h, pz, d_z.numel(), out.data_ptr()))
         return out
 
     def selftest_math3(self, op: int, d_x, d_y):
         """Two-argument / two-result building blocks (include/chicdiff_hip.h: the op numbers) -> (out, out2)."""
+        px = self._ptr("d_x", d_x, self.torch.float64)
+        py = self._ptr("d_y", d_y, self.torch.float64, tuple(d_x.shape))
         out, out2 = self.torch.empty_like(d_x), self.torch.empty_like(d_x)
-        self._check(self.lib.chicdiff_hip_selftest_math3_dev(self.h, op, d_x.data_ptr(), d_y.data_ptr(), d_x.numel(), out.data_ptr(),
-                                                             out2.data_ptr()))
+        self._check(self.lib.chicdiff_hip_selftest_math3_dev(self.h, op, px, py, d_x.numel(), out.data_ptr(), out2.data_ptr()))
         return out, out2
 
     def selftest_objective(self, d_counts, d_nf, group, d_log_alpha, d_prior_mean=None, prior_var=1.0, live_rows=0,
                            opts: Opts | None = None):
         """The dispersion objective at d_log_alpha (n, K): dict of lp, dlp, alpha (n, K), mu (S, n) and lanes_per_row."""
-        S, n = d_counts.shape
-        K = d_log_alpha.shape[1]
         t = self.torch
+        pk, pnf, S, n = self._matrices("d_nf", d_counts, d_nf)
+        pla = self._ptr("d_log_alpha", d_log_alpha, t.float64, (n, -1))
+        K = d_log_alpha.shape[1]
+        ppm = self._ptr_or_none("d_prior_mean", d_prior_mean, t.float64, (n,))
+        g, o = self._group(group, S), self._opts(opts)
         lp, dlp, alpha = (t.empty((n, K), dtype=t.float64, device=self.device) for _ in range(3))
         mu = t.empty((S, n), dtype=t.float64, device=self.device)
-        g = (C.c_int32 * S)(*[int(x) for x in group])
         lanes = C.c_int32(0)
         self._check(self.lib.chicdiff_hip_selftest_objective_dev(
-            self.h, d_counts.data_ptr(), d_nf.data_ptr(), n, S, g, C.byref(opts) if opts is not None else None,
-            d_log_alpha.data_ptr(), K, d_prior_mean.data_ptr() if d_prior_mean is not None else None, float(prior_var),
+            self.h, pk, pnf, n, S, g, o, pla, K, ppm, float(prior_var),
             int(live_rows), lp.data_ptr(), dlp.data_ptr(), alpha.data_ptr(), mu.data_ptr(), C.byref(lanes)))
         return dict(lp=lp, dlp=dlp, alpha=alpha, mu=mu, lanes_per_row=lanes.value)
 
@@ -1441,18 +1558,18 @@ class HipContext:
         dispFit, resid (device tensors, n), hist (40 counts), vertices (dict of nv and x, h, f, d: the local trend's, ascending x)
         and the scalars with their status bits."""
         t = self.torch
+        pbm = self._ptr("d_baseMean", d_baseMean, t.float64, (-1,))
         n = d_baseMean.numel()
-        self._check_tensor("d_baseMean", d_baseMean, t.float64, (n,))
-        self._check_tensor("d_dispGeneEst", d_dispGeneEst, t.float64, (n,))
-        self._check_tensor("d_allZero", d_allZero, t.int32, (n,))
+        pdg = self._ptr("d_dispGeneEst", d_dispGeneEst, t.float64, (n,))
+        paz = self._ptr("d_allZero", d_allZero, t.int32, (n,))
+        o = self._opts(opts)
         fit, resid = (t.empty(n, dtype=t.float64, device=self.device) for _ in range(2))
         hist = (C.c_double * 40)()
         nv = C.c_int32(0)
         vx, vh, vf, vd = ((C.c_double * 100)() for _ in range(4))
         sc = Scalars()
         self._check(self.lib.chicdiff_hip_selftest_global_stage_dev(
-            self.h, d_baseMean.data_ptr(), d_dispGeneEst.data_ptr(), d_allZero.data_ptr(), n, int(S), int(p),
-            C.byref(opts) if opts is not None else None, fit.data_ptr(), resid.data_ptr(), hist, C.byref(nv), vx, vh, vf, vd, C.byref(sc)))
+            self.h, pbm, pdg, paz, n, int(S), int(p), o, fit.data_ptr(), resid.data_ptr(), hist, C.byref(nv), vx, vh, vf, vd, C.byref(sc)))
         k = nv.value
         return dict(dispFit=fit, resid=resid, hist=np.array(hist[:]),
                     vertices=dict(nv=k, x=np.array(vx[:k]), h=np.array(vh[:k]), f=np.array(vf[:k]), d=np.array(vd[:k])),
@@ -1460,12 +1577,13 @@ class HipContext:
 
     def selftest_resid_hist(self, d_resid) -> np.ndarray:
         """TEST ENTRY: the 40 counts of hist(x[x > -10 & x < 10], breaks = -20:20/2) over a device column, by the fit's kernel."""
-        self._check_tensor("d_resid", d_resid, self.torch.float64, (d_resid.numel(),))
+        pr = self._ptr("d_resid", d_resid, self.torch.float64, (-1,))
         hist = (C.c_double * 40)()
-        self._check(self.lib.chicdiff_hip_selftest_resid_hist_dev(self.h, d_resid.data_ptr(), d_resid.numel(), hist))
+        self._check(self.lib.chicdiff_hip_selftest_resid_hist_dev(self.h, pr, d_resid.numel(), hist))
         return np.array(hist[:])
 
     def wald_pvalues(self, d_stat):
+        ps = self._ptr("d_stat", d_stat, self.torch.float64)
         out = self.torch.empty_like(d_stat)
-        self._check(self.lib.chicdiff_hip_wald_pvalues_dev(self.h, d_stat.data_ptr(), d_stat.numel(), out.data_ptr()))
+        self._check(self.lib.chicdiff_hip_wald_pvalues_dev(self.h, ps, d_stat.numel(), out.data_ptr()))
         return out

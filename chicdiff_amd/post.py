@@ -89,7 +89,8 @@ def getFullRegionDataHip(ctx, RU, chinput_files, condition, background):
     (what .hipBackgroundTables builds in R from ``x@x`` and ``.chicEstimateDistFun``)."""
     torch = ctx.torch
     S = len(chinput_files)
-    assert len(condition) == S
+    if len(condition) != S:
+        raise ValueError(f"condition: one label per chinput file ({S}) is required, got {len(condition)}")
     bait = np.asarray(RU["baitID"], dtype=np.int32)
     region = np.asarray(RU["regionID"], dtype=np.int64)
     oe = np.asarray(RU["otherEndID"], dtype=np.int32)

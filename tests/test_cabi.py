@@ -26,6 +26,61 @@ def test_exports_match_header(lib):
         assert hasattr(lib, sym), sym
 
 
+def test_argtypes_match_header(lib):
+    """Every prototype of include/chicdiff_hip.h against the ctypes declaration of hip.load_library(), position by position and by class:
+    an integer or double of the header's width, or a pointer (anything with '*' and the two callback typedefs); a return type other
+    than int needs its restype.  An entry point without argtypes would take every Python int as a 32-bit C int."""
+    from chicdiff_amd import hip
+    hdr = open(os.path.join(ROOT, "include", "chicdiff_hip.h")).read()
+    hdr = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))
+    scalars = {"int32_t": C.c_int32, "int": C.c_int, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "double": C.c_double}
+    assert C.sizeof(C.c_int) == 4                                                   # (the header's plain int and ctypes' default restype)
+
+    def kind(ctype):
+        if ctype is None:
+            return "void"
+        for name, t in scalars.items():
+            if ctype is t or (issubclass(ctype, C._SimpleCData) and ctype._type_ == t._type_):
+                return "int" if name in ("int", "int32_t") else name
+        assert ctype in (C.c_void_p, C.c_char_p) or issubclass(ctype, (C._Pointer, C._CFuncPtr, C.Array)), ctype
+        return "pointer"
+
+    def kind_of_text(text):
+        words = text.replace("const", " ").split()
+        if "*" in text or words[0] in ("chicdiff_allreduce_fn", "chicdiff_allgather_fn"):
+            return "pointer"
+        if words[0] == "void":
+            return "void"
+        return "int" if words[0] in ("int", "int32_t") else {k: k for k in scalars}[words[0]]
+
+    protos = re.findall(r"([A-Za-z_][A-Za-z0-9_ \*]*?)\b(chicdiff_hip_[a-z0-9_]+)\s*\(([^;{]*)\)\s*;", hdr)
+    assert sorted(p[1] for p in protos) == sorted(hip.EXPORTS)
+    bad = []
+    for ret, name, params in protos:
+        fn = getattr(lib, name)
+        if fn.argtypes is None:
+            bad.append(f"{name}: no argtypes")
+            continue
+        want = [kind_of_text(p) for p in params.split(",")]
+        got = [kind(t) for t in fn.argtypes]
+        if want != got:
+            bad.append(f"{name}: header {want}, argtypes {got}")
+        if kind_of_text(ret + " x") != kind(fn.restype):
+            bad.append(f"{name}: header returns {ret.strip()!r}, restype {fn.restype}")
+    assert not bad, "\n".join(bad)
+
+
+def test_no_assert_statement_guards_the_package():
+    """``python -O`` strips assert statements: nothing in chicdiff_amd/*.py may rest on one (refusals are ValueError)."""
+    import ast
+    import glob
+    found = []
+    for path in sorted(glob.glob(os.path.join(ROOT, "chicdiff_amd", "*.py"))):
+        tree = ast.parse(open(path).read(), path)
+        found += [f"{os.path.basename(path)}:{node.lineno}" for node in ast.walk(tree) if isinstance(node, ast.Assert)]
+    assert not found, found
+
+
 def test_header_lists_the_options_of_the_librarys_table():
     """The comment block above chicdiff_hip_set_option in include/chicdiff_hip.h is the only documentation a host has: it names
     every option of the library's table (kOptions, chicdiff_amd/csrc/ctx.hip), and no other, in the table's order."""

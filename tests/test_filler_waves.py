@@ -23,13 +23,7 @@ def lib():
     import __graft_entry__ as g
     g.build()
     from chicdiff_amd import hip
-    L = hip.load_library()
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    L.chicdiff_hip_selftest_sched_class.argtypes = [C.c_int32, C.c_double, dp, dp, C.c_int64, ip, ip]
-    L.chicdiff_hip_selftest_queue_claim.argtypes = [C.c_uint64, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
-                                                    C.POINTER(C.c_uint32), ip]
-    L.chicdiff_hip_selftest_queue_claim.restype = C.c_int
-    return L
+    return hip.load_library()
 
 
 # ---- CPU: the claim rule ----------------------------------------------------------------------------------------------------------------

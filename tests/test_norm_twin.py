@@ -320,14 +320,9 @@ def test_a4_planted_rows_are_present():
 def hiplib():
     import test_size_factors_direct as sfd
     import __graft_entry__ as g
-    import ctypes as C
     g.build()
     from chicdiff_amd import hip
-    L = hip.load_library()
-    L.chicdiff_hip_selftest_sf_bin.argtypes = [C.c_int32, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
-                                                  C.POINTER(C.c_int32)]
-    L.chicdiff_hip_selftest_sf_bin.restype = C.c_int
-    return L, sfd
+    return hip.load_library(), sfd
 
 
 def test_a5_planted_matrices_meet_the_select_paths(hiplib):

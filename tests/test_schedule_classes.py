@@ -36,10 +36,7 @@ def lib():
     import __graft_entry__ as g
     g.build()
     from chicdiff_amd import hip
-    L = hip.load_library()
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    L.chicdiff_hip_selftest_sched_class.argtypes = [C.c_int32, C.c_double, dp, dp, C.c_int64, ip, ip]
-    return L
+    return hip.load_library()
 
 
 def lib_sched_class(L, a0, gmin, mode):

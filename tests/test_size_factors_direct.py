@@ -24,11 +24,7 @@ def lib():
     import __graft_entry__ as g
     g.build()
     from chicdiff_amd import hip
-    L = hip.load_library()
-    L.chicdiff_hip_selftest_sf_bin.argtypes = [C.c_int32, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
-                                                  C.POINTER(C.c_int32)]
-    L.chicdiff_hip_selftest_sf_bin.restype = C.c_int
-    return L
+    return hip.load_library()
 
 
 def lib_bins(L, S, x, sub_of=None):

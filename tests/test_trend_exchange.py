@@ -21,11 +21,7 @@ def lib():
     import __graft_entry__ as g
     g.build()
     from chicdiff_amd import hip
-    L = hip.load_library()
-    L.chicdiff_hip_selftest_trend_exchange.argtypes = [C.c_int32, C.c_uint32, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_uint64),
-                                                       C.POINTER(C.c_int32)]
-    L.chicdiff_hip_selftest_trend_exchange.restype = C.c_int
-    return L
+    return hip.load_library()
 
 
 def call(L, op, tag, n, x=None, words=None, accept=None):

@@ -345,11 +345,10 @@ def oracle():
 def host_prior_var(hist, df):
     """chicdiff_hip_selftest_prior_mc: the library's host form of the simulated prior (pmc_prior_var)."""
     import ctypes as C
-    tt.simulated_densities(df)  # (loads the library and sets the argument types)
     from chicdiff_amd import hip
     h = np.ascontiguousarray(hist, dtype=np.float64)
     pv = C.c_double(0.0)
-    assert hip.load_library().chicdiff_hip_selftest_prior_mc(int(df), h.ctypes.data, None, C.addressof(pv)) == 0
+    assert hip.load_library().chicdiff_hip_selftest_prior_mc(int(df), h.ctypes.data_as(C.c_void_p), None, C.byref(pv)) == 0
     return pv.value
 
 

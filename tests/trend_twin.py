@@ -415,14 +415,10 @@ def simulated_densities(df):
     """The 200 x 40 simulated densities of residual d.f. `df` from the library's host entry (tests/test_r_rng.py holds them bit for
     bit to the oracle's): an input of the twin, not restated here."""
     if df not in _DENS:
-        import ctypes as C
-
         import numpy as np
 
         from chicdiff_amd import hip
         out = np.empty((200, 40))
-        lib = hip.load_library()
-        lib.chicdiff_hip_selftest_prior_mc.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        assert lib.chicdiff_hip_selftest_prior_mc(int(df), None, out.ctypes.data, None) == 0
+        assert hip.load_library().chicdiff_hip_selftest_prior_mc(int(df), None, out.ctypes.data, None) == 0
         _DENS[df] = out
     return _DENS[df]
