@@ -317,6 +317,9 @@ hipError_t launch_region_assemble(const int32_t *bait, const int32_t *oe, int64_
                                   const int64_t *midsum, const double *sj, const double *si, const int32_t *tblb, const int32_t *tlb,
                                   const double *T, int32_t ntblb, int32_t ntlb, const double *distfun_dev, int32_t *N, double *FM,
                                   void *scratch, int force_generic, hipStream_t st);
+size_t count_merge_scratch_bytes(int S, const int64_t *nkeys);
+hipError_t launch_count_merge(int pass, int S, const int64_t *const *keys, const int32_t *const *vals, const int64_t *nkeys, int64_t cap,
+                              int64_t *keys_out, int32_t *vals_out, void *scratch, int64_t **start_out, int64_t *ntile_out, hipStream_t st);
 // post_kernels.hip
 size_t bh_workspace_bytes(int64_t n);
 int launch_bh_adjust(const double *p, int64_t n, double *padj, char *ws, hipStream_t st);
@@ -332,6 +335,7 @@ size_t ct_workspace_bytes(int64_t n);
 int launch_count_table(const int32_t *bait, const int32_t *oe, const int32_t *N, int64_t n, const uint8_t *keep, int32_t max_id,
                        int64_t *keys_out, int32_t *vals_out, char *ws, hipStream_t st);
 size_t ru_scan_bytes(int64_t n);
+int launch_scan_i64(int64_t *d, int64_t n, void *tmp, size_t tmp_bytes, hipStream_t st);
 int launch_ru_count(const int32_t *bait, const int32_t *oe, int64_t n, int s, const int32_t *chr_of, int maxfrag,
                     int64_t *region_ptr, int32_t *minOE, int32_t *maxOE, int *bad, void *tmp, size_t tmp_bytes, hipStream_t st,
                     unsigned int *mask_out = nullptr);  // mask_out (n words, may be NULL): per region, which candidates of its window are kept

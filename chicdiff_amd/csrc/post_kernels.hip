@@ -317,6 +317,14 @@ size_t ru_scan_bytes(int64_t n) {
     (void)rocprim::exclusive_scan(nullptr, tmp, d, d, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), (hipStream_t)0);
     return tmp + 256;
 }
+// d (n + 1 entries: n lengths, entry n = 0) -> scanned in place: every item's first row and, in entry n, their sum (the same rocPRIM
+// instance as launch_ru_count's); tmp: ru_scan_bytes(n)
+int launch_scan_i64(int64_t *d, int64_t n, void *tmp, size_t tmp_bytes, hipStream_t st) {
+    size_t need = 0;
+    (void)rocprim::exclusive_scan(nullptr, need, d, d, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st);
+    if (need > tmp_bytes) return 2;
+    return rocprim::exclusive_scan(tmp, need, d, d, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st) == hipSuccess ? 0 : 1;
+}
 // region_ptr (n+1): first used as the lengths (entry n = 0), then scanned in place
 int launch_ru_count(const int32_t *bait, const int32_t *oe, int64_t n, int s, const int32_t *chr_of, int maxfrag,
                     int64_t *region_ptr, int32_t *minOE, int32_t *maxOE, int *bad, void *tmp, size_t tmp_bytes, hipStream_t st, unsigned int *mask_out) {

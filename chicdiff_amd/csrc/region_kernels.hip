@@ -607,7 +607,7 @@ void launch_fragment_background(const int32_t *bait, const int32_t *oe, int64_t 
 // Equal to those three calls bit for bit: the join is join_tile_table (its result does not depend on which lane holds which
 // query), FullMean is bg_row_geometry / bg_row_replicate, and a lane adds up its region's rows one after the other in ascending
 // row order from 0 / 0.0, as window_sums_kernel does.  The branch without chinput files (count_join_inner: Reduce(merge) semantics,
-// a pair counts only where every replicate holds it) is NOT covered; it keeps the three calls.
+// a pair counts only where every replicate holds it) comes here through the merged tables of launch_count_merge below.
 // Work unit: a wave owns a tile of kAsmRegions consecutive regions = the consecutive RU rows rptr[i0] .. rptr[i1].
 //   * kAsmRegions = 46: with the default RUexpand = 5 a region has at most 11 rows, so 46 regions (506 rows) fill the 512-row
 //     join tile; the tiling is fixed (region i belongs to tile i / 46), so no scan and no host read decides it.
@@ -831,6 +831,294 @@ hipError_t launch_region_assemble(const int32_t *bait, const int32_t *oe, int64_
         region_assemble_kernel<<<(unsigned)blocks, 256, 0, st>>>(a);
         if (hipError_t e = hipGetLastError()) return e;
     }
+    return hipSuccess;
+}
+
+// a1 without chinput files, the merge itself (chicdiff.R:778, the Reduce(merge) of :774-807 and :1202-1260): mergedFiles = the pairs
+// that EVERY replicate's table holds, each with its S counts, formed once per call of getFullRegionData.  The left join of the chinput
+// branch (count_join_multi, region_assemble) against the merged tables then IS the inner join of this branch, bit for bit: a pair absent
+// from any replicate is absent from the merged table and gets 0 in every replicate, a pair held by all keeps each replicate's N.
+//   * pivot = the table with the fewest keys (the first of them on a tie; the host knows nkeys).  Only its keys can be in the result,
+//     and the result is the intersection, so it does not depend on which table that is.
+//   * mark pass (count_merge_mark_kernel): a wave owns a tile of kJoinTile consecutive pivot keys, eight per lane as the RU rows of the
+//     count join, and tests them against every other table in turn.  Tile and table are sorted, so the tile maps to one narrow key
+//     range per table: the coarse level, wave_lower_bound, the key window in the wave's LDS slice and the branch-free searches are
+//     join_tile_table's (join_tile_hits below, its sibling without values).  A hit is KEY EQUALITY at the lower bound — a table may hold
+//     N = 0, which join_tile_table's result cannot tell from "absent".  The hits are ANDed over the tables; once no query of the tile
+//     is alive the wave leaves the tile (wave-uniform), so disjoint tables cost one table's test.  Out: one flag byte per lane (bit k =
+//     pivot key 8 lane + k is kept; 64 bytes = 512 flag bits per tile) and the tile's count.  More than kJoinMaxTables other tables:
+//     several launches, the flag bytes carry the mask from one batch to the next.
+//   * one rocPRIM exclusive scan of the tile counts (launch_scan_i64, in place): every tile's first output row, and behind the last
+//     tile n_out — the one value the host waits for.
+//   * write pass (count_merge_write_kernel): output row = the tile's first row + the key's rank among the tile's kept keys (one ballot
+//     and popcount per flag bit).  The key and the pivot's value come from the pivot's own columns; every other table's value comes from
+//     resolving the tile again with join_tile_table itself — for a kept key the value at its lower bound.  Tiles that keep nothing
+//     are skipped.  Why not positions stored by the mark pass: per pivot key and table they cost 8 bytes written and 8 read again plus a
+//     4-byte gather that touches the same lines of the value column, against 8 bytes of the key window read again (L2 / Infinity
+//     Cache warm from the mark pass) + 4 of values read coalesced; the traffic is about equal, the (S - 1) x npivot x 8 bytes of
+//     scratch are not needed, and the write pass runs the very function whose result the downstream joins must reproduce.
+// Placement is by the scan alone: no value and no position passes through an atomic, so the output does not depend on the launch
+// shape or on the order in which waves arrive.  Rows are 64-bit throughout.
+__device__ __forceinline__ uint32_t join_tile_hits(const int64_t (&q)[kJoinPerLane], int64_t kmin, int64_t kmax, const int64_t *__restrict__ keys,
+                                                   int64_t nkeys, const int64_t *__restrict__ index, int64_t nidx, int64_t *sk, int lane) {
+    // [lo, hi): join_tile_table's steps 1 and 2
+    const int64_t jlo = wave_lower_bound(index, 0, nidx, kmin, lane);
+    int64_t lo = 0;
+    if (jlo > 0) {
+        const int64_t e = 64 * jlo < nkeys ? 64 * jlo : nkeys;
+        lo = wave_lower_bound(keys, 64 * (jlo - 1) + 1, e, kmin, lane);
+    }
+    int64_t hi;
+    {
+        const int64_t j0 = lo / 64 + 1, pos = j0 + lane;
+        const int c = __popcll(__ballot(pos < nidx && index[pos] < kmax));
+        int64_t jhi = j0 + c;
+        if (c == 64) jhi = wave_lower_bound(index, j0 + 64, nidx, kmax, lane);
+        hi = jhi < nidx ? 64 * jhi + 1 : nkeys;
+    }
+    uint32_t hits = 0;
+    if (hi - lo <= kJoinCap) {
+        const int w = (int)(hi - lo);
+        {
+            int64_t tk[kJoinCap / 64];
+#pragma unroll
+            for (int e = 0; e < kJoinCap / 64; e++) {
+                const int at = e * 64 + lane;
+                tk[e] = at < w ? keys[lo + at] : 0;
+            }
+#pragma unroll
+            for (int e = 0; e < kJoinCap / 64; e++) sk[e * 64 + lane] = tk[e];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        int b[kJoinPerLane];
+#pragma unroll
+        for (int k = 0; k < kJoinPerLane; k++) b[k] = 0;
+        int len = w;
+        while (len > 1) {
+            const int half = len >> 1;
+#pragma unroll
+            for (int k = 0; k < kJoinPerLane; k++) b[k] += sk[b[k] + half - 1] < q[k] ? half : 0;
+            len -= half;
+        }
+        if (len == 1) {
+#pragma unroll
+            for (int k = 0; k < kJoinPerLane; k++) b[k] += sk[b[k]] < q[k] ? 1 : 0;
+        }
+#pragma unroll
+        for (int k = 0; k < kJoinPerLane; k++) {
+            const bool in = b[k] < w;
+            const int at = in ? b[k] : 0;
+            hits |= (in && sk[at] == q[k]) ? 1u << k : 0u;
+        }
+        __builtin_amdgcn_wave_barrier();  // the slice is rewritten by the next table
+    } else {
+        int64_t b[kJoinPerLane];
+#pragma unroll
+        for (int k = 0; k < kJoinPerLane; k++) b[k] = lo;
+        int64_t len = hi - lo;
+        while (len > 1) {
+            const int64_t half = len >> 1;
+#pragma unroll
+            for (int k = 0; k < kJoinPerLane; k++) b[k] += keys[b[k] + half - 1] < q[k] ? half : 0;
+            len -= half;
+        }
+#pragma unroll
+        for (int k = 0; k < kJoinPerLane; k++) b[k] += keys[b[k]] < q[k] ? 1 : 0;  // len == 1: the range has > kJoinCap keys
+#pragma unroll
+        for (int k = 0; k < kJoinPerLane; k++) {
+            const bool in = b[k] < hi;
+            const int64_t at = in ? b[k] : lo;
+            hits |= (in && keys[at] == q[k]) ? 1u << k : 0u;
+        }
+    }
+    return hits;
+}
+struct CountMergeArgs {
+    const int64_t *pkeys;  // the pivot: np keys, np >= 1
+    const int32_t *pvals;
+    int64_t np;
+    JoinTables tb;                  // the other tables of this launch
+    int32_t col[kJoinMaxTables];    // ... and the output column of each
+    int32_t pcol, first, vec;       // the pivot's column; first launch of its pass; pkeys is 16-byte aligned
+    uint8_t *flags;                 // ntile x 64
+    int64_t *start;                 // ntile + 1: the tiles' counts (mark), scanned in place to their first rows (write)
+    int64_t cap;
+    int64_t *keys_out;
+    int32_t *vals_out;
+};
+// a tile's pivot keys -> q[] (the rows behind the table's end repeat its last key: any value inside the tile's key range will do,
+// their flag bits are never set), which of them exist, and the tile's smallest / largest key: its first and last (the table is sorted)
+__device__ __forceinline__ uint32_t merge_tile_keys(const CountMergeArgs &a, int64_t tile, int lane, int64_t (&q)[kJoinPerLane], int64_t &kmin,
+                                                    int64_t &kmax) {
+    const int64_t t0 = tile * kJoinTile, r0 = t0 + (int64_t)lane * kJoinPerLane;
+    const int64_t last = t0 + kJoinTile <= a.np ? t0 + kJoinTile - 1 : a.np - 1;
+    kmin = uniform64(a.pkeys[t0]);
+    kmax = uniform64(a.pkeys[last]);
+    uint32_t valid = 0;
+    if (a.vec && t0 + kJoinTile <= a.np) {
+        const longlong2 *p = reinterpret_cast<const longlong2 *>(a.pkeys + r0);
+        const longlong2 v0 = p[0], v1 = p[1], v2 = p[2], v3 = p[3];
+        q[0] = v0.x; q[1] = v0.y; q[2] = v1.x; q[3] = v1.y; q[4] = v2.x; q[5] = v2.y; q[6] = v3.x; q[7] = v3.y;
+        valid = 0xffu;
+    } else {
+#pragma unroll
+        for (int k = 0; k < kJoinPerLane; k++) {
+            const bool v = r0 + k < a.np;
+            q[k] = v ? a.pkeys[r0 + k] : kmax;
+            valid |= v ? 1u << k : 0u;
+        }
+    }
+    return valid;
+}
+__global__ __launch_bounds__(256, 4) void count_merge_mark_kernel(CountMergeArgs a) {
+    __shared__ int64_t s_keys[4][kJoinCap];
+    const int lane = threadIdx.x & 63;
+    int64_t *const sk = s_keys[threadIdx.x >> 6];
+    const int64_t ntile = (a.np + kJoinTile - 1) / kJoinTile;
+    const int64_t per_xcd = (ntile + 7) / 8, t_begin = (int64_t)(blockIdx.x & 7) * per_xcd;  // (speed only: count_join_kernel)
+    const int64_t t_end = t_begin + per_xcd < ntile ? t_begin + per_xcd : ntile;
+    const int64_t wave0 = (int64_t)(blockIdx.x >> 3) * 4 + (threadIdx.x >> 6), nwave = (int64_t)(gridDim.x >> 3) * 4;
+    for (int64_t tile = t_begin + wave0; tile < t_end; tile += nwave) {
+        uint32_t alive = 0;
+        if (!a.first) {
+            alive = a.flags[tile * 64 + lane];
+            if (__ballot(alive != 0) == 0) continue;  // dead since an earlier batch: flags and count stand
+        }
+        int64_t q[kJoinPerLane], kmin, kmax;
+        const uint32_t valid = merge_tile_keys(a, tile, lane, q, kmin, kmax);
+        if (a.first) alive = valid;
+#pragma unroll 1
+        for (int t = 0; t < a.tb.T; t++) {
+            if (__ballot(alive != 0) == 0) break;
+            const int64_t nk = a.tb.nkeys[t];
+            alive &= join_tile_hits(q, kmin, kmax, a.tb.keys[t], nk, a.tb.index[t], (nk + 63) / 64, sk, lane);
+        }
+        a.flags[tile * 64 + lane] = (uint8_t)alive;
+        int cnt = 0;
+#pragma unroll
+        for (int k = 0; k < kJoinPerLane; k++) cnt += __popcll(__ballot((alive >> k) & 1u));
+        if (lane == 0) a.start[tile] = cnt;
+    }
+}
+__global__ __launch_bounds__(256, 4) void count_merge_write_kernel(CountMergeArgs a) {
+    __shared__ int64_t s_keys[4][kJoinCap];
+    __shared__ int32_t s_vals[4][kJoinCap];
+    const int lane = threadIdx.x & 63;
+    int64_t *const sk = s_keys[threadIdx.x >> 6];
+    int32_t *const sv = s_vals[threadIdx.x >> 6];
+    const int64_t ntile = (a.np + kJoinTile - 1) / kJoinTile;
+    const int64_t per_xcd = (ntile + 7) / 8, t_begin = (int64_t)(blockIdx.x & 7) * per_xcd;
+    const int64_t t_end = t_begin + per_xcd < ntile ? t_begin + per_xcd : ntile;
+    const int64_t wave0 = (int64_t)(blockIdx.x >> 3) * 4 + (threadIdx.x >> 6), nwave = (int64_t)(gridDim.x >> 3) * 4;
+    const uint64_t below = (1ull << lane) - 1;  // the lanes before this one
+    for (int64_t tile = t_begin + wave0; tile < t_end; tile += nwave) {
+        const int64_t row0 = uniform64(a.start[tile]);
+        if (uniform64(a.start[tile + 1]) == row0) continue;  // nothing kept
+        const uint32_t alive = a.flags[tile * 64 + lane];
+        int64_t q[kJoinPerLane], kmin, kmax;
+        merge_tile_keys(a, tile, lane, q, kmin, kmax);
+        int before = 0;  // kept keys of the lanes before this one
+#pragma unroll
+        for (int k = 0; k < kJoinPerLane; k++) before += __popcll(__ballot((alive >> k) & 1u) & below);
+        int64_t row[kJoinPerLane];
+#pragma unroll
+        for (int k = 0; k < kJoinPerLane; k++) row[k] = row0 + before + __popc(alive & ((1u << k) - 1u));
+        if (a.first) {
+            const int64_t r0 = tile * kJoinTile + (int64_t)lane * kJoinPerLane;
+            int32_t *pc = a.vals_out + (int64_t)a.pcol * a.cap;
+#pragma unroll
+            for (int k = 0; k < kJoinPerLane; k++)
+                if ((alive >> k) & 1u) {
+                    a.keys_out[row[k]] = q[k];
+                    pc[row[k]] = a.pvals[r0 + k];
+                }
+        }
+#pragma unroll 1
+        for (int t = 0; t < a.tb.T; t++) {
+            int32_t res[kJoinPerLane];
+            const int64_t nk = a.tb.nkeys[t];
+            join_tile_table(q, kmin, kmax, a.tb.keys[t], a.tb.vals[t], nk, a.tb.index[t], (nk + 63) / 64, sk, sv, lane, res);
+            int32_t *col = a.vals_out + (int64_t)a.col[t] * a.cap;
+#pragma unroll
+            for (int k = 0; k < kJoinPerLane; k++)
+                if ((alive >> k) & 1u) col[row[k]] = res[k];
+        }
+    }
+}
+// the scratch of launch_count_merge: the coarse levels of all tables, then the tiles' counts / first rows and their flag bytes
+// (+ the scan's own, launch_scan_i64: ru_scan_bytes(ntile))
+static size_t count_merge_index_bytes(int S, const int64_t *nkeys) { return (count_join_multi_scratch_bytes(S, nkeys) + 255) / 256 * 256; }
+static int64_t count_merge_ntile(int S, const int64_t *nkeys) {
+    int64_t np = nkeys[0];
+    for (int s = 1; s < S; s++) np = nkeys[s] < np ? nkeys[s] : np;
+    return (np + kJoinTile - 1) / kJoinTile;
+}
+size_t count_merge_scratch_bytes(int S, const int64_t *nkeys) {
+    const size_t ntile = (size_t)count_merge_ntile(S, nkeys);
+    return count_merge_index_bytes(S, nkeys) + (sizeof(int64_t) * (ntile + 1) + 255) / 256 * 256 + 64 * ntile;
+}
+// keys / vals / nkeys: host arrays of S entries (device pointers inside), every nkeys[s] >= 1; vals_out: column s at [s * cap], cap >= min nkeys.
+// pass 0 = the mark pass, then the caller scans *start_out (ntile + 1 entries, in place), pass 1 = the write pass; n_out = (*start_out)[ntile].
+hipError_t launch_count_merge(int pass, int S, const int64_t *const *keys, const int32_t *const *vals, const int64_t *nkeys, int64_t cap,
+                              int64_t *keys_out, int32_t *vals_out, void *scratch, int64_t **start_out, int64_t *ntile_out, hipStream_t st) {
+    int pivot = 0;
+    for (int s = 1; s < S; s++)
+        if (nkeys[s] < nkeys[pivot]) pivot = s;
+    const int64_t ntile = count_merge_ntile(S, nkeys);
+    char *ws = (char *)scratch;
+    int64_t *index = (int64_t *)ws;
+    int64_t *start = (int64_t *)(ws + count_merge_index_bytes(S, nkeys));
+    uint8_t *flags = (uint8_t *)start + (sizeof(int64_t) * (size_t)(ntile + 1) + 255) / 256 * 256;
+    *start_out = start;
+    *ntile_out = ntile;
+    if (pass == 0)
+        if (hipError_t e = hipMemsetAsync(start + ntile, 0, sizeof(int64_t), st)) return e;
+    int64_t blocks = ((ntile + 3) / 4 + 7) / 8 * 8;  // a multiple of 8: one share of the tiles per XCD
+    blocks = blocks > 8192 ? 8192 : blocks;
+    int s = 0;
+    bool first = true;
+    do {  // (S = 1: one launch without tables — every pivot key is kept)
+        CountMergeArgs a{};
+        a.pkeys = keys[pivot];
+        a.pvals = vals[pivot];
+        a.np = nkeys[pivot];
+        a.pcol = pivot;
+        a.first = first ? 1 : 0;
+        a.vec = (((uintptr_t)keys[pivot]) & 15) == 0;
+        a.flags = flags;
+        a.start = start;
+        a.cap = cap;
+        a.keys_out = keys_out;
+        a.vals_out = vals_out;
+        int64_t maxidx = 0;
+        for (; s < S && a.tb.T < kJoinMaxTables; s++) {
+            if (s == pivot) continue;
+            const int t = a.tb.T++;
+            a.tb.keys[t] = keys[s];
+            a.tb.vals[t] = vals[s];
+            a.tb.nkeys[t] = nkeys[s];
+            a.tb.index[t] = index;
+            a.col[t] = s;
+            const int64_t nidx = (nkeys[s] + 63) / 64;
+            index += nidx + 1;
+            maxidx = nidx > maxidx ? nidx : maxidx;
+        }
+        if (pass == 0) {
+            if (a.tb.T > 0) {  // the coarse levels stay for the write pass
+                const int64_t bx = (maxidx + 255) / 256;
+                join_index_multi_kernel<<<dim3((unsigned)(bx > 1024 ? 1024 : bx), a.tb.T), 256, 0, st>>>(a.tb);
+                if (hipError_t e = hipGetLastError()) return e;
+            }
+            count_merge_mark_kernel<<<(unsigned)blocks, 256, 0, st>>>(a);
+        } else {
+            count_merge_write_kernel<<<(unsigned)blocks, 256, 0, st>>>(a);
+        }
+        if (hipError_t e = hipGetLastError()) return e;
+        first = false;
+        if (s == pivot) s++;  // (the pivot as the last table)
+    } while (s < S);
     return hipSuccess;
 }
 

@@ -590,6 +590,58 @@ extern "C" int chicdiff_hip_count_join_inner_dev(chicdiff_hip_ctx *c, const int3
     return CHICDIFF_OK;
 }
 
+// a1 without chinput files, the merge alone (chicdiff.R:778, the Reduce(merge) of :774-807 and :1202-1260): the pairs every replicate
+// holds, each with its S counts.  count_join_multi / region_assemble on the merged tables equal count_join_inner on the original ones.
+extern "C" int chicdiff_hip_count_tables_merge_dev(chicdiff_hip_ctx *c, int32_t S, const int64_t *const *d_keys, const int32_t *const *d_vals,
+                                                   const int64_t *nkeys, int64_t cap, int64_t *d_keys_out, int32_t *d_vals_out,
+                                                   int64_t *n_out) {
+    if (!c) return CHICDIFF_E_INVALID;
+    if (S < 1 || S > kMaxS) return fail(c, CHICDIFF_E_INVALID, "count_tables_merge: need 1 <= S <= %d (S = %d)", kMaxS, (int)S);
+    if (!d_keys || !d_vals || !nkeys || !n_out || cap < 0) return fail(c, CHICDIFF_E_INVALID, "count_tables_merge: bad arguments (a NULL pointer)");
+    int64_t np = INT64_MAX;
+    for (int s = 0; s < S; s++) {
+        if (nkeys[s] < 0 || (nkeys[s] > 0 && (!d_keys[s] || !d_vals[s]))) return fail(c, CHICDIFF_E_INVALID, "count_tables_merge: bad table %d", s);
+        np = nkeys[s] < np ? nkeys[s] : np;
+    }
+    if (cap < np)
+        return fail(c, CHICDIFF_E_INVALID, "count_tables_merge: room for %lld rows needed (the smallest table), %lld given (nothing was written)",
+                    (long long)np, (long long)cap);
+    if (np > 0 && (!d_keys_out || !d_vals_out)) return fail(c, CHICDIFF_E_INVALID, "count_tables_merge: bad arguments (a NULL output)");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    *n_out = 0;
+    if (np == 0) return CHICDIFF_OK;  // an empty table: no pair is held by all
+    const size_t ws_bytes = (count_merge_scratch_bytes(S, nkeys) + 255) / 256 * 256;
+    const int64_t ntile_max = (np + 511) / 512;
+    const size_t scan_bytes = ru_scan_bytes(ntile_max);
+    if (int rc = ensure_aux(c, ws_bytes + scan_bytes)) return rc;
+    int64_t *start = nullptr, ntile = 0;
+    hipError_t le = hipSuccess;
+    int sc = 0;
+    {
+        Scope t(c, "count_merge_mark");
+        le = launch_count_merge(0, S, d_keys, d_vals, nkeys, cap, d_keys_out, d_vals_out, c->aux, &start, &ntile, c->stream);
+    }
+    if (le == hipSuccess) {
+        Scope t(c, "count_merge_scan");
+        sc = launch_scan_i64(start, ntile, c->aux + ws_bytes, scan_bytes, c->stream);
+    }
+    if (le == hipSuccess && sc == 0) {
+        Scope t(c, "count_merge_write");
+        le = launch_count_merge(1, S, d_keys, d_vals, nkeys, cap, d_keys_out, d_vals_out, c->aux, &start, &ntile, c->stream);
+    }
+    long long h = 0;
+    hipError_t e = hipSuccess;
+    if (le == hipSuccess && sc == 0) e = hipMemcpyAsync(&h, start + ntile, sizeof h, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    timing_collect(c);
+    if (le != hipSuccess) return fail(c, CHICDIFF_E_HIP, "count_tables_merge: a launch failed: %s", hipGetErrorString(le));
+    if (sc) return fail(c, CHICDIFF_E_HIP, "count_tables_merge: scan failed");
+    if (e != hipSuccess) return fail(c, CHICDIFF_E_HIP, "count_tables_merge: %s", hipGetErrorString(e));
+    *n_out = (int64_t)h;
+    return CHICDIFF_OK;
+}
+
 // ---- a9: results() on device -----------------------------------------------------------------------------------
 extern "C" int chicdiff_hip_cooks_filter_dev(chicdiff_hip_ctx *c, const int32_t *d_counts, int64_t n, int32_t S, const int32_t *group,
                                              const double *d_maxCooks, const int32_t *d_cooksArgmax, double cutoff, double *d_pvalue,

@@ -38,6 +38,7 @@ EXPORTS = [
     "chicdiff_hip_peaks_caps", "chicdiff_hip_selftest_peaks",
     "chicdiff_hip_peaks_textkeys_dev", "chicdiff_hip_peaks_merge_dev", "chicdiff_hip_peaks_header", "chicdiff_hip_selftest_peaks_textkeys",
     "chicdiff_hip_count_join_inner_dev", "chicdiff_hip_count_join_multi_dev", "chicdiff_hip_region_assemble_dev",
+    "chicdiff_hip_count_tables_merge_dev",
     "chicdiff_hip_malloc", "chicdiff_hip_free", "chicdiff_hip_outstanding_allocations", "chicdiff_hip_memcpy_h2d", "chicdiff_hip_memcpy_d2h",
     "chicdiff_hip_rccl_unique_id", "chicdiff_hip_rccl_init", "chicdiff_hip_cooks_filter_dev",
     "chicdiff_hip_independent_filtering_dev",
@@ -174,6 +175,7 @@ def load_library() -> C.CDLL:
     L.chicdiff_hip_region_avdist_dev.argtypes = [vp, vp, vp, i64, vp, i64, i32, i32, vp, vp, vp]
     L.chicdiff_hip_count_join_inner_dev.argtypes = [vp, vp, vp, i64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp]
     L.chicdiff_hip_count_join_multi_dev.argtypes = [vp, vp, vp, i64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp]
+    L.chicdiff_hip_count_tables_merge_dev.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), i64, vp, vp, C.POINTER(i64)]
     L.chicdiff_hip_region_assemble_dev.argtypes = [vp, vp, vp, i64, vp, i64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), i32, i32,
                                                    vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(dbl), vp, vp]
     L.chicdiff_hip_ihw_apply_dev.argtypes = [vp, vp, vp, i64, C.POINTER(dbl), C.POINTER(dbl), i32, vp, vp, vp, vp]
@@ -881,6 +883,23 @@ class HipContext:
         out = torch.empty((S, nru), dtype=torch.int32, device=self.device)
         self._check(self.lib.chicdiff_hip_count_join_inner_dev(self.h, pb, po, nru, S, kp, vp, nk, out.data_ptr()))
         return out
+
+    def merge_count_tables(self, count_tables):
+        """No-chinput branch, the merge alone (chicdiff.R:778, the Reduce(merge) of :774-807): ``count_tables`` = [(keys, vals)] per replicate as
+        ``count_table`` returns them -> [(keys, vals_s)] per replicate, the pairs that EVERY table holds (key equality: N = 0 is a count)
+        with each replicate's counts.  One keys tensor is shared by all replicates; the values are the rows of one (S, cap) tensor cut
+        to the merged length, so every ``vals_s`` is contiguous.  ``count_join_multi`` / ``region_assemble`` on the result equal
+        ``count_join_inner`` (-> ``fragment_background`` -> ``window_sums``) on ``count_tables`` bit for bit."""
+        torch = self.torch
+        S, kp, vp, nk = self._tables("merge_count_tables", count_tables)
+        cap = min(nk)
+        keys = torch.empty(cap, dtype=torch.int64, device=self.device)
+        vals = torch.empty((S, cap), dtype=torch.int32, device=self.device)
+        n = C.c_int64(0)
+        self._check(self.lib.chicdiff_hip_count_tables_merge_dev(
+            self.h, S, kp, vp, nk, cap, self._ptr("keys", keys, torch.int64, (cap,)), self._ptr("vals", vals, torch.int32, (S, cap)), C.byref(n)))
+        keys = keys[: n.value]
+        return [(keys, vals[s, : n.value]) for s in range(S)]
 
     def region_avdist(self, d_bait, d_oe, d_region_ptr, id_min, d_midsum, d_chr=None):
         """avDist = mean(distSign) by regionID (chicdiff.R:1965-1967, :868-882) for CSR-ordered RU rows: the covariate

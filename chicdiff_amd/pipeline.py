@@ -612,13 +612,13 @@ def frame_columns_dev(df, ctx):
 
 
 def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, read_chicago=None, assemble=False, device_tables=False,
-                      device_countput=False, device_chinput=False, device_write=False):
+                      device_countput=False, device_chinput=False, device_write=False, merge_counts=False):
     """chicdiff.R:1460-1478 with the device path behind it: list(test block, control block, countput).  Every Chicago
     data set and every chinput file is read ONCE for both universes (what ``parallel = TRUE`` -> getFullRegionData2,
     :948-1456, does in the reference; the result does not depend on it).  The long "recast" table (one row per region,
     fragment and sample) is never built: a block holds the per-sample fragment columns N and FullMean on the device in
     (regionID, otherEndID) order, the region offsets, and IHWcorrection()'s per-region avDist.
-    ``assemble=True`` (chinput branch only): a block holds the region-level ``regionN`` / ``regionFullMean`` (S, n) that DESeq2Wrap
+    ``assemble=True`` (chinput branch, or ``merge_counts=True`` without countData): a block holds the region-level ``regionN`` / ``regionFullMean`` (S, n) that DESeq2Wrap
     would sum from the fragment columns — from one kernel (HipContext.region_assemble), same bits — and no fragment columns.
     ``device_tables=True``: the Chicago background tables are built on the device (``background_tables_dev``) instead of by pandas
     and uploaded — same bits; without countData the uploaded ID columns also feed ``ctx.count_table``.
@@ -627,15 +627,20 @@ def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, rea
     ``device_chinput=True``: the text of every chinput file is parsed on the device (``ctx.read_chinput(..., device=True)``) instead of
     by host threads — the same key tables; without countData no chinput file is read and it has no effect.
     ``device_write=True`` (with ``device_countput=True`` only): ``_countput.csv`` is formatted on the device from the aggregation's own
-    columns (``write_countput_dev``) instead of by ``to_csv`` — the same file, byte for byte; the returned frame is built as before."""
+    columns (``write_countput_dev``) instead of by ``to_csv`` — the same file, byte for byte; the returned frame is built as before.
+    ``merge_counts=True`` (without countData): the replicates' reconstructed tables are inner-merged ONCE on the device
+    (``ctx.merge_count_tables``: mergedFiles <- Reduce(merge, tempForCounts), chicdiff.R:778) and both universes are served from the
+    merged tables by the left joins of the chinput branch — ``count_join_multi``, or ``region_assemble`` with ``assemble=True`` —
+    instead of one ``count_join_inner`` per universe: same bits.  With countData nothing is merged and it has no effect."""
     if device_write and not device_countput:
         raise ValueError("getFullRegionData(device_write=True) writes the device columns of the countput aggregation: it needs "
                          "device_countput=True")
     s = asChicdiffSettings(chicdiff_settings)
-    if assemble and s["countData"] is None:
+    if assemble and s["countData"] is None and not merge_counts:
         raise ValueError("getFullRegionData(assemble=True) covers the chinput branch only: without countData the counts are "
                          "reconstructed from the Chicago data sets and inner-merged (chicdiff.R:774-807), which keeps "
-                         "count_join_inner -> fragment_background -> window_sums; call it with assemble=False")
+                         "count_join_inner -> fragment_background -> window_sums; call it with assemble=False, or with "
+                         "merge_counts=True, which merges the tables once and serves region_assemble from the merged ones")
     if read_chicago is None:
         raise ValueError("read_chicago: a reader of the Chicago data sets is required (readRDSorRDA stays R)")
     torch = ctx.torch
@@ -692,6 +697,12 @@ def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, rea
             d_xb, d_xo = d_ids[i] if d_ids is not None else (dev(x["baitID"].to_numpy(), np.int32), dev(x["otherEndID"].to_numpy(), np.int32))
             tables.append(ctx.count_table(d_xb, d_xo, dev(x["N"].to_numpy(), np.int32), d_flags))
         d_ids = None
+        if merge_counts:                                                           # :778, once for both universes
+            message("Merging countData")
+            merged = ctx.merge_count_tables(tables)
+            del tables                                                             # the originals go back to the allocator
+            tables = merged
+            del merged
 
     d_midsum, d_chr = dev(midsum, np.int64), dev(chr_codes, np.int32)
     d_bg = {k: bg[k] if device_tables else dev(bg[k], t) for k, t in (("sj", np.float64), ("si", np.float64), ("tblb", np.int32), ("tlb", np.int32), ("T", np.float64))}
@@ -707,7 +718,7 @@ def getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=None, rea
             blocks.append(post.HipRegionData(samples=names, condition=list(conditions), S=S, n=n, regionN=regN, regionFullMean=regFM,
                                              region_ptr=ptr, avDist=avDist, dispersions=dispersions, is_control=is_control))
             continue
-        if countData is not None:
+        if countData is not None or merge_counts:                # (merged tables: the left join IS the inner join of :774-807)
             fragN = ctx.count_join_multi(d_bait, d_oe, tables)   # the replicate loop of :843-858 as one pass over the RU rows
         else:
             message("Merging countData")
@@ -814,8 +825,8 @@ def IHWcorrection(chicdiff_settings, DESeqOut, FullRegionData, DESeqOutControl, 
 
 
 def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, rng=None, assemble=False, control_seed=None,
-                     device_peaks=False, device_merge=False, device_countput=False, device_write=False):
-    """chicdiff.R:301-347, same stage order and messages.  ``assemble``: passed to getFullRegionData.  ``control_seed``: the control
+                     device_peaks=False, device_merge=False, device_countput=False, device_write=False, merge_counts=False):
+    """chicdiff.R:301-347, same stage order and messages.  ``assemble``, ``merge_counts``: passed to getFullRegionData.  ``control_seed``: the control
     regions are drawn on the device from this seed (getControlRegionUniverse(seed=...)) instead of on the host from ``rng``, which
     then serves IHWcorrection's columns alone.  ``device_peaks``, ``device_merge``: passed to getRegionUniverse.  ``device_countput``:
     passed to getFullRegionData; ``device_write``: passed to getFullRegionData and IHWcorrection."""
@@ -832,7 +843,8 @@ def chicdiffPipeline(chicdiff_settings, ctx=None, read_chicago=None, ihw=None, r
         RUcontrol = getControlRegionUniverse(chicdiff_settings, RU, ctx, rng=rng if control_seed is None else None, seed=control_seed)
         message("\n*** Running getFullRegionData\n")
         FullRegionData = getFullRegionData(chicdiff_settings, RU, RUcontrol, suffix="", ctx=ctx, read_chicago=read_chicago,
-                                           assemble=assemble, device_countput=device_countput, device_write=device_write)
+                                           assemble=assemble, device_countput=device_countput, device_write=device_write,
+                                           merge_counts=merge_counts)
         message("\n*** Running DESeq2Wrap for FullRegion\n")
         DESeqOut = DESeq2Wrap(chicdiff_settings, RU, FullRegionData[0], ctx=ctx)
         message("\n*** Running DESeq2Wrap for FullControlRegion\n")

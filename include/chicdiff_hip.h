@@ -267,8 +267,9 @@ int chicdiff_hip_count_join_multi_dev(chicdiff_hip_ctx *ctx, const int32_t *d_ru
  * outside [0, nru) are never read); id_min .. distfun_host (S x 10, host): as in chicdiff_hip_fragment_background_dev.
  * d_N (int32) and d_FullMean (double) are n x S column-major (column s = replicate s); either may be NULL, and then the key
  * tables respectively the background tables are not read and may be NULL too.  1 <= S <= 64.
- * The branch without chinput files (chicdiff_hip_count_join_inner_dev: a pair counts only where every replicate holds it) is
- * NOT covered: it keeps the three calls.
+ * The branch without chinput files (a pair counts only where every replicate holds it) is served through
+ * chicdiff_hip_count_tables_merge_dev: this call on the merged tables equals chicdiff_hip_count_join_inner_dev and the two
+ * calls after it on the original ones.
  * Test option "region_assemble_generic" (chicdiff_hip_set_option) 0 (default) | 1: every tile of regions takes the kernel's
  * generic path (one region per lane, a search of the whole table per row), which otherwise serves tiles whose 46 regions hold
  * more than 512 rows: same bits. */
@@ -288,6 +289,28 @@ int chicdiff_hip_region_assemble_dev(chicdiff_hip_ctx *ctx, const int32_t *d_ru_
 int chicdiff_hip_count_join_inner_dev(chicdiff_hip_ctx *ctx, const int32_t *d_ru_bait, const int32_t *d_ru_oe, int64_t nru,
                                       int32_t S, const int64_t *const *d_keys, const int32_t *const *d_vals,
                                       const int64_t *nkeys, int32_t *d_out);
+
+/* a1, branch without chinput files, the merge alone (chicdiff.R:778, the Reduce(merge) of :774-807 and of :1202-1260 in
+ * getFullRegionData2):
+ *   mergedFiles <- Reduce(merge, tempForCounts)
+ * is merge()'s default INNER join on (baitID, otherEndID) over the S replicates' tables: the pairs that EVERY table holds, each
+ * with its S counts (N.x, N.y, ... one column per replicate).  It does not depend on the region universe, so one call serves
+ * every region set.  A pair is held by a table when its key is there, whatever its count: N = 0 is a count.
+ * In: d_keys / d_vals / nkeys, HOST arrays of S entries as in chicdiff_hip_count_join_multi_dev (device pointers inside): one
+ * key table per replicate as chicdiff_hip_count_table_dev builds it.  Precondition, as for chicdiff_hip_count_join_dev and
+ * not checked: every table's keys are ascending and unique.
+ * Out: d_keys_out[0 .. *n_out) = the keys present in all S tables, ascending; d_vals_out[s * cap + i] = table s's value at
+ * d_keys_out[i]; *n_out (host) = their number, <= min_s nkeys[s].  Entries from *n_out on are not written.
+ * Contract: chicdiff_hip_count_join_multi_dev / chicdiff_hip_region_assemble_dev on the merged tables (d_keys_out with column
+ * s, *n_out keys, for replicate s) equal chicdiff_hip_count_join_inner_dev (-> chicdiff_hip_fragment_background_dev ->
+ * chicdiff_hip_window_sums_dev) on the original ones bit for bit.
+ * The result does not depend on the order of launches or of arrival: rows are placed by a scan, nothing passes through an atomic.
+ * Limits: 1 <= S <= 64; cap >= min_s nkeys[s], otherwise CHICDIFF_E_INVALID and nothing is written; no pointer may be NULL
+ * (a table's pointers may be where its nkeys is 0, the outputs where the smallest table is empty: then *n_out = 0).  The outputs
+ * must not overlap the inputs or each other.  Scratch comes from the context's grow-only workspace.  With timing on the stages
+ * are "count_merge_mark", "count_merge_scan" and "count_merge_write". */
+int chicdiff_hip_count_tables_merge_dev(chicdiff_hip_ctx *ctx, int32_t S, const int64_t *const *d_keys, const int32_t *const *d_vals,
+                                        const int64_t *nkeys, int64_t cap, int64_t *d_keys_out, int32_t *d_vals_out, int64_t *n_out);
 
 /* IHWcorrection's covariate (chicdiff.R:1965-1967 for the test set, :1980-1982 for the control set):
  *   RU.distances <- RU.recast[, list(avDist = mean(distSign)), by = "regionID"]
