@@ -570,8 +570,18 @@ class HipContext:
         self._check(self.lib.chicdiff_hip_set_stream(self.h, C.c_void_p(stream.cuda_stream)))
 
     def set_option(self, name: str, value: int):
-        """Tuning / test options: every name and range is listed above chicdiff_hip_set_option in include/chicdiff_hip.h
-        (results never depend on them); an unknown name or a value outside its range raises ChicdiffHipError."""
+        """Tuning / test options: every name and range is listed above chicdiff_hip_set_option in include/chicdiff_hip.h; an
+        unknown name or a value outside its range raises ChicdiffHipError.
+
+        Most options are bit-neutral.  These select another summation order and so move results at the 1e-13 level (a row in
+        about 1e5 then stops its line search a step apart): ``trend_one_launch_per_pass`` and
+        ``sharded_trend_gather`` (the trend's sums over another partition of the rows), ``theta_grid_concurrency`` (with more than
+        one fit in flight the fits of a theta grid run the trend as one launch per pass; one fit in flight, or a one-point grid,
+        is the default single fit by bits, and any two settings above 1 agree by bits), ``trend_persistent_blocks`` (the
+        partition of the single-launch trend kernel) and ``wald_final_row_constant`` (``deviance`` and ``sumDeviance`` only).
+        ``trend_mad_in_kernel = 0`` keeps the trend's bits and was found bit-identical in ``varLogDispEsts`` and the prior
+        variance as well (tests/test_gpu_theta_scan.py).  ``local_trend_substitute`` changes the outcome of a fit whose
+        parametric trend fails, as DESeq2's fitType does."""
         self._check(self.lib.chicdiff_hip_set_option(self.h, name.encode(), int(value)))
 
     def enable_timing(self, on=True):

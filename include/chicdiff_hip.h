@@ -78,8 +78,17 @@ int chicdiff_hip_set_allgather(chicdiff_hip_ctx *ctx, chicdiff_allgather_fn fn, 
  * call reports the same number — each verdict is all-reduced before anybody acts on it. */
 int32_t chicdiff_hip_last_refits(const chicdiff_hip_ctx *ctx);
 
-/* Tuning / test options; results never depend on them, the defaults are what bench.py measures.  (Every option the library
- * accepts, in the order of its table — kOptions in chicdiff_amd/csrc/ctx.hip; any other name or value is CHICDIFF_E_INVALID.)
+/* Tuning / test options; the defaults are what bench.py measures.  (Every option the library accepts, in the order of its
+ * table — kOptions in chicdiff_amd/csrc/ctx.hip; any other name or value is CHICDIFF_E_INVALID.)
+ * Results and options: five options select another summation order and so move results at the 1e-13 level (about one row in
+ * 1e5 then stops a line search one step apart) — "trend_one_launch_per_pass" and "sharded_trend_gather"
+ * (the trend's sums over another partition of the rows), "theta_grid_concurrency" through the route of its lanes (more than one
+ * fit in flight: every fit of the grid has its trend as one launch per pass, and is the single fit under
+ * "trend_one_launch_per_pass" = 1 bit for bit, whatever the number of lanes; one fit in flight or a one-point grid: the default
+ * single fit, bit for bit), "trend_persistent_blocks" (the partition of the single-launch trend kernel) and
+ * "wald_final_row_constant" (`deviance` and `sumDeviance` alone).  Every other option is bit-neutral ("same bits" below), but for
+ * "local_trend_substitute" at the end of the list.  tests/test_gpu_theta_scan.py holds the lanes' route to the 50-digit twin and
+ * the grid to the single fits.
  *   "line_search_spread"        1 (default) | 0 | 2 | 3: evaluate straggler rows (line searches and IRLS) with their samples spread across
  *                               lanes; 0 = row per lane only; 2 = as 1 without the lean tick of the launch's end, 3 = as 1 without the layouts of
  *                               more than 128 exchange entries (bit-identity tests)
